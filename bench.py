@@ -13,11 +13,25 @@ golden snapshot -- exact), outcome histogram, and the RCCL
 all-reduce of the histogram (the campaign's only exchange; N > 1).
 Trials shard by id across ranks (weak scaling: per-GPU work fixed).
 
-The same line carries the other C2 workload (qsort, 100k trials per GPU) and
-C3's per-GPU shard (intmix, 125k trials per GPU) under "workloads", each with
-its own steps, roofline, cold start and (N = 1) a >= 20k-trial parity leg.
+A plain run does only what the headline figure needs: load + golden run,
+the translated kernels (from the code-object cache when it holds them),
+`--warmup` + `--steps` steps, the result line.  The per-kernel roofline in it
+is read from the timed steps' own counters and event timers.
 
-Launch: python bench.py [--gpus 1] [--steps 5] [--warmup 1]
+With --full the same line also carries the cold start (no code-object cache:
+golden run, then the first step while the translated kernels build), the CPU
+baseline and (N = 1) the parity leg against the oracle, and the other C2
+workload (qsort, 100k trials per GPU) and C3's per-GPU shard (intmix, 125k
+trials per GPU) under "workloads", each with its own steps, roofline, cold
+start and (N = 1) a >= 20k-trial parity leg.
+
+--dump-outputs DIR writes what the last timed step returned (rank 0):
+DIR/outcomes.npy, float64 [rows, 7] = trial id, cls, sub, exit_code, flags,
+detail, ninst of the step's trials (all of them up to 1M, else a fixed seeded
+sample of 1M rows), and DIR/histogram.npy, float64 = the node histogram's
+counts, crash_sub, escape_sub, trials, guest_insts, flattened in that order.
+
+Launch: python bench.py [--gpus 1] [--steps 5] [--warmup 1] [--full] [--dump-outputs DIR]
         python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
 """
 from __future__ import annotations
@@ -45,6 +59,11 @@ def parse():
     ap.add_argument("--workload", default="crc32")
     ap.add_argument("--trials", type=int, default=100_000, help="trials per GPU per step")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED0002)
+    ap.add_argument("--full", action="store_true",
+                    help="also: cold start without the code-object cache, CPU baseline + parity against the "
+                         "oracle, the further workloads (the options below that name them apply with --full)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0: write the last timed step's outcomes and node histogram as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline sample budget")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--parity-trials", type=int, default=0,
@@ -132,40 +151,66 @@ def load_traffic(path, workload, trials, lanes):
     return {}
 
 
+def dump_outputs(directory, d_out, node_h, first, T, max_rows=1_000_000):
+    """The last timed step's results as float64 .npy files: the per-trial
+    outcomes (trial id first; a fixed seeded sample of `max_rows` rows past
+    that many trials, which keeps the files under 64 MB) and the node
+    histogram's result fields."""
+    from shrewd_amd.fi import OUTCOME_DT
+    os.makedirs(directory, exist_ok=True)
+    out = np.frombuffer(d_out.cpu().numpy().tobytes(), OUTCOME_DT)[:T]
+    rows = np.arange(T)
+    if T > max_rows:
+        rows = np.sort(np.random.default_rng(0x5EED0D).choice(T, max_rows, replace=False))
+    cols = [(first + rows).astype(np.float64)]
+    cols += [out[f][rows].astype(np.float64) for f in ("cls", "sub", "exit_code", "flags", "detail", "ninst")]
+    np.save(os.path.join(directory, "outcomes.npy"), np.stack(cols, axis=1))
+    hist = [np.asarray(node_h[f], np.float64).ravel()
+            for f in ("counts", "crash_sub", "escape_sub", "trials", "guest_insts")]
+    np.save(os.path.join(directory, "histogram.npy"), np.concatenate(hist))
+
+
 def run_workload(a, name, T, steps, warmup, rank, world, dev, cpu_seconds, min_parity):
-    """One workload's bench record: cold start (golden run, the first campaign
-    step while the translated kernels build in the background), then `warmup`
-    + `steps` timed steps of T trials per GPU on the translated kernels, the
-    per-kernel roofline, and (N = 1) the CPU baseline + parity leg."""
+    """One workload's bench record: load + golden run and the translated
+    kernels, then `warmup` + `steps` timed steps of T trials per GPU on them
+    and the per-kernel roofline those steps' counters give.  With --full also
+    the cold start (the first campaign step while the translated kernels build
+    in the background, no code-object cache) and (N = 1) the CPU baseline +
+    parity leg."""
     import torch
     import torch.distributed as dist
     from shrewd_amd import ESCAPE_NAMES, HIST_DT, Engine
     from shrewd_amd.fi import CFG_JIT_NO_CACHE, escape_breakdown
     with open(os.path.join(ROOT, "workloads", f"{name}.elf"), "rb") as f:
         elf = f.read()
-    # no code-object cache: the cold start below is the one a fresh campaign pays
+    # --full: no code-object cache, the cold start below is the one a fresh campaign pays
     eng = Engine(device=dev.index, max_trials_per_launch=max(T, 1024), lanes_per_wave=a.lanes,
-                 resume_lanes=a.resume_lanes, epoch_iters=a.epoch_iters, epochs=a.epochs, flags=CFG_JIT_NO_CACHE)
+                 resume_lanes=a.resume_lanes, epoch_iters=a.epoch_iters, epochs=a.epochs,
+                 flags=CFG_JIT_NO_CACHE if a.full else 0)
     lanes = eng.config()["lanes_per_wave"]
-    # ---- cold start: load + golden run (+ snapshots, liveness, translation
-    # text) until trials can run; the first step runs while the translated
-    # kernels build (static kernels, 16k-trial chunks, switching when it lands)
+    # ---- load + golden run (+ snapshots, liveness, translation text) until
+    # trials can run
     t0 = time.perf_counter()
     eng.load_elf(elf, [name])
     g = eng.golden_run(wait_translation=False)
     golden_s = time.perf_counter() - t0
     eng.set_campaign(a.seed, REGS_PC, 1)
-    t1 = time.perf_counter()
-    eng.run_trials(rank * T, T, want_outcomes=False)
-    first_step_s = time.perf_counter() - t1
+    cold = None
+    if a.full:
+        # ---- cold start: the first step runs while the translated kernels
+        # build (static kernels, 16k-trial chunks, switching when it lands)
+        t1 = time.perf_counter()
+        eng.run_trials(rank * T, T, want_outcomes=False)
+        first_step_s = time.perf_counter() - t1
     g = eng.wait_translation()
     jit_ready_s = time.perf_counter() - t0
-    cold = {"golden_s": golden_s, "first_step_s": first_step_s,
-            "campaign_s": golden_s + first_step_s, "campaign_trials_per_s": T / (golden_s + first_step_s),
-            "translated_ready_s": jit_ready_s, "translate_us": int(g.translate_us),
-            "translated_blocks": int(g.translated_blocks),
-            "note": "load + golden run, then one step of T trials through the product path while the "
-                    "translated kernels build in the background (no code-object cache)"}
+    if a.full:
+        cold = {"golden_s": golden_s, "first_step_s": first_step_s,
+                "campaign_s": golden_s + first_step_s, "campaign_trials_per_s": T / (golden_s + first_step_s),
+                "translated_ready_s": jit_ready_s, "translate_us": int(g.translate_us),
+                "translated_blocks": int(g.translated_blocks),
+                "note": "load + golden run, then one step of T trials through the product path while the "
+                        "translated kernels build in the background (no code-object cache)"}
 
     d_out = torch.empty(T * 16, dtype=torch.uint8, device=dev)
     hist_words = HIST_DT.itemsize // 8
@@ -211,6 +256,8 @@ def run_workload(a, name, T, steps, warmup, rank, world, dev, cpu_seconds, min_p
     node_h = np.frombuffer(d_hist_node.cpu().numpy().tobytes(), HIST_DT)[0]
     if rank == 0 and a.hist_out and name == a.workload:
         np.save(a.hist_out, np.array([node_h], HIST_DT))
+    if rank == 0 and a.dump_outputs and name == a.workload:
+        dump_outputs(a.dump_outputs, d_out, node_h, rank * T, T)
     if rank != 0:
         eng.close()
         return None
@@ -253,8 +300,20 @@ def run_workload(a, name, T, steps, warmup, rank, world, dev, cpu_seconds, min_p
                              # solo-odd kernel also holds its wait for CU slots the solo
                              # kernel on the other stream occupies
                              "device_busy_ms": sum(busy_k) / len(busy_k) if busy_k else None}
-    dom = max(per_kernel, key=lambda n: per_kernel[n]["ms_per_step"])
-    D = per_kernel[dom]
+    # the engine keeps the dispatch timers in a ring: once a long run's
+    # dispatches have lapped it, what is left is no whole number of steps and
+    # says nothing per step (the run's own figures above do not depend on it)
+    roofline = None
+    if per_kernel and len(kinds) >= steps and len(kinds) % steps == 0:
+        dom = max(per_kernel, key=lambda n: per_kernel[n]["ms_per_step"])
+        D = per_kernel[dom]
+        roofline = {"bound": "hbm", "achieved": D["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": D["frac"], "traffic": D["traffic"], "kernel": dom,
+                    "avg_kernel_ms": D["avg_kernel_ms"], "dispatches_per_step": D["dispatches_per_step"],
+                    "algorithmic_bytes_per_launch": D["algorithmic_bytes_per_launch"],
+                    # the roof that binds: issue slots (SQ counters of the same
+                    # command, profiles/)
+                    "issue": D["issue"], "per_kernel": per_kernel}
     cls = node_h["counts"].sum(axis=(0, 1))
     rec = {
         "value": trials_total / elapsed,
@@ -271,22 +330,18 @@ def run_workload(a, name, T, steps, warmup, rank, world, dev, cpu_seconds, min_p
         # actually executed
         "guest_inst_per_s_gem5_equiv": int(node_h["guest_insts"]) * steps / elapsed,
         "device_inst_per_s": int(node_h["device_insts"]) * steps / elapsed,
-        "roofline": {"bound": "hbm", "achieved": D["achieved"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": D["frac"], "traffic": D["traffic"], "kernel": dom,
-                     "avg_kernel_ms": D["avg_kernel_ms"], "dispatches_per_step": D["dispatches_per_step"],
-                     "algorithmic_bytes_per_launch": D["algorithmic_bytes_per_launch"],
-                     # the roof that binds: issue slots (SQ counters of the same
-                     # command, profiles/)
-                     "issue": D["issue"], "per_kernel": per_kernel},
+        "roofline": roofline,
         "outcomes": {n: int(cls[i]) for i, n in enumerate(["masked", "sdc", "crash", "hang", "detected", "escape"])},
         "escape_sub": {ESCAPE_NAMES.get(i, str(i)): int(node_h["escape_sub"][i]) for i in range(8)
                        if node_h["escape_sub"][i]},
-        "cold_start": cold,
         "golden_s": golden_s,
+        "translated_ready_s": jit_ready_s,
         "parity": None,
         "cpu_baseline": None,
     }
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full:
+        rec["cold_start"] = cold
+    if a.full and world == 1 and not a.no_cpu_baseline:
         rec["cpu_baseline"], ref = cpu_baseline(elf, name, a.seed, cpu_seconds, min_parity)
         rec["cold_start"]["campaign_vs_cpu_baseline"] = cold["campaign_trials_per_s"] / rec["cpu_baseline"]["value"]
         # the same trial ids through the device (the timed campaign's first
@@ -321,10 +376,10 @@ def main():
 
     head = run_workload(a, a.workload, a.trials, a.steps, a.warmup, rank, world, dev, a.cpu_seconds,
                         a.parity_trials)
-    # the other C2 / C3 workloads on the same line (BASELINE.json configs[1], [2]):
+    # --full: the other C2 / C3 workloads on the same line (BASELINE.json configs[1], [2]):
     # qsort 100k trials per GPU, intmix 125k per GPU (C3's 1M over 8 GPUs)
     extra = {}
-    for spec in [w for w in a.workloads.split(",") if w]:
+    for spec in [w for w in a.workloads.split(",") if w and a.full]:
         name, _, rest = spec.partition(":")
         T, _, steps = rest.partition(":")
         T, steps = int(T or a.trials), int(steps or a.steps)

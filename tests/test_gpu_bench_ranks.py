@@ -45,10 +45,20 @@ def test_bench_two_ranks_gloo(tmp_path):
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     two = _line(r.stdout)
     h1 = str(tmp_path / "h1.npy")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--trials", str(2 * T), "--hist-out", h1]
-                       + common, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
+    d1 = str(tmp_path / "d1")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--trials", str(2 * T), "--hist-out", h1,
+                        "--dump-outputs", d1] + common, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
     one = _line(r.stdout)
+    # --dump-outputs: the last step's outcomes (trial id first) and the histogram's result fields
+    out, hist = np.load(os.path.join(d1, "outcomes.npy")), np.load(os.path.join(d1, "histogram.npy"))
+    assert out.dtype == np.float64 and out.shape == (2 * T, 7) and hist.dtype == np.float64
+    assert np.array_equal(out[:, 0], np.arange(2 * T))
+    assert np.bincount(out[:, 1].astype(int), minlength=6).tolist() == list(one["outcomes"].values())
+    h = np.load(h1).astype(HIST_DT)[0]
+    assert np.array_equal(hist, np.concatenate([np.asarray(h[f], np.float64).ravel() for f in
+                                                ("counts", "crash_sub", "escape_sub", "trials", "guest_insts")]))
+    assert out[:, 6].sum() == float(h["guest_insts"])
     a, b = np.load(h2).astype(HIST_DT)[0], np.load(h1).astype(HIST_DT)[0]
     for f in ("counts", "crash_sub", "escape_sub", "trials", "guest_insts"):
         assert np.array_equal(a[f], b[f]), f

@@ -5,10 +5,11 @@ import sys
 
 
 def line(name, r):
-    c = r.get("cold_start", {})
+    c = r.get("cold_start") or {}    # (bench.py --full)
     p = r.get("parity") or {}
+    rf = r.get("roofline") or {}
     return (f"{name:7s} {r['value']:>12,.0f} trials/s  {r['ms_per_step']:9.2f} ms/step  "
-            f"{r['roofline']['kernel']} frac {r['roofline']['frac']:.4f}  "
+            f"{rf.get('kernel')} frac {rf.get('frac', 0):.4f}  "
             f"golden {c.get('golden_s', 0):.2f}s first-step {c.get('first_step_s', 0):.2f}s "
             f"jit-ready {c.get('translated_ready_s', 0):.1f}s  "
             f"parity {p.get('checked')}/{p.get('mismatches')}  esc {r.get('escape_sub')}")

@@ -12,7 +12,7 @@ if [ "$SEL" != none ]; then
 fi
 export SHREWD_FI_JIT_CACHE=$PWD/gpurun_out/jitcache
 for lib in $LIBS; do
-    SHREWD_FI_LIB=$PWD/shrewd_amd/_lib/$lib timeout -k 10 400 python -u bench.py --no-cpu-baseline \
+    SHREWD_FI_LIB=$PWD/shrewd_amd/_lib/$lib timeout -k 10 400 python -u bench.py --full --no-cpu-baseline \
         > gpurun_out/bench_${TAG}_$lib.json 2> gpurun_out/bench_${TAG}_$lib.err || exit $?
     echo "== $lib"; python tools/bench_summary.py gpurun_out/bench_${TAG}_$lib.json
 done

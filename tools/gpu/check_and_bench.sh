@@ -14,5 +14,8 @@ if [ "$SEL" != "none" ]; then
     rc=$?; tail -3 gpurun_out/pytest_gpu_$TAG.log; grep -E "FAILED|Error" gpurun_out/pytest_gpu_$TAG.log | head -5
     [ $rc -eq 0 ] || exit $rc
 fi
-timeout -k 10 400 python -u bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err || exit $?
-python tools/bench_summary.py gpurun_out/bench_$TAG.json
+# the bench line goes to $BENCH_OUT (default build/bench, which git ignores)
+B=${BENCH_OUT:-build/bench}
+mkdir -p $B
+timeout -k 10 400 python -u bench.py --full > $B/bench_$TAG.json 2> $B/bench_$TAG.err || exit $?
+python tools/bench_summary.py $B/bench_$TAG.json

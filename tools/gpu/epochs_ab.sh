@@ -8,7 +8,7 @@ O=gpurun_out/epochs_$TAG.jsonl
 export SHREWD_FI_JIT_CACHE=$PWD/gpurun_out/jitcache
 for v in $2; do
     ep=${v%%:*}; it=${v#*:}
-    timeout -k 10 300 python -u bench.py --no-cpu-baseline --workloads "$W" --extra-parity 0 --epochs $ep --epoch-iters $it \
+    timeout -k 10 300 python -u bench.py --full --no-cpu-baseline --workloads "$W" --extra-parity 0 --epochs $ep --epoch-iters $it \
         > gpurun_out/epochs_${TAG}_$ep_$it.json 2> gpurun_out/epochs_$TAG.err || exit $?
     python - >> $O <<PY
 import json

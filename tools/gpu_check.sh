@@ -6,6 +6,9 @@ export SHREWD_FI_JIT_CACHE=$PWD/gpurun_out/jitcache
 timeout -k 10 500 python -u -m pytest tests -m gpu -x -v --timeout 200 --timeout-method thread > gpurun_out/pytest_gpu.log 2>&1; rc=$?
 tail -5 gpurun_out/pytest_gpu.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python -u bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err; rc=$?
-cat gpurun_out/bench.json; tail -3 gpurun_out/bench.err
+# the bench line goes to $BENCH_OUT (default build/bench, which git ignores)
+B=${BENCH_OUT:-build/bench}
+mkdir -p $B
+timeout -k 10 400 python -u bench.py --full > $B/bench.json 2> $B/bench.err; rc=$?
+cat $B/bench.json; tail -3 $B/bench.err
 exit $rc

@@ -11,7 +11,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 export SHREWD_FI_JIT_CACHE=$O/jitcache
 cd /tmp
-timeout -k 10 400 python $R/bench.py > $O/bench_$TAG.json 2> $O/bench_$TAG.err &&
+timeout -k 10 400 python $R/bench.py --full > $O/bench_$TAG.json 2> $O/bench_$TAG.err &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_trace_$TAG -o trace --output-format csv -- \
     python $R/bench.py --steps $STEPS --warmup 1 --no-cpu-baseline --workloads "" > $O/prof_trace_$TAG.log 2>&1 &&
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $O/prof_fetch_$TAG -o fetch --output-format csv -- \
