@@ -1563,12 +1563,6 @@ __device__ __forceinline__ bool ult64(uint64_t a, uint64_t b) {
     return ah < bh || (ah == bh && (uint32_t)a < (uint32_t)b);
 }
 
-#ifndef FI_SOLO_VLOAD   // clean solo body: vector loads from shared frames too (0: scalar loads there; profiles/r06 A/B)
-#define FI_SOLO_VLOAD 1
-#endif
-#ifndef FI_SOLO_CPB     // clean solo body: site caches hold frame - page address (0: the TLB entry)
-#define FI_SOLO_CPB 1
-#endif
 typedef __attribute__((address_space(3))) uint64_t lds_u64;
 typedef __attribute__((address_space(3))) LaneMem lds_mem;
 
@@ -1834,24 +1828,15 @@ __device__ __noinline__ void solo_tx_clean_run(KCtx *CX, lds_u64 *R, lds_mem *mp
     TXR(26) TXR(27) TXR(28) TXR(29) TXR(30) TXR(31)
 #undef TXR
     // the site caches (fi_translate.cpp): the page number CV of the last page a
-    // site touched and its TLB entry CP (frame | private bit) -- or, with
-    // FI_SOLO_CPB, the frame minus the page's own address (a hit is one add)
-    // and the private bit apart in CQ
-#if FI_SOLO_CPB
+    // site touched, in CP its frame minus the page's own address (a hit is one
+    // add) and in CQ the private bit of its TLB entry
 #define SC_SET(i, vp, e) (CV##i = (vp), CP##i = ((e) & ~1ULL) - ((vp) << 12), CQ##i = (uint32_t)(e) & 1u)
 #define SC_PTR(i, ea) ((uint8_t *)(uintptr_t)(CP##i + (ea)))
 #define SC_PRIV(i) (CQ##i != 0u)
-#else
-#define SC_SET(i, vp, e) (CV##i = (vp), CP##i = (e))
-#define SC_PTR(i, ea) ((uint8_t *)(uintptr_t)((CP##i & ~1ULL) + ((ea) & 4095u)))
-#define SC_PRIV(i) ((CP##i & 1u) != 0)
-#endif
-#if FI_SOLO_VLOAD
     // every translated load through the vector memory path (shared frames are
     // read-only during a launch: either path reads the same bytes)
 #undef SPRIV
 #define SPRIV(x) ((x) || true)
-#endif
     TX_TEMPS();
     goto S_entry;
     /*@TX_SOLO_CLEAN@*/
@@ -3335,6 +3320,40 @@ __device__ __forceinline__ bool slt64(uint64_t a, uint64_t b) {
 }
 __device__ __forceinline__ uint64_t r64(const lds_u64 *R, uint32_t r) { return uni64(R[r]); }
 
+// The micro-op ALU group (rv64_isa.h Kind: K_SUB ... K_REMU; M-extension high
+// products and division as utility.hh:171-231), written once for the three
+// pre-decoded loops: the solo interpreter (solo_pre_run), the SIMT step loop
+// and the 64-lane pre-decoded loop.  Expands to case labels of the site's own
+// switch over the kind, on its av, bv, w32 and shm, result in v.  SLT / ULT
+// are the site's signed / unsigned 64-bit a < b: slt64 / ult64 where the
+// operands are wave-uniform, the plain compares elsewhere.
+#define FI_SLT_PLAIN(a, b) ((int64_t)(a) < (int64_t)(b))
+#define FI_ULT_PLAIN(a, b) ((a) < (b))
+#define FI_UOP_ALU_CASES(SLT, ULT)                                                                      \
+    case K_SUB: v = av - bv; break;                                                                     \
+    case K_AND: v = av & bv; break;                                                                     \
+    case K_OR: v = av | bv; break;                                                                      \
+    case K_XOR: v = av ^ bv; break;                                                                     \
+    case K_SLT: v = SLT(av, bv) ? 1 : 0; break;                                                         \
+    case K_SLTU: v = ULT(av, bv) ? 1 : 0; break;                                                        \
+    case K_SLL: v = av << (bv & shm); break;                                                            \
+    case K_SRL: v = (w32 ? (av & 0xFFFFFFFFULL) : av) >> (bv & shm); break;                             \
+    case K_SRA: v = (uint64_t)((w32 ? (int64_t)(int32_t)av : (int64_t)av) >> (bv & shm)); break;        \
+    case K_MUL: v = av * bv; break;                                                                     \
+    case K_MULH: v = (uint64_t)__mul64hi((int64_t)av, (int64_t)bv); break;                              \
+    case K_MULHU: v = __umul64hi(av, bv); break;                                                        \
+    case K_MULHSU: v = __umul64hi(av, bv) - (((int64_t)av < 0) ? bv : 0); break;                        \
+    case K_DIV: v = w32 ? divw(av, bv) : div64(av, bv); break;                                          \
+    case K_DIVU:                                                                                        \
+        v = w32 ? ((uint32_t)bv == 0 ? ~0ULL : sx32((uint32_t)av / (uint32_t)bv))                       \
+                : (bv == 0 ? ~0ULL : av / bv);                                                          \
+        break;                                                                                          \
+    case K_REM: v = w32 ? remw(av, bv) : rem64(av, bv); break;                                          \
+    case K_REMU:                                                                                        \
+        v = w32 ? ((uint32_t)bv == 0 ? sx32(av) : sx32((uint32_t)av % (uint32_t)bv))                    \
+                : (bv == 0 ? av : av % bv);                                                             \
+        break;
+
 template <bool kOdd>
 __device__ __noinline__ void solo_pre_run(KCtx *CX, lds_u64 *R, lds_mem *mp, lds_u32 *DCT, lds_pre4 *DCE,
                                           lds_u32 *LC, lds_pio *io) {
@@ -3590,30 +3609,10 @@ __device__ __noinline__ void solo_pre_run(KCtx *CX, lds_u64 *R, lds_mem *mp, lds
                 if (c) { npc = pc + imm; jump = true; }
                 break;
             }
-            case K_SUB: v = av - bv; break;
-            case K_AND: v = av & bv; break;
-            case K_OR: v = av | bv; break;
-            case K_XOR: v = av ^ bv; break;
-            case K_SLT: v = slt64(av, bv) ? 1 : 0; break;
-            case K_SLTU: v = ult64(av, bv) ? 1 : 0; break;
-            case K_SLL: v = av << (bv & shm); break;
-            case K_SRL: v = (w32 ? (av & 0xFFFFFFFFULL) : av) >> (bv & shm); break;
-            case K_SRA: v = (uint64_t)((w32 ? (int64_t)(int32_t)av : (int64_t)av) >> (bv & shm)); break;
+            FI_UOP_ALU_CASES(slt64, ult64)
             case K_JAL: v = pc + len; npc = pc + imm; jump = true; break;
             case K_JALR: v = pc + len; npc = (a0 + imm) & ~1ULL; jump = true; break;
             case K_NOP: wr = false; break;
-            case K_MUL: v = av * bv; break;
-            case K_MULH: v = (uint64_t)__mul64hi((int64_t)av, (int64_t)bv); break;
-            case K_MULHU: v = __umul64hi(av, bv); break;
-            case K_MULHSU: v = __umul64hi(av, bv) - (((int64_t)av < 0) ? bv : 0); break;
-            case K_DIV: v = w32 ? divw(av, bv) : div64(av, bv); break;
-            case K_DIVU:
-                v = w32 ? ((uint32_t)bv == 0 ? ~0ULL : sx32((uint32_t)av / (uint32_t)bv)) : (bv == 0 ? ~0ULL : av / bv);
-                break;
-            case K_REM: v = w32 ? remw(av, bv) : rem64(av, bv); break;
-            case K_REMU:
-                v = w32 ? ((uint32_t)bv == 0 ? sx32(av) : sx32((uint32_t)av % (uint32_t)bv)) : (bv == 0 ? av : av % bv);
-                break;
             case K_SLOW: {   // an F/D/Zfh op (solo_fp_ok), out of line
                 uint32_t fm = 0;
                 const uint32_t r = solo_fp_op(CX, w, m, slot, R, io, q1, q2, v, fm);
@@ -3669,12 +3668,6 @@ leave:
 // crc32 (tools/gpu/solo_ab.sh, profiles/r02j_solo_ab.txt): 1 (no bound, 136-140
 // VGPRs, 3 waves) 6.44M, 4: 7.06M trials/s; VGPR-pinned guest registers
 // 3.2-3.7M.
-#ifndef FI_SOLO_DIRTY_PRIO   // solo waves of trials that rewrote code run at this priority (0: no change)
-#define FI_SOLO_DIRTY_PRIO 0
-#endif
-#ifndef FI_SOLO_AGE   // solo waves raise their priority at 2^k, 2^(k+1), 2^(k+2) instructions (0: off)
-#define FI_SOLO_AGE 0
-#endif
 #ifndef FI_SOLO_WAVES_PER_EU
 #define FI_SOLO_WAVES_PER_EU 4
 #endif
@@ -4112,13 +4105,6 @@ __device__ __forceinline__ void trial_body() {
             next_snap += CX->rec_interval;
         }
 
-#if FI_SOLO_DIRTY_PRIO
-        // a solo trial that rewrote its code runs interpreted, ~10x slower per
-        // instruction than translated code: the issue arbiter prefers it
-        if constexpr (kNL == 1) {
-            if (m.code_dirty) __builtin_amdgcn_s_setprio(FI_SOLO_DIRTY_PRIO);
-        }
-#endif
         const bool ready = !L.done && m.req_vpn == kNone;
         const uint64_t act = wballot<kNL>(ready);
         if (act == 0) {
@@ -4190,29 +4176,7 @@ __device__ __forceinline__ void trial_body() {
                             const uint32_t shm = w32 ? 31 : 63;
                             switch (kind) {
                             case K_ADD: v = av + bv; break;
-                            case K_SUB: v = av - bv; break;
-                            case K_AND: v = av & bv; break;
-                            case K_OR: v = av | bv; break;
-                            case K_XOR: v = av ^ bv; break;
-                            case K_SLT: v = (int64_t)av < (int64_t)bv ? 1 : 0; break;
-                            case K_SLTU: v = av < bv ? 1 : 0; break;
-                            case K_SLL: v = av << (bv & shm); break;
-                            case K_SRL: v = (w32 ? (av & 0xFFFFFFFFULL) : av) >> (bv & shm); break;
-                            case K_SRA: v = (uint64_t)((w32 ? (int64_t)(int32_t)av : (int64_t)av) >> (bv & shm)); break;
-                            case K_MUL: v = av * bv; break;
-                            case K_MULH: v = (uint64_t)__mul64hi((int64_t)av, (int64_t)bv); break;
-                            case K_MULHU: v = __umul64hi(av, bv); break;
-                            case K_MULHSU: v = __umul64hi(av, bv) - (((int64_t)av < 0) ? bv : 0); break;
-                            case K_DIV: v = w32 ? divw(av, bv) : div64(av, bv); break;
-                            case K_DIVU:
-                                v = w32 ? ((uint32_t)bv == 0 ? ~0ULL : sx32((uint32_t)av / (uint32_t)bv))
-                                        : (bv == 0 ? ~0ULL : av / bv);
-                                break;
-                            case K_REM: v = w32 ? remw(av, bv) : rem64(av, bv); break;
-                            case K_REMU:
-                                v = w32 ? ((uint32_t)bv == 0 ? sx32(av) : sx32((uint32_t)av % (uint32_t)bv))
-                                        : (bv == 0 ? av : av % bv);
-                                break;
+                            FI_UOP_ALU_CASES(FI_SLT_PLAIN, FI_ULT_PLAIN)
                             case K_NOP: wr = false; break;
                             case K_JAL: v = ft; npc = pc + imm; break;
                             case K_JALR: v = ft; npc = (a0 + imm) & ~1ULL; break;
@@ -4358,14 +4322,6 @@ __device__ __forceinline__ void trial_body() {
                     n_iter += st;
                     n_tx += st;
                     n_txin++;
-#if FI_SOLO_AGE
-                    // ageing: a solo trial that has run long is likely to run long
-                    // still (the campaign's tail); it gets the issue arbiter's
-                    // preference over the younger waves of its CU
-                    if (n_iter >= (4u << FI_SOLO_AGE)) __builtin_amdgcn_s_setprio(3);
-                    else if (n_iter >= (2u << FI_SOLO_AGE)) __builtin_amdgcn_s_setprio(2);
-                    else if (n_iter >= (1u << FI_SOLO_AGE)) __builtin_amdgcn_s_setprio(1);
-#endif
                     if (kOdd && L.ninst > CX->gninst && !uni32(sio->hang)) {
                         LP.cnt += st;
                         if (LP.cnt >= LP.at) lp_count((lds_lp *)&LP, CX, (const lds_u64 *)R, slot, L.pc, L.fp, LP_ELIGIBLE, 0u);
@@ -4634,28 +4590,7 @@ __device__ __forceinline__ void trial_body() {
                 bool wr = true, took = false, ind = false;
                 switch (kind) {
                 case K_ADD: v = av + bv; break;
-                case K_SUB: v = av - bv; break;
-                case K_AND: v = av & bv; break;
-                case K_OR: v = av | bv; break;
-                case K_XOR: v = av ^ bv; break;
-                case K_SLT: v = (int64_t)av < (int64_t)bv ? 1 : 0; break;
-                case K_SLTU: v = av < bv ? 1 : 0; break;
-                case K_SLL: v = av << (bv & shm); break;
-                case K_SRL: v = (w32 ? (av & 0xFFFFFFFFULL) : av) >> (bv & shm); break;
-                case K_SRA: v = (uint64_t)((w32 ? (int64_t)(int32_t)av : (int64_t)av) >> (bv & shm)); break;
-                case K_MUL: v = av * bv; break;
-                // M-extension high products and division (utility.hh:171-231)
-                case K_MULH: v = (uint64_t)__mul64hi((int64_t)av, (int64_t)bv); break;
-                case K_MULHU: v = __umul64hi(av, bv); break;
-                case K_MULHSU: v = __umul64hi(av, bv) - (((int64_t)av < 0) ? bv : 0); break;
-                case K_DIV: v = w32 ? divw(av, bv) : div64(av, bv); break;
-                case K_DIVU:
-                    v = w32 ? ((uint32_t)bv == 0 ? ~0ULL : sx32((uint32_t)av / (uint32_t)bv)) : (bv == 0 ? ~0ULL : av / bv);
-                    break;
-                case K_REM: v = w32 ? remw(av, bv) : rem64(av, bv); break;
-                case K_REMU:
-                    v = w32 ? ((uint32_t)bv == 0 ? sx32(av) : sx32((uint32_t)av % (uint32_t)bv)) : (bv == 0 ? av : av % bv);
-                    break;
+                FI_UOP_ALU_CASES(FI_SLT_PLAIN, FI_ULT_PLAIN)
                 case K_NOP: wr = false; break;
                 case K_JAL: v = ft; npc = spc + imm; took = true; break;
                 case K_JALR: {

@@ -730,19 +730,29 @@ def test_known_answer_programs(oracle_mod, prog):
     compare(dev, o.run_trials(sites, protect_mask=0), sites)
 
 
-@pytest.mark.parametrize("prog", ["alu", "cmp", "rvc", "mem"])
-def test_known_answer_programs_solo_interpreter(oracle_mod, prog):
-    """The known-answer programs from process start through the solo
-    pre-decoded interpreter only (FI_CFG_SOLO_ALL | NO_TRANSLATE |
-    NO_SNAPSHOT_START | NO_EARLY_EXIT): every op of the alu program -- the
+@pytest.mark.parametrize("prog,path", [pytest.param(p, q, id=p if q == "solo" else f"{p}-{q}")
+                                       for q in ("solo", "lanes", "simt") for p in ("alu", "cmp", "rvc", "mem")])
+def test_known_answer_programs_solo_interpreter(oracle_mod, prog, path):
+    """The known-answer programs from process start through one pre-decoded
+    interpreter only (NO_TRANSLATE | NO_SNAPSHOT_START | NO_EARLY_EXIT), once
+    per copy of the micro-op ALU group: every op of the alu program -- the
     M-extension edge pairs (x / 0, INT_MIN / -1, the W forms, mulh*) among
-    them -- runs in the assembly inner loop (solo_fast_run), no-fault trials
-    print the models and end masked, faulted trials match the oracle."""
+    them -- runs
+    solo: on the solo kernel (SOLO_ALL), in its assembly inner loop
+    (solo_fast_run);
+    lanes: in the 64-lane pre-decoded loop (NO_SOLO);
+    simt: the same with diverged lanes in the SIMT step loop (SIMT);
+    no-fault trials print the models and end masked, faulted trials match the
+    oracle."""
     from shrewd_amd import Engine
+    from shrewd_amd.fi import (CFG_NO_EARLY_EXIT, CFG_NO_SNAPSHOT_START, CFG_NO_SOLO, CFG_NO_TRANSLATE, CFG_SIMT,
+                               CFG_SOLO_ALL)
     import test_isa_vectors as kat
     elf = {"alu": kat.program_elf, "cmp": kat.cmp_program_elf, "rvc": kat.rvc_program_elf,
            "mem": kat.mem_program_elf}[prog]()
-    e = Engine(private_pages=64, flags=128 | 4 | 1 | 2)
+    start = CFG_NO_TRANSLATE | CFG_NO_SNAPSHOT_START | CFG_NO_EARLY_EXIT
+    flags = {"solo": CFG_SOLO_ALL | start, "lanes": CFG_NO_SOLO | start, "simt": CFG_NO_SOLO | CFG_SIMT | start}[path]
+    e = Engine(private_pages=64, flags=flags)
     e.load_elf(elf, [prog])
     e.golden_run()
     o = oracle_mod.Oracle(elf, prog)
@@ -759,7 +769,10 @@ def test_known_answer_programs_solo_interpreter(oracle_mod, prog):
     dev, _ = e.run_sites(sites)
     compare(dev, o.run_trials(sites, protect_mask=0), sites)
     st = e.debug_stats()
-    assert int(st[54]) > 0, "the assembly inner loop did not run"
+    if path == "solo":
+        assert int(st[54]) > 0, "the assembly inner loop did not run"
+    if path == "simt":
+        assert int(st[24]) > 0, "the SIMT step loop did not run"
     e.close()
 
 
