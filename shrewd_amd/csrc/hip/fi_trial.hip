@@ -5475,11 +5475,14 @@ __global__ void __launch_bounds__(64) fi_debug_loop_kernel(DevCtx, const fi_debu
     m.dlo = m.dhi = 0; m.resv = m.lock = kNone; m.vm = false; m.vcfg = 0; m.nmiss = 0; m.dl = nullptr;
     uint64_t k = 0, fva = 0;
     const int r = loop_outcome(kx, w, m, 0, d->regs, d, d->left, k, fva);
-    // the body's proof (TXHANG in solo_tx_clean_run) against hleft capped as the kernel caps it
+    // the body's proof (TXHANG in solo_tx_clean_run; TXHANGU for a region
+    // record, bit 24 of lp_cnt) against hleft capped as the kernel caps it
     const uint32_t cnt = d->lp_cnt, cr = cnt & 0xFF, tr = (cnt >> 8) & 0xFF;
+    const int cs = (int)(int8_t)(uint8_t)(cnt >> 16);
     const uint32_t hl = d->left > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d->left;
-    const bool body = cr && d->lp_m && tx_hang_proof(d->regs[cr] - (tr ? d->regs[tr] : 0ULL),
-                                                     (int)(int8_t)(uint8_t)(cnt >> 16), d->lp_m, hl);
+    const bool body = !cr || !d->lp_m ? false
+                      : (cnt >> 24) & 1 ? tr && cs > 0 && tx_hang_proof_u(d->regs[cr], d->regs[tr], cs, d->lp_m, hl)
+                                        : tx_hang_proof(d->regs[cr] - (tr ? d->regs[tr] : 0ULL), cs, d->lp_m, hl);
     fi_debug_loop_out o;
     o.verdict = r; o.body_proof = body ? 1u : 0u; o.k = k; o.fva = fva;
     out[i] = o;

@@ -500,6 +500,65 @@ def test_storeoff_loop_proofs(oracle_mod):
     assert ins_on < ins_off
 
 
+def test_region_kat_proofs(oracle_mod):
+    """The region program (tests/test_isa_vectors.py): three valid region loops
+    and eleven near-miss twins the translator must refuse, under faults on
+    each loop's counter, bound, table bases and ra, plus hand-placed sites
+    (region_explicit_sites).  Every record equals the oracle's, with the
+    proofs on and off.  With them on, hangs are proved (stats[56]) with fewer
+    instructions run, and the sites that move V0's store table into the text,
+    onto an unmapped page, or to the end of the data page with its last 64
+    bytes on the unmapped page after it (a check of the table's first page
+    alone would call that one a hang; the oracle has it page-fault ten passes
+    on) while lengthening the loop stay undecided (stats[58]: loop_outcome
+    kinds 1 / 5) and run on.  The counts below are
+    the oracle's for seed 13 and the 3000 random sites (valid-loop hangs 119, V0
+    bound flips of bit 12 and up 37, all hangs; V3's 34, none a hang; V6
+    crashes 119): a site set that exercised nothing cannot pass."""
+    from shrewd_amd import Engine
+    from shrewd_amd.fi import CFG_NO_HANG_PROOF
+    import test_isa_vectors as kat
+    elf = kat.region_program_elf()
+    o = oracle_mod.Oracle(elf, "region")
+    g = o.run_golden()
+    sites = kat.region_sites(g.ninst, kat.REGION_SITES_GPU)
+    ref = o.run_trials(sites, protect_mask=0)
+    # what the site set holds, from the oracle's records alone
+    nr = kat.REGION_SITES_GPU   # the random sites; the explicit ones follow
+    names = np.array(kat.region_site_variant(sites[:nr]))
+    cls = ref["cls"][:nr]
+    rs = sites[:nr]
+    valid_hangs = int((np.isin(names, kat.REGION_VALID) & (cls == 3)).sum())
+    v0_rl = (names == "V0") & (rs["target"] == 19) & (rs["mask"] >= 1 << 12)
+    v3_rl = (names == "V3") & (rs["target"] == 13) & (rs["mask"] >= 1 << 12)
+    assert valid_hangs == 119
+    assert int(v0_rl.sum()) == 37 and (cls[v0_rl] == 3).all()
+    assert int(v3_rl.sum()) == 34 and (cls[v3_rl] != 3).all()
+    assert int(((names == "V6") & (cls == 2)).sum()) == 119
+    by = kat.region_explicit_outcomes(ref[nr:])
+    assert [c for c, _ in by["v0_rl"]] == [3] * 5 and all(c != 3 for c, _ in by["v3_rl"]), by
+    assert by["base_text"][0][0] != 3 and by["base_unmapped"] == [(2, 3)] and by["base_straddle"] == [(2, 3)], by
+    assert by["base_text_far"] == [(3, 1)], by
+    got = []
+    for flags in (0, CFG_NO_HANG_PROOF):
+        e = Engine(flags=flags)
+        e.load_elf(elf, ["region"])
+        e.golden_run()
+        assert e.translate_status() == ""
+        dev, h = e.run_sites(sites)
+        compare(dev, ref, sites)
+        st = e.debug_stats()
+        got.append((int(st[56]), int(st[57]), int(st[58]), int(h["device_insts"])))
+        e.close()
+    print("region KAT (hangs proved, crashes proved, undecided, device insts): on", got[0], "off", got[1])
+    (hang_on, _, und_on, ins_on), (hang_off, crash_off, und_off, ins_off) = got
+    # each of V0's high bound flips is proved at its next entry into the loop; the
+    # moved-table sites that get there (base_text_far runs to the cap) stay undecided
+    assert hang_on >= int(v0_rl.sum()) and und_on > 0
+    assert hang_off == crash_off == und_off == 0
+    assert ins_on < ins_off
+
+
 def test_region_loop_proofs(engine_factory, oracle_mod):
     """intmix's loop bound s3 flipped high: the main loop (a call and table
     stores per pass) runs to the hang cap.  The region proof (fi_translate.cpp,

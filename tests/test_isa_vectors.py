@@ -2423,3 +2423,371 @@ def test_runoff_program_on_oracle(oracle_mod):
     assert o.golden_stdout() == runoff_program_expected()
     res = o.run_trials(runoff_sites(g.ninst, 400), protect_mask=0)
     assert (res["cls"] == 2).sum() > 20 and (res["sub"][res["cls"] == 2] == 3).any()
+
+
+# -------------------------------------------------------------- region program
+# Region proofs (fi_translate.cpp "region proofs", fi_trial.hip loop_outcome
+# with the region bit): one outer loop of the intmix shape per variant -- a
+# hash step, a call to a leaf that sums four bytes of a 256-byte table (s0),
+# a read-modify-write of a 64-word table (s1), `addi rc, rc, c; bltu rc, rl`
+# -- run one after the other.  V0 / V0c8 / V0c3 are valid region loops; every
+# other variant breaks exactly one rule of the region walk and must be refused:
+#   V1   the leaf returns with `jalr ra, 0(ra)` (c.jalr ra: it links ra)
+#   V2   the leaf calls a second leaf through t4 on odd passes (a nested call
+#        that a branch skips, so the leaf's `ret` stays reachable without it)
+#   V3   the leaf runs `andi rl, rl, 127`: nothing on the golden run, but a
+#        bound flipped high comes back under 128 -- the loop leaves
+#   V4   the leaf runs `addi ra, ra, 0` (ra written by more than the call)
+#   V5   an indirect call, `jalr ra, 0(tp)` (c.jalr tp)
+#   V5b  a `ret` in the loop's own blocks (never taken on the golden run)
+#   V6   the store's offset is a loaded word (lw t1; add t4, s1, t1; sw 0(t4))
+#   V7   rc written a second time (`addi rc, rc, 0` at the loop's head)
+#   V8a / V8b  the exit test is `bne` / `blt` in place of `bltu`
+#   V9   getpid inside the loop
+# V0's bound is derived from its store table's base (s3 = acc + 32 - s1, 32 on
+# the golden run).  A single fault flips one register; a flip of a table base
+# alone never makes the loop long, so the body's proof would not fire and
+# loop_outcome would never see the moved table.  A flip of s1 just before that
+# `sub` both moves the table and lengthens the loop: the explicit sites of
+# region_sites() use it to reach loop_outcome's refusals (a store table in the
+# code range, a table on an unmapped page, a table from a mapped page on to an
+# unmapped page).
+REGION_PASSES = 32
+REGION_SITES_CPU = 400    # random sites of the oracle leg (test_region_program_on_oracle)
+REGION_SITES_GPU = 3000   # ... of the device parity test (tests/test_gpu_parity.py)
+# name, rc, rl (register numbers), step, leaf
+REGION_LOOPS = [("V0", 18, 19, 1, "f0"), ("V0c8", 20, 21, 8, "f0"), ("V0c3", 22, 23, 3, "f0"),
+                ("V1", 24, 25, 1, "f1"), ("V2", 26, 27, 1, "f2"), ("V3", 12, 13, 1, "f3"),
+                ("V4", 30, 31, 1, "f4"), ("V5", 20, 21, 1, "fs"), ("V5b", 22, 23, 1, "fs"),
+                ("V6", 24, 25, 1, "fs"), ("V7", 26, 27, 1, "fs"), ("V8a", 12, 13, 1, "fs"),
+                ("V8b", 30, 31, 1, "fs"), ("V9", 18, 19, 1, "fs")]
+REGION_VALID = ("V0", "V0c8", "V0c3")
+
+
+def _region_limit(name, c):
+    return {8: 8 * REGION_PASSES, 3: 3 * REGION_PASSES - 2}.get(c, REGION_PASSES)
+
+
+def _region_leaf(name, extra="", ret="ret", tail=""):
+    return f"""{name}:
+    li    t0, 0
+    li    t1, 4
+{name}_l:
+    andi  t2, a0, 255
+    add   t2, t2, s0
+    lbu   t2, 0(t2)
+    add   t0, t0, t2
+    srli  a0, a0, 8
+    addi  t1, t1, -1
+    bnez  t1, {name}_l
+{extra}{tail}    mv    a0, t0
+    {ret}
+{name}_end:
+"""
+
+
+def region_program_source() -> str:
+    out = ["""    .text
+_start:
+    la    s0, tab0
+    la    s1, acc
+    li    t0, 0
+    li    t1, 256
+fill0:
+    add   t2, s0, t0
+    slli  t3, t0, 3
+    sub   t3, t3, t0
+    addi  t3, t3, 3
+    sb    t3, 0(t2)
+    addi  t0, t0, 1
+    bne   t0, t1, fill0
+    li    t0, 0
+    li    t1, 64
+fill1:
+    slli  t2, t0, 2
+    add   t2, t2, s1
+    slli  t3, t0, 2
+    add   t3, t3, t0
+    addi  t3, t3, 3
+    andi  t3, t3, 63
+    slli  t3, t3, 2
+    sw    t3, 256(t2)
+    addi  t0, t0, 1
+    bne   t0, t1, fill1
+    li    a5, 0x1234567
+"""]
+    for name, rc, rl, c, leaf in REGION_LOOPS:
+        rc, rl = f"x{rc}", f"x{rl}"
+        out.append(f"{name}_lo:\n    li    {rc}, 0\n")
+        if name == "V0":     # the bound from the store table's base (see above)
+            out.append(f"    la    t0, acc+{REGION_PASSES}\n    sub   {rl}, t0, s1\n")
+        else:
+            out.append(f"    li    {rl}, {_region_limit(name, c)}\n")
+        if name == "V5":
+            out.append("    la    tp, fs\n")
+        out.append(f"{name}:\n")
+        if name == "V7":
+            out.append(f"    addi  {rc}, {rc}, 0\n")
+        out.append(f"""    xor   a5, a5, {rc}
+    slli  t0, a5, 13
+    xor   a5, a5, t0
+    srli  t0, a5, 7
+    xor   a5, a5, t0
+    mv    a0, a5
+""")
+        out.append("    jalr  ra, 0(tp)\n" if name == "V5" else f"    jal   ra, {leaf}\n")
+        out.append(f"{name}_r:\n")
+        if name == "V5b":
+            out.append(f"    beq   {rl}, zero, V5b_ret\n")
+        out.append("    andi  t2, a5, 63\n    slli  t2, t2, 2\n    add   t2, t2, s1\n")
+        if name == "V6":
+            out.append("    lw    t1, 256(t2)\n    add   t4, s1, t1\n    lw    t3, 0(t4)\n    addw  t3, t3, a0\n"
+                       "    sw    t3, 0(t4)\n")
+        else:
+            out.append("    lw    t3, 0(t2)\n    addw  t3, t3, a0\n    sw    t3, 0(t2)\n")
+        if name == "V9":
+            out.append("    li    a7, 172\n    ecall\n")
+        br = {"V8a": "bne", "V8b": "blt"}.get(name, "bltu")
+        out.append(f"    addi  {rc}, {rc}, {c}\n    {br}  {rc}, {rl}, {name}\n{name}_hi:\n")
+    out.append("""    li    s6, 0
+    li    t0, 0
+    li    t1, 64
+hsum:
+    slli  t2, t0, 2
+    add   t2, t2, s1
+    lwu   t3, 0(t2)
+    slli  s6, s6, 1
+    xor   s6, s6, t3
+    addi  t0, t0, 1
+    bne   t0, t1, hsum
+    xor   s6, s6, a5
+    la    a1, out
+    sd    s6, 0(a1)
+    li    a0, 1
+    li    a2, 8
+    li    a7, 64
+    ecall
+    li    a0, 0
+    li    a7, 93
+    ecall
+V5b_ret:
+    ret
+""")
+    out.append(_region_leaf("f0"))
+    out.append(_region_leaf("f1", ret="jalr  ra, 0(ra)"))
+    out.append(_region_leaf("f2", extra="    andi  t2, x26, 1\n    beqz  t2, f2_skip\n    jal   t4, f2b\nf2_skip:\n"))
+    out.append("f2b:\n    addi  t0, t0, 1\n    jr    t4\nf2b_end:\n")
+    out.append(_region_leaf("f3", extra="    andi  x13, x13, 127\n"))
+    out.append(_region_leaf("f4", extra="    addi  ra, ra, 0\n"))
+    out.append(_region_leaf("fs"))
+    out.append("""    .bss
+    .balign 8
+out:
+    .zero 8
+    .balign 256
+tab0:
+    .zero 256
+acc:
+    .zero 512
+""")
+    return "".join(out)
+
+
+def region_program_asm():
+    """(elf, labels): the ELF and the assembler's label addresses."""
+    from rvasm import Assembler
+    a = Assembler(compress=True)
+    elf = a.assemble(region_program_source())
+    return elf, dict(a.labels)
+
+
+def region_program_elf() -> bytes:
+    return region_program_asm()[0]
+
+
+def region_program_model():
+    """The program in plain Python: (stdout bytes, layout).  layout[name] =
+    (first, end, per-pass starts): the instruction counts (committed before it)
+    of the variant's first set-up instruction, of the first instruction after
+    its loop, and of each pass's first instruction; layout["end"] = the whole
+    run's count.  (An ecall is not counted: the oracle's numInst steps on the
+    instructions that commit without a syscall.)"""
+    tab0 = [(7 * i + 3) & 255 for i in range(256)]
+    idx = [((5 * i + 3) & 63) * 4 for i in range(64)]
+    acc = [0] * 64
+    a5 = 0x1234567
+    n = 4 + 2 + 256 * 7 + 2 + 64 * 10 + 2   # la s0, la s1; fill0; fill1; li a5 (lui + addi)
+    layout = {}
+    for name, rc_r, rl_r, c, leaf in REGION_LOOPS:
+        first = n
+        n += {"V0": 4, "V5": 4}.get(name, 2)
+        rc, rl, starts = 0, _region_limit(name, c), []
+        while True:
+            starts.append(n)
+            a5 ^= rc
+            a5 ^= (a5 << 13) & M64
+            a5 ^= a5 >> 7
+            a0 = sum(tab0[(a5 >> (8 * k)) & 255] for k in range(4))
+            n += 7 + 32 + 8 + {"V7": 1, "V5b": 1, "V6": 2, "V9": 1, "V3": 1, "V4": 1, "V2": 2}.get(name, 0)
+            if name == "V2" and rc & 1:
+                a0 += 1
+                n += 3
+            j = idx[a5 & 63] // 4 if name == "V6" else a5 & 63
+            acc[j] = (acc[j] + a0) & M32
+            rc += c
+            if not ((rc != rl) if name == "V8a" else (rc < rl)):
+                break
+        layout[name] = (first, n, starts)
+    s6 = 0
+    for w in acc:
+        s6 = ((s6 << 1) ^ w) & M64
+    layout["end"] = n + 3 + 64 * 7 + 1 + 2 + 1 + 3 + 2   # li x3; hsum; xor; la; sd; write; exit
+    return ((s6 ^ a5) & M64).to_bytes(8, "little"), layout
+
+
+def region_program_expected() -> bytes:
+    return region_program_model()[0]
+
+
+REGION_TABLE_BYTES = 256   # the word table's range at s1: (a5 & 63) * 4 + [0, 4)
+
+
+def elf_load_pages(elf: bytes):
+    """(pages of the PT_LOAD segments, [lo, hi) of the executable ones)."""
+    import struct
+    phoff, = struct.unpack_from("<Q", elf, 32)
+    phentsize, phnum = struct.unpack_from("<HH", elf, 54)
+    pages, lo, hi = set(), M64, 0
+    for i in range(phnum):
+        typ, flags, _, _, paddr, _, memsz, _ = struct.unpack_from("<IIQQQQQQ", elf, phoff + i * phentsize)
+        if typ != 1 or not memsz:
+            continue
+        pages |= set(range(paddr >> 12, ((paddr + memsz - 1) >> 12) + 1))
+        if flags & 1:
+            lo, hi = min(lo, paddr), max(hi, paddr + memsz)
+    return pages, (lo, hi)
+
+
+def region_straddle_base():
+    """A base for V0's word table whose first 192 bytes end the last mapped
+    data page and whose last 64 lie on the page after it, which no segment
+    maps (nor is it stack or heap: the program never moves brk)."""
+    elf, lab = region_program_asm()
+    pages, (code_lo, code_hi) = elf_load_pages(elf)
+    base = ((lab["acc"] >> 12) + 1 << 12) - 3 * REGION_TABLE_BYTES // 4
+    lo, hi = base, base + REGION_TABLE_BYTES - 1
+    assert lo >> 12 != hi >> 12 and (lo >> 12 in pages) and (hi >> 12 not in pages)
+    assert hi < code_lo or lo >= code_hi       # not in the code range: only the pages refuse it
+    assert base > lab["acc"] + 512 and base % 4 == 0
+    return base
+
+
+def region_explicit_sites():
+    """The hand-placed sites, as (tag, inst, target, mask):
+    - base_text / base_text_far / base_unmapped / base_straddle: s1 flipped
+      just before V0's `sub s3, t0, s1`, so the store table s1 + [0, 256)
+      moves (onto V0's own loop in the text: it rewrites itself and dies;
+      onto V3's loop: V0 rewrites code it never reaches and runs to the cap;
+      to the unmapped page 0x2000; to the last 192 bytes of the data page, so
+      that words 0..47 lie on that mapped page and words 48..63 on the page
+      after .bss, outside every VMA: a check of the first page alone would
+      pass it; the first pass uses word 45 and stores, and the trial
+      page-faults at its first word index >= 48, some passes on)
+      and the loop gets that much longer (for a base above acc the bound
+      acc + 32 - s1 wraps to nearly 2^64);
+    - v0_rl / v3_rl: the same bits of the bound flipped in the middle of V0
+      (a would-be hang) and of V3 (whose leaf masks the bound: it leaves);
+    - v6_off: the loaded offset t1 flipped between V6's `lw t1` and its
+      `add t4, s1, t1`, in eight different passes."""
+    _, lab = region_program_asm()
+    _, lay = region_program_model()
+    acc = lab["acc"]
+    sub_inst = lay["V0"][0] + 3   # li s2; la t0 (auipc, addi); sub
+    out = [("base_text", sub_inst, 9, acc ^ (lab["V0"] & ~3)),
+           ("base_text_far", sub_inst, 9, acc ^ (lab["V3"] & ~3)),
+           ("base_unmapped", sub_inst, 9, acc ^ 0x2000),
+           ("base_straddle", sub_inst, 9, acc ^ region_straddle_base())]
+    for bit in (12, 20, 31, 40, 63):
+        out.append(("v0_rl", lay["V0"][2][REGION_PASSES // 2], 19, 1 << bit))
+        out.append(("v3_rl", lay["V3"][2][REGION_PASSES // 2], 13, 1 << bit))
+    for p in range(8):   # pass 4p + 1: 7 to the call, the leaf's 32, then andi, slli, add, lw
+        out.append(("v6_off", lay["V6"][2][4 * p + 1] + 7 + 32 + 4, 6, 1 << (10 + 7 * p)))
+    return out
+
+
+def region_sites(ninst, n=REGION_SITES_GPU, seed=13):
+    """n random single-bit faults -- a variant, an instruction inside it (its
+    set-up included), one of its rc, rl, the table bases s0 / s1 and ra -- then
+    the explicit sites (region_explicit_sites).  region_site_variant() names
+    the variant of each random site."""
+    import numpy as np
+    from oracle.pyoracle import SITE_DT
+    _, lay = region_program_model()
+    ex = region_explicit_sites()
+    r = np.random.default_rng(seed)
+    s = np.zeros(n + len(ex), SITE_DT)
+    v = r.integers(0, len(REGION_LOOPS), n)
+    u, w = r.random(n), r.integers(0, 5, n)
+    for i in range(n):
+        name, rc, rl, _, _ = REGION_LOOPS[v[i]]
+        lo, hi, _ = lay[name]
+        s["inst"][i] = min(lo + int(u[i] * (hi - lo)), ninst - 1)
+        s["target"][i] = (rc, rl, 8, 9, 1)[w[i]]
+    s["mask"][:n] = np.uint64(1) << r.integers(0, 64, n).astype(np.uint64)
+    for i, (_, inst, target, mask) in enumerate(ex):
+        s["inst"][n + i], s["target"][n + i], s["mask"][n + i] = inst, target, mask
+    s["trial"] = np.arange(len(s))
+    return s
+
+
+def region_explicit_outcomes(res):
+    """(cls, sub) of the explicit sites' outcomes (the tail of a region_sites
+    result), by tag."""
+    by = {}
+    for (tag, _, _, _), r in zip(region_explicit_sites(), res):
+        by.setdefault(tag, []).append((int(r["cls"]), int(r["sub"])))
+    return by
+
+
+def region_site_variant(sites):
+    """The variant's name for each site (by its instruction count)."""
+    _, lay = region_program_model()
+    names = []
+    for inst in sites["inst"]:
+        names.append(next((k for k, v in lay.items() if k != "end" and v[0] <= inst < v[1]), ""))
+    return names
+
+
+def test_region_program_on_oracle(oracle_mod):
+    import numpy as np
+    elf, lab = region_program_asm()
+    o = oracle_mod.Oracle(elf, "region")
+    g = o.run_golden()
+    assert g.exit_code == 0, g
+    out, lay = region_program_model()
+    assert o.golden_stdout() == out
+    # the model's instruction counts are the golden run's (the sites stand on them)
+    assert lay["end"] == g.ninst, (lay["end"], g.ninst)
+    sites = region_sites(g.ninst, REGION_SITES_CPU)
+    res = o.run_trials(sites, protect_mask=0)
+    by = region_explicit_outcomes(res[REGION_SITES_CPU:])
+    # V0's bound flipped high: the loop runs to the cap; V3's leaf masks the
+    # same flips away (bits >= 7: the trial is the golden run again)
+    assert [c for c, _ in by["v0_rl"]] == [3] * 5 and all(c != 3 for c, _ in by["v3_rl"]), by
+    # V6 with a corrupted offset stores outside its table
+    assert sorted(by["v6_off"]) == [(1, 0)] + [(2, 3)] * 7, by
+    # the moved store table: in the text the trial rewrites its own loop and
+    # does not reach the cap; on an unmapped page, or with its second half on
+    # one, it page-faults
+    assert by["base_text"][0][0] != 3 and by["base_unmapped"] == [(2, 3)] and by["base_straddle"] == [(2, 3)], by
+    assert by["base_text_far"] == [(3, 1)], by
+    # the straddling table takes stores on its mapped part first (at least one
+    # whole pass more than the unmapped one) and faults on the page after it
+    tags = [t for t, *_ in region_explicit_sites()]
+    un, st = (res[REGION_SITES_CPU + tags.index(t)] for t in ("base_unmapped", "base_straddle"))
+    hi_page = (region_straddle_base() + REGION_TABLE_BYTES - 1) >> 12
+    assert int(st["detail"]) >> 12 == hi_page and int(st["ninst"]) > int(un["ninst"]) + 47, (un, st)
+    # the random sites reach every class in the valid loops
+    names = region_site_variant(sites[:REGION_SITES_CPU])
+    valid = np.array([n in REGION_VALID for n in names])
+    assert {0, 1, 2, 3} <= set(res["cls"][:REGION_SITES_CPU][valid].tolist())
