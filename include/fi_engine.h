@@ -533,6 +533,33 @@ fi_status fi_map_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi
 fi_status fi_run_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi_outcome *out, fi_histogram *hist);
 fi_status fi_run_tick_trials(fi_engine *e, uint64_t first_trial, uint64_t n, fi_outcome *out, fi_histogram *hist);
 
+/* Where fi_run_tick_sites / fi_run_tick_trials sample and map their sites.
+ * FI_TICK_MAP_HOST (the default): on the host, as described above; only the
+ * trials that run reach the device.  FI_TICK_MAP_DEVICE: a kernel draws and
+ * maps every site from a packed copy of the golden attempts (built at the
+ * first such call after fi_golden_run); golden-equal and escape trials keep
+ * their slot and end at once in the trial kernels, the histogram is built on
+ * the device, and only outcomes and the histogram are copied back.  Same
+ * checks and error texts, same outcomes, same counts / crash_sub / escape_sub /
+ * trials / guest_insts; the histogram's traffic diagnostics (fetch_bytes,
+ * data_bytes, cow_pages, device_insts) may differ by what the parked trials
+ * add. */
+#define FI_TICK_MAP_HOST 0
+#define FI_TICK_MAP_DEVICE 1
+fi_status fi_set_tick_map(fi_engine *e, int where);
+/* The device map alone, for comparison with fi_map_tick_sites: ts = NULL
+ * samples trials [first_trial, first_trial + n) on the device, else ts[0..n)
+ * are mapped (first_trial unused).  ts_out (may be NULL) receives the tick
+ * sites; sites, disp and host_out (may be NULL) are fi_map_tick_sites'. */
+fi_status fi_map_tick_sites_device(fi_engine *e, const fi_tick_site *ts, uint64_t first_trial, uint64_t n,
+                                   fi_tick_site *ts_out, fi_site *sites, uint8_t *disp, fi_outcome *host_out);
+/* The tick counterpart of fi_run_trials_device (below): trials [first_trial,
+ * first_trial + n) sampled, mapped, run and counted on the device whatever
+ * fi_set_tick_map says; d_out, d_hist and stream as there.  Asynchronous:
+ * nothing is copied back (fi_sync waits for it). */
+fi_status fi_run_tick_trials_device(fi_engine *e, uint64_t first_trial, uint64_t n, void *d_out, void *d_hist,
+                                    void *stream);
+
 fi_status fi_sample_sites(fi_engine *e, uint64_t first_trial, uint64_t n, fi_site *out);
 /* out (n entries, trial order) and hist may be NULL. hist is accumulated into (+=). */
 fi_status fi_run_trials(fi_engine *e, uint64_t first_trial, uint64_t n, fi_outcome *out, fi_histogram *hist);

@@ -37,6 +37,11 @@ namespace fi {
 hipError_t launch_sample(const SampleCtx &c, uint64_t n, fi_site *sites, uint64_t *keys, uint32_t *perm,
                          hipStream_t st);
 hipError_t launch_keys(const fi_site *sites, uint64_t n, uint64_t *keys, uint32_t *perm, hipStream_t st);
+hipError_t launch_tick_map(const TickMapCtx &c, uint64_t n, fi_site *sites, uint64_t *keys, uint32_t *perm,
+                           fi_site *tsites, uint8_t *disp, fi_outcome *res, hipStream_t st);
+hipError_t launch_tick_park(const fi_site *sites, const uint8_t *disp, uint64_t n, uint32_t fill, uint64_t *keys,
+                            uint64_t *eff, hipStream_t st);
+hipError_t launch_tick_fix(const uint8_t *disp, const fi_outcome *res, uint64_t n, fi_outcome *out, hipStream_t st);
 hipError_t launch_forward(const fi_site *sites, uint64_t n, const FwdCtx &c, uint64_t *keys, uint64_t *eff,
                           hipStream_t st);
 hipError_t launch_predecode(const uint8_t *text, uint64_t code_off, uint64_t code_end, uint64_t nhalf, PreInst *pre,
@@ -245,6 +250,19 @@ struct fi_engine {
     fi_timing_stats t_stats{};
     std::string t_status = "no golden run";
     uint32_t clk_esc = 0;                // DevCtx::clk_esc while tick trials run
+    // the device map (fi_set_tick_map; fi_tick_map.h): the packed attempt table, built at its first use
+    int tick_map = FI_TICK_MAP_HOST;
+    uint64_t *d_tk_done = nullptr;
+    TickRec *d_tk_rec = nullptr;
+    uint64_t tk_n = 0;
+    // ... and its per-chunk-slot work buffers (ensure_tick_work), [cap] each: the tick sites in fi_site
+    // layout, the dispositions, the disp 1 / 2 outcomes, uploaded explicit sites
+    fi_site *d_tk_sites[2] = {nullptr, nullptr};
+    uint8_t *d_tk_disp[2] = {nullptr, nullptr};
+    fi_outcome *d_tk_res[2] = {nullptr, nullptr};
+    fi_tick_site *d_tk_in[2] = {nullptr, nullptr};
+    bool tk_run = false;                 // run_chunks maps tick sites (a device tick run is being enqueued)
+    const fi_tick_site *tk_in = nullptr; //   its explicit sites (host; NULL: sampled)
 
     // work buffers, sized for `cap` trials per launch
     uint64_t cap = 0;
@@ -421,6 +439,7 @@ static void free_work(fi_engine *e) {
     dfree(e->d_redo_idx); dfree(e->d_redo_cnt); dfree(e->d_redo_sites); dfree(e->d_redo_out);
     for (auto &h : e->h_stage)
         if (h) { (void)hipHostFree(h); h = nullptr; }
+    for (int i = 0; i < 2; i++) { dfree(e->d_tk_sites[i]); dfree(e->d_tk_disp[i]); dfree(e->d_tk_res[i]); dfree(e->d_tk_in[i]); }
     e->cap = 0;
 }
 static void free_snaps(fi_engine *e) { dfree(e->d_snaps); dfree(e->d_tab); dfree(e->d_pool); }
@@ -428,6 +447,10 @@ static void free_mem_index(fi_engine *e) {
     dfree(e->d_mw_addr); dfree(e->d_mw_off); dfree(e->d_mw_ev);
     e->mw_n = 0;
     e->mem_live = false;
+}
+static void free_tick_table(fi_engine *e) {
+    dfree(e->d_tk_done); dfree(e->d_tk_rec);
+    e->tk_n = 0;
 }
 static void free_fw(fi_engine *e) {
     dfree(e->d_fw_off); dfree(e->d_fw_ev); dfree(e->d_loops);
@@ -503,6 +526,7 @@ static void free_image(fi_engine *e) {
     free_snaps(e);
     free_mem_index(e);
     free_fw(e);
+    free_tick_table(e);
     free_tx(e);
     dfree(e->d_shadow);
     e->g_pre.clear(); e->g_trace.clear(); e->shadow.clear();
@@ -1117,6 +1141,7 @@ fi_status fi_golden_run(fi_engine *e, fi_golden_info *out) {
     // back to the process-start image only
     e->t_status = "no golden run";
     e->t_ops.clear(); e->t_att.clear(); e->t_ticks.clear();
+    free_tick_table(e);   // (rebuilt from the new golden run at the next device map)
     e->snaps.resize(1);
     e->tab.resize(e->n_start_frames);
     e->pool.resize((uint64_t)e->n_start_frames * kPage);
@@ -1575,7 +1600,10 @@ static std::pair<hipEvent_t, hipEvent_t> &timer_slot(fi_engine *e, uint32_t kind
 
 // One pass over sites[0..k) (keys/perm set) with P private pages per slot:
 // forwarding, sort by inject time, the epochs.  Outcomes to d_out.
-static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *d_out, uint32_t P, hipStream_t st) {
+// disp (tick-domain chunks, else NULL): trials with disp[i] != 0 are parked --
+// dead at injection, so the trial kernels end them at once as the golden run.
+static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *d_out, uint32_t P, hipStream_t st,
+                          const uint8_t *disp = nullptr) {
     int end_bit = 64 - __builtin_clzll(std::max<uint64_t>(e->golden.ninst, 1));
     // (a dead site ends at injection: an early exit, so not with FI_CFG_NO_EARLY_EXIT)
     const bool fwd = e->fw_ok && !(e->cfg.flags & (FI_CFG_NO_FORWARD | FI_CFG_NO_EARLY_EXIT));
@@ -1591,11 +1619,13 @@ static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *
         fc.snap_interval = e->snap_I; fc.text_lo = e->text_lo; fc.text_hi = e->text_hi;
         HIPCHK(launch_forward(sites, k, fc, e->d_keys, e->d_eff, st));
     }
+    // (without forwarding the parked trials still need eff: the identity for the rest)
+    if (disp) HIPCHK(launch_tick_park(sites, disp, k, fwd ? 0u : 1u, e->d_keys, e->d_eff, st));
     HIPCHK(sort_pairs(e->d_tmp, e->tmp_bytes, e->d_keys, e->d_keys2, e->d_perm, e->d_perm2, k, end_bit, st));
     DevCtx c = base_ctx(e);
     c.sites = sites;
     c.perm = e->d_perm2;
-    c.eff = fwd ? e->d_eff : nullptr;
+    c.eff = (fwd || disp) ? e->d_eff : nullptr;
     c.out = d_out;
     c.n = k;
     c.n_slots = (uint32_t)k;
@@ -1718,11 +1748,15 @@ struct Chunk {
     fi_site *sites = nullptr;
     fi_outcome *out = nullptr;
     fi_outcome *host_out = nullptr;   // run_common: where the outcomes go on the host
+    // a tick-domain chunk (else NULL): the tick sites as fi_site, dispositions, disp 1 / 2 outcomes
+    const fi_site *tsites = nullptr;
+    const uint8_t *disp = nullptr;
+    const fi_outcome *res = nullptr;
     uint32_t slot = 0;                // redo list / count / event pair
 };
 
 static fi_status chunk_begin(fi_engine *e, const Chunk &ch, hipStream_t st) {
-    fi_status s = run_pass(e, ch.sites, ch.k, ch.out, e->cfg.private_pages, st);
+    fi_status s = run_pass(e, ch.sites, ch.k, ch.out, e->cfg.private_pages, st, ch.disp);
     if (s) return s;
     if (!(e->cfg.flags & FI_CFG_NO_REDO)) {
         uint32_t *cnt = e->d_redo_cnt + ch.slot;
@@ -1753,7 +1787,9 @@ static fi_status chunk_end(fi_engine *e, const Chunk &ch, fi_histogram *d_hist, 
             }
         }
     }
-    HIPCHK(launch_hist(ch.sites, ch.out, ch.k, d_hist, nullptr, st));
+    // (a redo trial is never a parked one: those end masked, not as resource escapes)
+    if (ch.disp) HIPCHK(launch_tick_fix(ch.disp, ch.res, ch.k, ch.out, st));
+    HIPCHK(launch_hist(ch.tsites ? ch.tsites : ch.sites, ch.out, ch.k, d_hist, nullptr, st));
     if (ch.host_out) {
         if (!e->h_stage[ch.slot]) HIPCHK(hipHostMalloc(&e->h_stage[ch.slot], e->cap * sizeof(fi_outcome)));
         HIPCHK(hipMemcpyAsync(e->h_stage[ch.slot], ch.out, ch.k * sizeof(fi_outcome), hipMemcpyDeviceToHost, st));
@@ -1777,6 +1813,21 @@ static void hist_add(fi_histogram *dst, const fi_histogram *src) {
     for (size_t i = 0; i < sizeof(fi_histogram) / 8; i++) d[i] += s[i];
 }
 
+// The device map's arguments: the packed table, the campaign's draw, the
+// golden outcome.  in = uploaded explicit sites (NULL: sample from `first`).
+static TickMapCtx tick_map_ctx(fi_engine *e, uint64_t first, const fi_tick_site *in) {
+    TickMapCtx c{};
+    c.done = e->d_tk_done; c.rec = e->d_tk_rec; c.n_att = e->tk_n;
+    c.golden_ninst = e->golden.ninst; c.golden_ticks = e->t_stats.ticks;
+    c.in = in;
+    c.seed = e->seed; c.structures = e->structures; c.first = first;
+    c.burst = e->burst;
+    c.bits = e->bits & (e->burst == 1 ? ~0ULL : ((2ULL << (64 - e->burst)) - 1));
+    c.n_struct = (uint32_t)__builtin_popcountll(e->structures);
+    c.gsub = e->gsub; c.gexit = e->golden.exit_code; c.gdetail = e->gdetail;
+    return c;
+}
+
 // Trials [first, first + n) (sampled on the device) or the given sites, in
 // chunks of at most e->cap; outcomes to out_dev (device, n entries) or
 // out_host (through the alternating device buffers), histogram added to
@@ -1796,7 +1847,17 @@ static fi_status run_chunks(fi_engine *e, uint64_t first, const fi_site *sites, 
         ch.sites = ch.slot ? e->d_sites_alt : e->d_sites;
         ch.out = out_dev ? out_dev + done : ch.slot ? e->d_out_alt : e->d_out;
         ch.host_out = out_host ? out_host + done : nullptr;
-        if (sites) {
+        if (e->tk_run) {   // tick sites: the mapper takes the sampler's place
+            ch.tsites = e->d_tk_sites[ch.slot]; ch.disp = e->d_tk_disp[ch.slot]; ch.res = e->d_tk_res[ch.slot];
+            const fi_tick_site *in = nullptr;
+            if (e->tk_in) {
+                HIPCHK(hipMemcpyAsync(e->d_tk_in[ch.slot], e->tk_in + done, ch.k * sizeof(fi_tick_site),
+                                      hipMemcpyHostToDevice, st));
+                in = e->d_tk_in[ch.slot];
+            }
+            HIPCHK(launch_tick_map(tick_map_ctx(e, first + done, in), ch.k, ch.sites, e->d_keys, e->d_perm,
+                                   e->d_tk_sites[ch.slot], e->d_tk_disp[ch.slot], e->d_tk_res[ch.slot], st));
+        } else if (sites) {
             HIPCHK(hipMemcpyAsync(ch.sites, sites + done, ch.k * sizeof(fi_site), hipMemcpyHostToDevice, st));
             HIPCHK(launch_keys(ch.sites, ch.k, e->d_keys, e->d_perm, st));
         } else {
@@ -1980,8 +2041,150 @@ fi_status fi_map_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi
     return FI_OK;
 }
 
+// ---- the device map (fi_set_tick_map FI_TICK_MAP_DEVICE)
+fi_status fi_set_tick_map(fi_engine *e, int where) {
+    if (!e) return FI_E_ARG;
+    if (where != FI_TICK_MAP_HOST && where != FI_TICK_MAP_DEVICE) return fail(e, FI_E_ARG, "unknown tick map %d", where);
+    e->tick_map = where;
+    return FI_OK;
+}
+
+// The packed attempt table on the device, built from the golden run's
+// attempts at the first device map after it (fi_golden_run drops it).
+static fi_status ensure_tick_table(fi_engine *e) {
+    if (e->d_tk_done) return FI_OK;
+    std::vector<uint64_t> done;
+    std::vector<TickRec> rec;
+    pack_tick_table(e->t_att, e->t_ticks, done, rec);
+    if (done.empty()) return fail(e, FI_E_STATE, "tick model: no attempts");
+    HIPCHK(hipMalloc(&e->d_tk_done, done.size() * sizeof(uint64_t)));
+    HIPCHK(hipMalloc(&e->d_tk_rec, rec.size() * sizeof(TickRec)));
+    HIPCHK(hipMemcpy(e->d_tk_done, done.data(), done.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_tk_rec, rec.data(), rec.size() * sizeof(TickRec), hipMemcpyHostToDevice));
+    e->tk_n = done.size();
+    return FI_OK;
+}
+
+// The device map's work buffers, one set per chunk slot, beside the others
+// (ensure_work, which frees them when it grows): made once a device tick run
+// or map is first asked for.
+static fi_status ensure_tick_work(fi_engine *e) {
+    for (int i = 0; i < 2; i++) {
+        if (!e->d_tk_sites[i]) HIPCHK(hipMalloc(&e->d_tk_sites[i], e->cap * sizeof(fi_site)));
+        if (!e->d_tk_disp[i]) HIPCHK(hipMalloc(&e->d_tk_disp[i], e->cap));
+        if (!e->d_tk_res[i]) HIPCHK(hipMalloc(&e->d_tk_res[i], e->cap * sizeof(fi_outcome)));
+        if (!e->d_tk_in[i]) HIPCHK(hipMalloc(&e->d_tk_in[i], e->cap * sizeof(fi_tick_site)));
+    }
+    return FI_OK;
+}
+
+// The host path's checks, in its order and words: a sampled run's
+// (fi_sample_tick_sites, then fi_run_tick_sites) or an explicit one's
+// (fi_run_tick_sites, then fi_map_tick_sites site by site).
+static fi_status tick_check(fi_engine *e, const fi_tick_site *ts, uint64_t n, bool run) {
+    fi_status st = tick_ready(e);
+    if (st) return st;
+    if (!ts) {
+        if (!e->structures) return fail(e, FI_E_STATE, "fi_set_campaign first");
+        if (e->structures & (1ULL << FI_T_MEM)) return fail(e, FI_E_ARG, "tick sites: memory words are not supported");
+    }
+    if (run && (e->protect || e->protect_opc))
+        return fail(e, FI_E_ARG, "tick sites: selective replication (fi_set_protect*) is not supported");
+    for (uint64_t i = 0; ts && i < n; i++) {
+        const fi_tick_site &t = ts[i];
+        const bool target_ok = (t.target >= 1 && t.target <= FI_T_PC) || t.target == FI_T_RESULT;
+        if (!t.mask || !target_ok || t.tick >= e->t_stats.ticks)
+            return fail(e, FI_E_ARG, "tick site %llu: target %u, tick %llu (golden run %llu ticks)",
+                        (unsigned long long)i, t.target, (unsigned long long)t.tick,
+                        (unsigned long long)e->t_stats.ticks);
+    }
+    return FI_OK;
+}
+
+static fi_status tick_device_prepare(fi_engine *e, uint64_t n) {
+    HIPCHK(hipSetDevice(e->dev));
+    fi_status s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch));
+    if (!s) s = ensure_tick_work(e);
+    if (!s) s = ensure_tick_table(e);
+    return s;
+}
+
+// Enqueue a device tick run: run_chunks with the mapper in the sampler's
+// place.  DevCtx::clk_esc is 1 in every launch of the run (a DevCtx is copied
+// at its launch) and 0 again on every way out.
+static fi_status tick_run_chunks(fi_engine *e, uint64_t first, const fi_tick_site *ts, uint64_t n, fi_outcome *out_dev,
+                                 fi_outcome *out_host, fi_histogram *d_hist, hipStream_t st) {
+    e->tk_run = true;
+    e->tk_in = ts;
+    e->clk_esc = 1;   // this engine's clock is AtomicSimpleCPU's: a curTick read escapes
+    const fi_status s = run_chunks(e, first, nullptr, n, out_dev, out_host, d_hist, st);
+    e->clk_esc = 0;
+    e->tk_in = nullptr;
+    e->tk_run = false;
+    return s;
+}
+
+// fi_run_tick_sites / fi_run_tick_trials with the device map: only outcomes
+// and the histogram come back.
+static fi_status tick_run_device(fi_engine *e, uint64_t first, const fi_tick_site *ts, uint64_t n, fi_outcome *out,
+                                 fi_histogram *hist) {
+    fi_status s = tick_check(e, ts, n, true);
+    if (s || !n) return s;
+    if ((s = tick_device_prepare(e, n))) return s;
+    HIPCHK(hipMemsetAsync(e->d_hist, 0, sizeof(fi_histogram), e->stream));
+    if ((s = tick_run_chunks(e, first, ts, n, nullptr, out, e->d_hist, e->stream))) return s;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    e->last_ms = ms;
+    if (hist) {
+        fi_histogram h;
+        HIPCHK(hipMemcpy(&h, e->d_hist, sizeof h, hipMemcpyDeviceToHost));
+        hist_add(hist, &h);
+    }
+    return FI_OK;
+}
+
+fi_status fi_run_tick_trials_device(fi_engine *e, uint64_t first, uint64_t n, void *d_out, void *d_hist, void *stream) {
+    if (!e || !d_out || !d_hist) return FI_E_ARG;
+    fi_status s = tick_check(e, nullptr, n, true);
+    if (s || !n) return s;
+    if ((s = tick_device_prepare(e, n))) return s;
+    hipStream_t st = stream ? (hipStream_t)stream : e->stream;
+    return tick_run_chunks(e, first, nullptr, n, (fi_outcome *)d_out, nullptr, (fi_histogram *)d_hist, st);
+}
+
+fi_status fi_map_tick_sites_device(fi_engine *e, const fi_tick_site *ts, uint64_t first, uint64_t n,
+                                   fi_tick_site *ts_out, fi_site *sites, uint8_t *disp, fi_outcome *host_out) {
+    if (!e || (n && (!sites || !disp))) return FI_E_ARG;
+    fi_status s = tick_check(e, ts, n, false);
+    if (s || !n) return s;
+    if ((s = tick_device_prepare(e, n))) return s;
+    std::vector<fi_site> tsv(ts_out ? std::min<uint64_t>(n, e->cap) : 0);
+    for (uint64_t done = 0; done < n;) {
+        const uint64_t k = std::min<uint64_t>(n - done, e->cap);
+        if (ts) HIPCHK(hipMemcpyAsync(e->d_tk_in[0], ts + done, k * sizeof(fi_tick_site), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(launch_tick_map(tick_map_ctx(e, first + done, ts ? e->d_tk_in[0] : nullptr), k, e->d_sites, e->d_keys,
+                               e->d_perm, e->d_tk_sites[0], e->d_tk_disp[0], e->d_tk_res[0], e->stream));
+        HIPCHK(hipMemcpyAsync(sites + done, e->d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(disp + done, e->d_tk_disp[0], k, hipMemcpyDeviceToHost, e->stream));
+        if (host_out)
+            HIPCHK(hipMemcpyAsync(host_out + done, e->d_tk_res[0], k * sizeof(fi_outcome), hipMemcpyDeviceToHost, e->stream));
+        if (ts_out)
+            HIPCHK(hipMemcpyAsync(tsv.data(), e->d_tk_sites[0], k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        for (uint64_t i = 0; ts_out && i < k; i++) {
+            fi_tick_site &o = ts_out[done + i];
+            o.tick = tsv[i].inst; o.mask = tsv[i].mask; o.target = tsv[i].target; o.trial = tsv[i].trial;
+        }
+        done += k;
+    }
+    return FI_OK;
+}
+
 fi_status fi_run_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi_outcome *out, fi_histogram *hist) {
     if (!e || (n && !ts)) return FI_E_ARG;
+    if (e->tick_map == FI_TICK_MAP_DEVICE && n) return tick_run_device(e, 0, ts, n, out, hist);
     fi_status st = tick_ready(e);
     if (st) return st;
     if (e->protect || e->protect_opc)
@@ -2023,6 +2226,7 @@ fi_status fi_run_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi
 
 fi_status fi_run_tick_trials(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist) {
     if (!e) return FI_E_ARG;
+    if (e->tick_map == FI_TICK_MAP_DEVICE) return tick_run_device(e, first, nullptr, n, out, hist);
     std::vector<fi_tick_site> ts(n);
     fi_status st = fi_sample_tick_sites(e, first, n, ts.data());
     if (st) return st;

@@ -218,6 +218,30 @@ std::string build_tick_attempts(const TickGoldenIn &in, std::vector<fi_timing_op
     return "";
 }
 
+void pack_tick_table(const std::vector<TickAttempt> &att, const std::vector<fi_timing_ticks> &ticks,
+                     std::vector<uint64_t> &done, std::vector<TickRec> &rec) {
+    const size_t n = std::min(att.size(), ticks.size());
+    done.resize(n);
+    rec.resize(n);
+    uint32_t g = 0;   // the first attempt since the last commit
+    for (size_t i = 0; i < n; i++) {
+        const TickAttempt &a = att[i];
+        if (i == 0 || att[i - 1].commits) g = (uint32_t)i;
+        done[i] = ticks[i].done;
+        TickRec r{};
+        r.pc = a.pc; r.n = a.n;
+        r.fetch_done0 = ticks[i].fetch_done[0]; r.exec = ticks[i].exec;
+        r.imm = (int32_t)a.imm;
+        r.g = g;
+        r.len = a.len; r.nfetch = a.nfetch; r.ctl = a.ctl;
+        r.rd = a.rd; r.rs1 = a.rs1; r.rs2 = a.rs2; r.done_rd = a.done_rd;
+        r.flags = (uint8_t)((a.commits ? kTrCommits : 0) | (a.ecall ? kTrEcall : 0) | (a.pgfault ? kTrPgfault : 0) |
+                            (a.end ? kTrEnd : 0) | (a.macro ? kTrMacro : 0) |
+                            (a.next_pc != a.pc + a.len ? kTrTaken : 0));
+        rec[i] = r;
+    }
+}
+
 TickMapped map_tick_site(const std::vector<TickAttempt> &att, const std::vector<fi_timing_ticks> &ticks,
                          uint64_t golden_ninst, uint64_t t, uint32_t target, uint64_t mask, uint32_t trial) {
     TickMapped r;

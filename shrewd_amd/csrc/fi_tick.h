@@ -26,7 +26,7 @@ struct TickAttempt {
     bool macro = false;             // AMO / LR / SC: a macro-op (formats/amo.isa)
     uint8_t done_rd = 0;            // the x register its completeAcc writes (int loads, AMO, LR, SC); 0 none
 };
-enum : uint8_t { kCtlNone = 0, kCtlBranch = 1, kCtlJal = 2, kCtlJalr = 3, kCtlAuipc = 4 };
+// (kCtl*: fi_types.h)
 
 struct TickGoldenIn {
     const std::vector<uint32_t> *trace;   // per committed instruction and ecall: halfword | bit 31 ecall
@@ -42,6 +42,12 @@ struct TickGoldenIn {
 // list cannot be rebuilt exactly: unsupported ops, inconsistent records).
 std::string build_tick_attempts(const TickGoldenIn &in, std::vector<fi_timing_op> &ops,
                                 std::vector<TickAttempt> &att);
+
+// The attempts and their ticks packed for the device map (fi_tick_map.h):
+// done[i] = ticks[i].done, rec[i] = attempt i with its ticks and the index of
+// the first attempt since the last commit.
+void pack_tick_table(const std::vector<TickAttempt> &att, const std::vector<fi_timing_ticks> &ticks,
+                     std::vector<uint64_t> &done, std::vector<TickRec> &rec);
 
 // The site map: disposition 0 run `site`, 1 golden-equal, 2 escape (reason).
 struct TickMapped {

@@ -270,6 +270,35 @@ struct DevCtx {
                                      // (0 the 64-lane kernel, 1 solo, 2 solo-odd)
 };
 
+// Tick-domain sites mapped on the device (fi_tick_map.h, fi_tick_map_kernel):
+// the golden run's attempts packed for the map.  done[] -- the tick each
+// attempt completes, the binary-search key -- is a dense array of its own;
+// one TickRec per attempt carries the rest of what the map reads.
+enum : uint8_t { kCtlNone = 0, kCtlBranch = 1, kCtlJal = 2, kCtlJalr = 3, kCtlAuipc = 4 };
+struct TickRec {
+    uint64_t pc, n;                  // its pc; numInst before it
+    uint64_t fetch_done0, exec;      // fi_timing_ticks::fetch_done[0] and ::exec
+    int32_t imm;                     // branch / jal offset
+    uint32_t g;                      // first attempt since the last commit (== its own index: none before it)
+    uint8_t len, nfetch, ctl;        // ctl: kCtl*
+    uint8_t rd, rs1, rs2, done_rd;
+    uint8_t flags;                   // kTr*
+};
+static_assert(sizeof(TickRec) == 48, "TickRec layout");
+constexpr uint8_t kTrCommits = 1, kTrEcall = 2, kTrPgfault = 4, kTrEnd = 8, kTrMacro = 16;
+constexpr uint8_t kTrTaken = 32;     // the next attempt's pc is not pc + len
+
+struct TickMapCtx {
+    const uint64_t *done;            // [n_att] ascending
+    const TickRec *rec;              // [n_att]
+    uint64_t n_att, golden_ninst, golden_ticks;
+    const fi_tick_site *in;          // explicit tick sites; NULL = sample trials first, first + 1, ...
+    uint64_t seed, structures, first;
+    uint64_t bits;                   // as SampleCtx::bits
+    uint32_t burst, n_struct;
+    uint32_t gsub, gexit, gdetail, gpad_;   // the golden outcome (a disp-1 trial's record)
+};
+
 struct SampleCtx {
     uint64_t seed, structures, golden_ninst, first;
     uint32_t burst, n_struct;

@@ -1,6 +1,7 @@
 // fi_kernels.hip -- CDNA4 (gfx950) kernels around the interpreter:
 //
 //   fi_sample_kernel    fault-site sampler: SplitMix64 keyed by (seed, trial)
+//   fi_tick_map_kernel  tick-domain sites: the same draw over ticks, mapped to numInst sites
 //   fi_predecode_kernel decodes every halfword of the golden text once
 //   fi_hist_kernel      outcome histogram (structure x first-bit x class)
 //   hipcub radix sort   trials by inject time, so a wave's 64 lanes share the
@@ -11,6 +12,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "fi_types.h"
+#include "fi_tick_map.h"
 #include "fi_device.h"
 #include "rv64_isa.h"
 #include "fi_softfp.h"
@@ -65,6 +67,86 @@ __global__ void fi_keys_kernel(const fi_site *sites, uint64_t n, uint64_t *keys,
     if (i >= n) return;
     keys[i] = sites[i].inst;
     perm[i] = (uint32_t)i;
+}
+
+// ------------------------------------------------------------------ tick-domain sites
+// One trial per thread (DESIGN.md §4g "device map"): the tick site -- drawn
+// with fi_sample_kernel's own draw, golden_ticks in place of numInst, or read
+// from c.in -- is mapped to the numInst site the trial kernels run
+// (fi_tick_map.h).  Every trial keeps its slot: disp[i] != 0 (golden-equal,
+// escape) is parked by fi_tick_park_kernel and, for an escape, given res[i]
+// by fi_tick_fix_kernel.  tsites[i] is the tick site in fi_site layout
+// (inst = tick): the histogram files the trial under it.  res[i] is the
+// outcome of a disp 1 / 2 trial (zero for disp 0).
+__global__ void __launch_bounds__(256) fi_tick_map_kernel(TickMapCtx c, uint64_t n, fi_site *sites, uint64_t *keys,
+                                                          uint32_t *perm, fi_site *tsites, uint8_t *disp,
+                                                          fi_outcome *res) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fi_site t;   // inst = the tick
+    t.addr = 0;
+    if (c.in) {
+        const fi_tick_site x = c.in[i];
+        t.inst = x.tick; t.mask = x.mask; t.target = x.target; t.trial = x.trial;
+    } else {
+        const uint64_t id = c.first + i;
+        uint64_t st = c.seed ^ (id * 0xD6E8FEB86659FD93ULL);
+        const uint64_t r0 = splitmix(st), r1 = splitmix(st), r2 = splitmix(st);
+        t.inst = __umul64hi(r0, c.golden_ticks);
+        const uint64_t k = __umul64hi(r1, (uint64_t)c.n_struct);
+        uint64_t m = c.structures;
+        for (uint64_t j = 0; j < k; j++) m &= m - 1;
+        t.target = (uint32_t)__builtin_ctzll(m);
+        uint64_t b;
+        if (c.bits == (c.burst == 1 ? ~0ULL : ((2ULL << (64 - c.burst)) - 1))) {
+            b = __umul64hi(r2, (uint64_t)(65 - c.burst));   // every position
+        } else {                                             // the k-th eligible position
+            uint64_t mm = c.bits;
+            const uint64_t kk = __umul64hi(r2, (uint64_t)__popcll(mm));
+            for (uint64_t j = 0; j < kk; j++) mm &= mm - 1;
+            b = (uint64_t)__builtin_ctzll(mm);
+        }
+        t.mask = (c.burst == 64 ? ~0ULL : ((1ULL << c.burst) - 1)) << b;
+        t.trial = (uint32_t)id;
+    }
+    const TickMap m = tick_map_site(c.done, c.rec, c.n_att, c.golden_ninst, t.inst, t.target, t.mask, t.trial);
+    fi_outcome o;
+    o.cls = 0; o.sub = 0; o.exit_code = 0; o.flags = 0; o.detail = 0; o.ninst = 0;
+    if (m.disp == 1) {   // the golden run itself
+        o.cls = FI_MASKED; o.sub = (uint8_t)c.gsub; o.exit_code = (uint8_t)c.gexit;
+        o.flags = 1; o.detail = c.gdetail; o.ninst = c.golden_ninst;
+    } else if (m.disp == 2) {
+        const TickRec A = c.rec[m.attempt];
+        o.cls = FI_ESCAPE; o.sub = FI_ESC_TIMING; o.exit_code = (uint8_t)m.reason;
+        o.flags = 1; o.detail = (uint32_t)A.pc; o.ninst = A.n;
+    }
+    sites[i] = m.site;
+    keys[i] = m.site.inst;
+    perm[i] = (uint32_t)i;
+    tsites[i] = t;
+    disp[i] = (uint8_t)m.disp;
+    res[i] = o;
+}
+
+// After fi_forward_kernel (or in its place: fill = 1 writes the identity for
+// the trials that run): a parked trial is dead at injection, so the trial
+// kernels end it at once as the golden run, and it sorts first.
+__global__ void fi_tick_park_kernel(const fi_site *sites, const uint8_t *disp, uint64_t n, uint32_t fill,
+                                    uint64_t *keys, uint64_t *eff) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (disp[i]) {
+        eff[i] = kFwDead;
+        keys[i] = 0;
+    } else if (fill) {
+        eff[i] = sites[i].inst;
+    }
+}
+
+// Before the histogram and the copy to the host: an escape's outcome.
+__global__ void fi_tick_fix_kernel(const uint8_t *disp, const fi_outcome *res, uint64_t n, fi_outcome *out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n && disp[i] == 2) out[i] = res[i];
 }
 
 // First-access forwarding.  A register site (x1..x31) at
@@ -382,6 +464,21 @@ hipError_t launch_forward(const fi_site *sites, uint64_t n, const FwdCtx &c, uin
 }
 hipError_t launch_keys(const fi_site *sites, uint64_t n, uint64_t *keys, uint32_t *perm, hipStream_t st) {
     hipLaunchKernelGGL(fi_keys_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, sites, n, keys, perm);
+    return hipGetLastError();
+}
+hipError_t launch_tick_map(const TickMapCtx &c, uint64_t n, fi_site *sites, uint64_t *keys, uint32_t *perm,
+                           fi_site *tsites, uint8_t *disp, fi_outcome *res, hipStream_t st) {
+    hipLaunchKernelGGL(fi_tick_map_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, c, n, sites, keys, perm, tsites, disp,
+                       res);
+    return hipGetLastError();
+}
+hipError_t launch_tick_park(const fi_site *sites, const uint8_t *disp, uint64_t n, uint32_t fill, uint64_t *keys,
+                            uint64_t *eff, hipStream_t st) {
+    hipLaunchKernelGGL(fi_tick_park_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, sites, disp, n, fill, keys, eff);
+    return hipGetLastError();
+}
+hipError_t launch_tick_fix(const uint8_t *disp, const fi_outcome *res, uint64_t n, fi_outcome *out, hipStream_t st) {
+    hipLaunchKernelGGL(fi_tick_fix_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, disp, res, n, out);
     return hipGetLastError();
 }
 hipError_t launch_predecode(const uint8_t *text, uint64_t code_off, uint64_t code_end, uint64_t nhalf, PreInst *pre,

@@ -29,6 +29,7 @@ TICK_ESCAPE_NAMES = {1: "after_noncounting_tick", 2: "pc_straddle_first_fetch", 
                      4: "pc_aligned_mid_decode", 5: "pc_two_values", 6: "pc_on_fault_attempt",
                      7: "pc_macro_op_access", 8: "reads_curtick"}
 CPU_ATOMIC, CPU_TIMING = 0, 1
+TICK_MAPS = {"host": 0, "device": 1}   # FI_TICK_MAP_*
 HANG_NAMES = {1: "max_insts", 2: "m5_quiesce"}
 END_NAMES = {0: "exit", 1: "m5_exit", 2: "m5_fail"}     # sub-codes of masked / sdc: how the run ended
 T_PC, T_MEM, T_RESULT, N_STRUCT = 32, 33, 34, 35
@@ -321,6 +322,9 @@ def lib():
         L.fi_map_tick_sites.argtypes = [vp, vp, C.c_uint64, vp, vp, vp]
         L.fi_run_tick_sites.argtypes = [vp, vp, C.c_uint64, vp, vp]
         L.fi_run_tick_trials.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
+        L.fi_set_tick_map.argtypes = [vp, C.c_int]
+        L.fi_map_tick_sites_device.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
+        L.fi_run_tick_trials_device.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp]
         L.fi_translate_status.restype = C.c_char_p
         L.fi_translate_status.argtypes = [vp]
         _lib = L
@@ -503,6 +507,39 @@ class Engine:
         self._chk(self.L.fi_run_tick_trials(self.h, first, n, out.ctypes.data if out is not None else None,
                                             hist.ctypes.data), "fi_run_tick_trials")
         return out, hist[0]
+
+    def set_tick_map(self, where: int | str):
+        """fi_set_tick_map: 'host' (the default) or 'device' -- where
+        run_tick_sites / run_tick_trials sample and map their sites."""
+        if isinstance(where, str):
+            if where.lower() not in TICK_MAPS:
+                raise ValueError(f"tick_map {where!r}: 'host' or 'device'")
+            where = TICK_MAPS[where.lower()]
+        self._chk(self.L.fi_set_tick_map(self.h, where), "fi_set_tick_map")
+
+    def map_tick_sites_device(self, ts: np.ndarray | None = None, first: int = 0, n: int | None = None):
+        """The device map alone: ts (TICK_SITE_DT) mapped, or with ts None the
+        trials [first, first + n) sampled and mapped on the device
+        -> (tick sites, numInst sites, disposition, host outcomes), the last
+        three as map_tick_sites gives them."""
+        if ts is not None:
+            ts = np.ascontiguousarray(ts, TICK_SITE_DT)
+            n = len(ts)
+        elif n is None:
+            raise ValueError("map_tick_sites_device: ts or n")
+        ts_out = np.zeros(n, TICK_SITE_DT)
+        sites = np.zeros(n, SITE_DT)
+        disp = np.zeros(n, np.uint8)
+        ho = np.zeros(n, OUTCOME_DT)
+        self._chk(self.L.fi_map_tick_sites_device(self.h, ts.ctypes.data if ts is not None else None, first, n,
+                                                  ts_out.ctypes.data, sites.ctypes.data, disp.ctypes.data,
+                                                  ho.ctypes.data), "fi_map_tick_sites_device")
+        return ts_out, sites, disp, ho
+
+    def run_tick_trials_device(self, first: int, n: int, d_out: int, d_hist: int, stream: int | None = None):
+        """fi_run_tick_trials_device: device pointers, asynchronous (sync() waits)."""
+        self._chk(self.L.fi_run_tick_trials_device(self.h, first, n, d_out, d_hist, stream),
+                  "fi_run_tick_trials_device")
 
     def sample(self, first: int, n: int) -> np.ndarray:
         out = np.zeros(n, SITE_DT)
@@ -722,7 +759,9 @@ class FaultCampaign:
     cpu_type ("atomic": sites at a committed-instruction count, the default;
     "timing": sites at a tick of a TimingSimpleCPU run on the reference run
     script's NoCache + SingleChannelDDR3_1600 board -- simple_binary_run.py's
-    CPUTypes.TIMING -- mapped to the instruction in flight) and timing_params.
+    CPUTypes.TIMING -- mapped to the instruction in flight) and timing_params;
+    tick_map ("host", the default, or "device": where a timing campaign
+    samples and maps its sites, Engine.set_tick_map; outcomes are the same).
     """
 
     def __init__(self, workload: str, cmd: Sequence[str] | None = None, env: Sequence[str] | None = None,
@@ -731,7 +770,15 @@ class FaultCampaign:
                  device: int = 0, private_pages: int = 16, protect_opclasses=(), bits=None,
                  shadow_fu_model: bool = False, priority_to_shadow: bool = False, issue_params: dict | None = None,
                  checkpoint: str = "", executable: str | None = None, input: str = "cin",
-                 cpu_type: str = "atomic", timing_params: TimingParams | None = None):
+                 cpu_type: str = "atomic", timing_params: TimingParams | None = None, tick_map: str = "host"):
+        self.cpu_type = cpu_type.lower().removesuffix("simplecpu")
+        if self.cpu_type not in ("atomic", "timing"):
+            raise ValueError(f"cpu_type {cpu_type!r}: 'atomic' or 'timing'")
+        self.tick_map = tick_map.lower()
+        if self.tick_map not in TICK_MAPS:
+            raise ValueError(f"tick_map {tick_map!r}: 'host' or 'device'")
+        if self.tick_map != "host" and self.cpu_type != "timing":
+            raise ValueError(f"tick_map {tick_map!r} needs cpu_type='timing'")
         self.workload, self.cmd, self.env = workload, list(cmd or [workload]), list(env or [])
         self.trials, self.seed, self.structures, self.burst = trials, seed, structures, burst
         self.protect_mask, self.num_gpus, self.output = protect_mask, num_gpus, output
@@ -760,14 +807,12 @@ class FaultCampaign:
                 raise ValueError("input='': gem5 polls fd -1 and retries read(0) forever")
             with open(input, "rb") as f:
                 self.engine.set_stdin(f.read())
-        self.cpu_type = cpu_type.lower().removesuffix("simplecpu")
-        if self.cpu_type not in ("atomic", "timing"):
-            raise ValueError(f"cpu_type {cpu_type!r}: 'atomic' or 'timing'")
         self.engine.set_cpu_model(self.cpu_type, timing_params)
         # trials start at once; the translated kernels join when their build lands
         self.golden = self.engine.golden_run(wait_translation=False)
         if self.cpu_type == "timing" and self.engine.tick_info()["status"]:
             raise EngineError(f"cpu_type='timing': {self.engine.tick_info()['status']}")
+        self.engine.set_tick_map(self.tick_map)
         self.engine.set_campaign(seed, structures, burst)
         self.bits = bits_mask(bits)
         self.engine.set_bits(self.bits)

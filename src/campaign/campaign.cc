@@ -148,6 +148,9 @@ Campaign::Campaign(const CampaignParams &p) : p_(p) {
     if (p_.cpu_type != "atomic" && p_.cpu_type != "timing")
         throw std::runtime_error("cpu_type: 'atomic' or 'timing', not '" + p_.cpu_type + "'");
     const bool timing = p_.cpu_type == "timing";
+    if (p_.tick_map != "host" && p_.tick_map != "device")
+        throw std::runtime_error("tick_map: 'host' or 'device', not '" + p_.tick_map + "'");
+    if (p_.tick_map != "host" && !timing) throw std::runtime_error("tick_map '" + p_.tick_map + "' needs cpu_type 'timing'");
     std::vector<int32_t> devs = p_.devices;
     if (devs.empty())
         for (uint32_t g = 0; g < p_.num_gpus; g++) devs.push_back((int32_t)(p_.first_device + g));
@@ -177,6 +180,8 @@ Campaign::Campaign(const CampaignParams &p) : p_(p) {
             fi_tick_info ti{};
             check(e, fi_tick_golden(e, &ti), "fi_tick_golden");
             if (ti.status[0]) throw std::runtime_error(std::string("cpu_type timing: ") + ti.status);
+            check(e, fi_set_tick_map(e, p_.tick_map == "device" ? FI_TICK_MAP_DEVICE : FI_TICK_MAP_HOST),
+                  "fi_set_tick_map");
         }
         check(e, fi_set_campaign(e, p_.seed, smask, p_.burst), "fi_set_campaign");
         check(e, fi_set_bits(e, bits_mask(p_.bits)), "fi_set_bits");

@@ -51,6 +51,8 @@ struct CampaignParams {
     std::string output;                   // prefix: <output>.outcomes.bin + <output>.json
     std::string cpu_type = "atomic";      // "atomic": sites at a numInst; "timing": at a tick of a
                                           // TimingSimpleCPU run on the reference board (fi_set_cpu_model)
+    std::string tick_map = "host";        // cpu_type "timing": where the tick sites are sampled and mapped,
+                                          // "host" or "device" (fi_set_tick_map; the outcomes are the same)
 };
 
 // 'int_reg' (x1..x31), 'pc', 'mem', 'xN' or ABI register names -> bitmask

@@ -60,6 +60,9 @@ class FaultCampaign(SimObject):
         "atomic", "time coordinate of the fault sites: 'atomic' (a committed-instruction count, "
         "AtomicSimpleCPU) or 'timing' (a tick of a TimingSimpleCPU run on the NoCache + "
         "SingleChannelDDR3_1600 board of the SE run script)")
+    tick_map = Param.String(
+        "host", "cpu_type 'timing': where the tick sites are sampled and mapped to the instruction "
+        "in flight, 'host' or 'device' (fi_set_tick_map; the outcomes are the same)")
     num_gpus = Param.UInt32(1, "MI355X devices used by this process")
     first_gpu = Param.UInt32(0, "first HIP device ordinal")
     max_insts_factor = Param.Float(

@@ -1,0 +1,98 @@
+// Host check of the device map's shared function: random attempt tables and
+// tick sites through fi_tick.cpp map_tick_site and through pack_tick_table +
+// fi_tick_map.h tick_map_site; every field must agree.  Stand-alone (no
+// device, no engine): build with the host compiler, with sanitizers if
+// wanted, e.g.
+//   g++ -std=c++17 -fsanitize=address,undefined -D__HIP_PLATFORM_AMD__ -I$ROCM_PATH/include -Iinclude \
+//       -Ishrewd_amd/csrc -Ishrewd_amd/csrc/hip tools/tick_map_check.cpp shrewd_amd/csrc/fi_tick.cpp -o tick_map_check
+// (tests/test_tick_device_cpu.py does).  Exit status 0 and "ok" on agreement.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <random>
+
+#include "fi_tick.h"
+#include "fi_tick_map.h"
+
+using namespace fi;
+
+int main(int argc, char **argv) {
+    const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 0) : 1;
+    std::mt19937_64 rng(seed);
+    auto rnd = [&](uint64_t n) { return n ? rng() % n : 0; };
+    uint64_t checked = 0, by_disp[3] = {0, 0, 0};
+    for (int table = 0; table < 40; table++) {
+        const size_t n = 1 + rnd(400);
+        std::vector<TickAttempt> att(n);
+        std::vector<fi_timing_ticks> ticks(n);
+        uint64_t t = 1 + rnd(1000), ninst = 0, pc = 0x10000 + 2 * rnd(64);
+        for (size_t i = 0; i < n; i++) {
+            TickAttempt &a = att[i];
+            a.pc = pc; a.n = ninst;
+            a.len = rnd(3) ? 4 : 2;
+            a.nfetch = ((pc & 3) == 2 && a.len == 4) ? 2 : 1;
+            a.imm = (int64_t)rnd(4096) - 2048;
+            a.ctl = (uint8_t)(rnd(3) ? kCtlNone : rnd(5));
+            a.rd = (uint8_t)rnd(32); a.rs1 = (uint8_t)rnd(32); a.rs2 = (uint8_t)rnd(32);
+            const uint64_t kind = rnd(10);   // 0 ecall, 1 page-fault retry, else a commit
+            const bool last = i + 1 == n;
+            a.ecall = kind == 0; a.pgfault = kind == 1;
+            a.commits = kind > 1;
+            a.end = last;
+            a.macro = a.commits && rnd(8) == 0;
+            const bool data = a.commits && (a.macro || rnd(3) == 0) && !last;
+            if (data && rnd(2)) a.done_rd = a.rd;
+            fi_timing_ticks &k = ticks[i];
+            k.fetch_send[0] = t;
+            t += 1 + rnd(50); k.fetch_done[0] = t;
+            if (a.nfetch == 2) { k.fetch_send[1] = t; t += 1 + rnd(50); k.fetch_done[1] = t; }
+            k.exec = t;
+            if (data) t += 1 + rnd(80);
+            k.done = t;
+            t += rnd(3);   // (the next attempt may start at the same tick)
+            if (a.commits) ninst++;
+            const bool taken = a.commits && rnd(3) == 0;
+            const uint64_t next = a.commits ? (taken ? 0x10000 + 2 * rnd(4096) : pc + a.len) : pc;
+            a.next_pc = last ? 0 : next;
+            pc = next;
+        }
+        const uint64_t golden_ninst = ninst, golden_ticks = ticks[n - 1].exec;
+        std::vector<uint64_t> done;
+        std::vector<TickRec> rec;
+        pack_tick_table(att, ticks, done, rec);
+        if (done.size() != n || rec.size() != n) { printf("pack: size\n"); return 1; }
+        for (int s = 0; s < 4000; s++) {
+            uint64_t tick = rnd(golden_ticks);
+            if (rnd(2)) {   // on and next to an attempt's own ticks
+                const fi_timing_ticks &k = ticks[rnd(n)];
+                const uint64_t ev[4] = {k.fetch_done[0], k.exec, k.done, k.fetch_send[0]};
+                tick = ev[rnd(4)] + rnd(3) - 1;
+                if (tick >= golden_ticks) tick = golden_ticks - 1;
+            }
+            const uint64_t tr = rnd(8);
+            const uint32_t target = tr == 0 ? FI_T_RESULT : tr < 4 ? FI_T_PC : (uint32_t)(1 + rnd(31));
+            const uint64_t mask = rnd(4) ? 1ULL << rnd(64) : (rng() | 1);
+            const uint32_t trial = (uint32_t)rng();
+            const TickMapped a = map_tick_site(att, ticks, golden_ninst, tick, target, mask, trial);
+            const TickMap b = tick_map_site(done.data(), rec.data(), n, golden_ninst, tick, target, mask, trial);
+            const bool same = (uint32_t)a.disp == b.disp && a.attempt == b.attempt &&
+                              (a.disp != 2 || a.reason == b.reason) && !memcmp(&a.site, &b.site, sizeof(fi_site));
+            if (!same) {
+                printf("seed %llu table %d: tick %llu target %u mask %llx: host disp %d reason %u attempt %llu "
+                       "site (%llu, %llx, %u) != shared disp %u reason %u attempt %llu site (%llu, %llx, %u)\n",
+                       (unsigned long long)seed, table, (unsigned long long)tick, target, (unsigned long long)mask,
+                       a.disp, a.reason, (unsigned long long)a.attempt, (unsigned long long)a.site.inst,
+                       (unsigned long long)a.site.mask, a.site.target, b.disp, b.reason,
+                       (unsigned long long)b.attempt, (unsigned long long)b.site.inst,
+                       (unsigned long long)b.site.mask, b.site.target);
+                return 1;
+            }
+            checked++;
+            by_disp[b.disp]++;
+        }
+    }
+    if (!by_disp[0] || !by_disp[1] || !by_disp[2]) { printf("a disposition never occurred\n"); return 1; }
+    printf("ok %llu sites (run %llu, golden %llu, escape %llu)\n", (unsigned long long)checked,
+           (unsigned long long)by_disp[0], (unsigned long long)by_disp[1], (unsigned long long)by_disp[2]);
+    return 0;
+}
