@@ -47,6 +47,9 @@ def parse(argv=None):
                          "NoCache + SingleChannelDDR3_1600 board of simple_binary_run.py)")
     ap.add_argument("--tick-map", default="host", choices=["host", "device"],
                     help="--cpu-type timing: sample and map the tick sites on the host or on the device")
+    ap.add_argument("--tick-contract", default="numinst", choices=["numinst", "literal"],
+                    help="--cpu-type timing: literal runs the sites where the timing CPU is not a numInst flip "
+                         "instead of reporting them as escape/timing")
     ap.add_argument("--num-gpus", type=int, default=1)
     ap.add_argument("--max-insts-factor", type=float, default=2.0)
     ap.add_argument("--private-pages", type=int, default=16)
@@ -69,7 +72,7 @@ def run_gem5(a):
                          protect_opclasses=_split(a.protect_opclasses), shadow_fu_model=a.shadow_fu_model,
                          priority_to_shadow=a.priority_to_shadow, issue_width=a.issue_width,
                          load_latency=a.load_latency, num_gpus=a.num_gpus, max_insts_factor=a.max_insts_factor,
-                         cpu_type=a.cpu_type, tick_map=a.tick_map,
+                         cpu_type=a.cpu_type, tick_map=a.tick_map, tick_contract=a.tick_contract,
                          private_pages=a.private_pages, output=a.output)
     root = Root(full_system=False, campaign=camp)
     m5.instantiate()
@@ -100,7 +103,7 @@ def run_ctypes(a):
                       shadow_fu_model=a.shadow_fu_model, priority_to_shadow=a.priority_to_shadow, checkpoint=a.checkpoint,
                       issue_params={"issue_width": a.issue_width, "load_latency": a.load_latency},
                       input=a.input, executable=a.executable or None, cpu_type=a.cpu_type,
-                      tick_map=a.tick_map)
+                      tick_map=a.tick_map, tick_contract=a.tick_contract)
     t0 = time.perf_counter()
     c.run(first_trial=a.first_trial)
     dt = time.perf_counter() - t0

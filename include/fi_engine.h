@@ -96,7 +96,9 @@ typedef int32_t fi_status;
                                numInst injection; exit_code = FI_TK_* (the reason), detail = the pc in flight */
 /* FI_ESC_TIMING reasons.  A flip at tick t lands inside the instruction in
  * flight; most such flips equal a numInst injection (fi_run_tick_trials
- * maps them), these do not: */
+ * maps them), these do not.  Under FI_TICK_CONTRACT_LITERAL (fi_set_tick_contract)
+ * reasons 1-6 run on the device as TimingSimpleCPU runs them and only
+ * FI_TK_MACRO and FI_TK_CLOCK remain escapes: */
 #define FI_TK_NONCOUNT 1    /* after an ecall / a page-fault retry (no numInst step) that reads or writes the
                                flipped register (ecall: a0..a7; retry: rs1, rs2), or any pc flip there */
 #define FI_TK_STRADDLE1 2   /* pc flip while the first half of a 32-bit instruction at pc % 4 == 2 is fetched,
@@ -128,10 +130,30 @@ typedef struct {
 typedef struct {
     uint64_t inst;    /* numInst at whose tick the flip is applied */
     uint64_t mask;    /* xor mask (burst of adjacent bits) */
-    uint64_t addr;    /* memory sites: 8-byte aligned guest virtual address */
+    uint64_t addr;    /* memory sites: 8-byte aligned guest virtual address; register and pc sites: 0, or the
+                         tick descriptor FI_SITE_TK_* of a literal tick site (below); result sites: 0 */
     uint32_t target;  /* FI_T_* */
     uint32_t trial;   /* trial id */
 } fi_site;
+
+/* The tick descriptor of a register / pc site (fi_site.addr; 0 = a plain
+ * numInst flip).  fi_map_tick_sites writes it under FI_TICK_CONTRACT_LITERAL
+ * and fi_run_sites runs it:
+ *   bits 8-14 (FI_SITE_TK_SKIP)  k: the flip is applied after k more fetch-execute attempts that do not
+ *                                count (ecalls, page-fault retries) once numInst has reached `inst`
+ *   FI_SITE_TK_FETCH   pc sites: the attempt's fetch request went out before the flip -- the next 4-byte
+ *                      fetch reads the word of the old pc ((pc ^ mask) & ~3, + 4 with FI_SITE_TK_FETCH2),
+ *                      Decoder::moreBytes slices it by the new pc's alignment, a second fetch it may still
+ *                      need reads (pc & ~3) + 4, and the instruction executes at the new pc
+ *   FI_SITE_TK_FETCH2  the flip lands before the second fetch of a 32-bit instruction at pc % 4 == 2: the
+ *                      decoder holds its first half; flipped to a 4-aligned pc it keeps that state, and
+ *                      the next instruction decoded at pc % 4 == 2 is composed from the low half of the
+ *                      instruction decoded before it and the halfword at pc - 2
+ * Sites with a descriptor are not forwarded to the register's first access. */
+#define FI_SITE_TK_FETCH 1ull
+#define FI_SITE_TK_FETCH2 2ull
+#define FI_SITE_TK_SKIP_SHIFT 8
+#define FI_SITE_TK_SKIP_MAX 127ull
 
 typedef struct {
     int32_t device;                 /* HIP device ordinal */
@@ -547,6 +569,17 @@ fi_status fi_run_tick_trials(fi_engine *e, uint64_t first_trial, uint64_t n, fi_
 #define FI_TICK_MAP_HOST 0
 #define FI_TICK_MAP_DEVICE 1
 fi_status fi_set_tick_map(fi_engine *e, int where);
+/* What a tick site maps to (fi_map_tick_sites, fi_map_tick_sites_device,
+ * fi_run_tick_sites, fi_run_tick_trials, fi_run_tick_trials_device; callable
+ * where fi_set_tick_map is).  FI_TICK_CONTRACT_NUMINST (the default): plain
+ * numInst sites, the rest FI_ESC_TIMING.  FI_TICK_CONTRACT_LITERAL: the sites
+ * of reasons FI_TK_NONCOUNT .. FI_TK_FAULTOP carry a tick descriptor
+ * (FI_SITE_TK_*) and run; FI_TK_MACRO, FI_TK_CLOCK and a site more than
+ * FI_SITE_TK_SKIP_MAX non-counting attempts after its numInst (FI_TK_NONCOUNT)
+ * stay escapes.  Any other value: FI_E_ARG. */
+#define FI_TICK_CONTRACT_NUMINST 0
+#define FI_TICK_CONTRACT_LITERAL 1
+fi_status fi_set_tick_contract(fi_engine *e, int contract);
 /* The device map alone, for comparison with fi_map_tick_sites: ts = NULL
  * samples trials [first_trial, first_trial + n) on the device, else ts[0..n)
  * are mapped (first_trial unused).  ts_out (may be NULL) receives the tick

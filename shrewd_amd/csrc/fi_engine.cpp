@@ -252,6 +252,7 @@ struct fi_engine {
     uint32_t clk_esc = 0;                // DevCtx::clk_esc while tick trials run
     // the device map (fi_set_tick_map; fi_tick_map.h): the packed attempt table, built at its first use
     int tick_map = FI_TICK_MAP_HOST;
+    int tick_contract = FI_TICK_CONTRACT_NUMINST;   // fi_set_tick_contract
     uint64_t *d_tk_done = nullptr;
     TickRec *d_tk_rec = nullptr;
     uint64_t tk_n = 0;
@@ -1825,6 +1826,7 @@ static TickMapCtx tick_map_ctx(fi_engine *e, uint64_t first, const fi_tick_site 
     c.bits = e->bits & (e->burst == 1 ? ~0ULL : ((2ULL << (64 - e->burst)) - 1));
     c.n_struct = (uint32_t)__builtin_popcountll(e->structures);
     c.gsub = e->gsub; c.gexit = e->golden.exit_code; c.gdetail = e->gdetail;
+    c.literal = e->tick_contract == FI_TICK_CONTRACT_LITERAL ? 1u : 0u;
     return c;
 }
 
@@ -2022,7 +2024,8 @@ fi_status fi_map_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi
             return fail(e, FI_E_ARG, "tick site %llu: target %u, tick %llu (golden run %llu ticks)",
                         (unsigned long long)i, t.target, (unsigned long long)t.tick,
                         (unsigned long long)e->t_stats.ticks);
-        const TickMapped m = map_tick_site(e->t_att, e->t_ticks, e->golden.ninst, t.tick, t.target, t.mask, t.trial);
+        const TickMapped m = map_tick_site(e->t_att, e->t_ticks, e->golden.ninst, t.tick, t.target, t.mask, t.trial,
+                                           e->tick_contract == FI_TICK_CONTRACT_LITERAL);
         disp[i] = (uint8_t)m.disp;
         sites[i] = m.site;
         if (host_out) {
@@ -2046,6 +2049,14 @@ fi_status fi_set_tick_map(fi_engine *e, int where) {
     if (!e) return FI_E_ARG;
     if (where != FI_TICK_MAP_HOST && where != FI_TICK_MAP_DEVICE) return fail(e, FI_E_ARG, "unknown tick map %d", where);
     e->tick_map = where;
+    return FI_OK;
+}
+
+fi_status fi_set_tick_contract(fi_engine *e, int contract) {
+    if (!e) return FI_E_ARG;
+    if (contract != FI_TICK_CONTRACT_NUMINST && contract != FI_TICK_CONTRACT_LITERAL)
+        return fail(e, FI_E_ARG, "unknown tick contract %d", contract);
+    e->tick_contract = contract;
     return FI_OK;
 }
 

@@ -56,7 +56,10 @@ struct TickMapped {
     fi_site site{};
     uint64_t attempt = 0;
 };
+// literal (fi_set_tick_contract FI_TICK_CONTRACT_LITERAL): the FI_TK_NONCOUNT ..
+// FI_TK_FAULTOP cases become sites with a tick descriptor (fi_site.addr).
 TickMapped map_tick_site(const std::vector<TickAttempt> &att, const std::vector<fi_timing_ticks> &ticks,
-                         uint64_t golden_ninst, uint64_t t, uint32_t target, uint64_t mask, uint32_t trial);
+                         uint64_t golden_ninst, uint64_t t, uint32_t target, uint64_t mask, uint32_t trial,
+                         bool literal = false);
 
 }  // namespace fi

@@ -37,14 +37,17 @@ FI_TM_HD inline TickMap tick_map_done(TickMap r, uint32_t disp, uint32_t reason)
     return r;
 }
 FI_TM_HD inline TickMap tick_map_to(TickMap r, uint64_t golden_ninst, uint32_t tg, uint64_t m, uint64_t inst,
-                                    uint32_t trial) {
-    r.site.inst = inst; r.site.mask = m; r.site.target = tg; r.site.trial = trial;
+                                    uint32_t trial, uint64_t desc = 0) {
+    r.site.inst = inst; r.site.mask = m; r.site.addr = desc; r.site.target = tg; r.site.trial = trial;
     r.disp = inst > golden_ninst ? 1u : 0u;   // after the run's last commit: the golden run
     return r;
 }
 
+// literal: fi_set_tick_contract FI_TICK_CONTRACT_LITERAL (the FI_TK_NONCOUNT ..
+// FI_TK_FAULTOP cases become sites with a tick descriptor, fi_site.addr)
 FI_TM_HD inline TickMap tick_map_site(const uint64_t *done, const TickRec *rec, uint64_t n_att, uint64_t golden_ninst,
-                                      uint64_t t, uint32_t target, uint64_t mask, uint32_t trial) {
+                                      uint64_t t, uint32_t target, uint64_t mask, uint32_t trial,
+                                      uint32_t literal = 0) {
     TickMap r;
     r.disp = 0; r.reason = 0;
     r.site.inst = 0; r.site.mask = 0; r.site.addr = 0; r.site.target = 0; r.site.trial = 0;
@@ -56,6 +59,10 @@ FI_TM_HD inline TickMap tick_map_site(const uint64_t *done, const TickRec *rec, 
                    : t <= A.exec                          ? (A.nfetch == 2 ? FETCH2 : FETCH1)
                                                           : DATA;
     const uint64_t g = A.g <= j ? A.g : j;   // the attempts since the last commit (ecalls, page-fault retries)
+    const bool lit = literal && j - g <= FI_SITE_TK_SKIP_MAX;
+    const uint64_t skip = (j - g) << FI_SITE_TK_SKIP_SHIFT;
+    // the literal contract's pc site: the old word at the new pc, after the j - g attempts before it
+    const uint64_t refetch = skip | FI_SITE_TK_FETCH | (ph == FETCH2 ? FI_SITE_TK_FETCH2 : 0);
     // a result fault: the first commit at or after t
     if (target == FI_T_RESULT) return tick_map_to(r, golden_ninst, FI_T_RESULT, mask, A.n, trial);
     if (target >= 1 && target <= 31) {
@@ -65,40 +72,43 @@ FI_TM_HD inline TickMap tick_map_site(const uint64_t *done, const TickRec *rec, 
         }
         for (uint64_t q = g; q < j; q++) {   // the flip lands after these: it must commute with them
             const TickRec Q = rec[q];
-            if ((Q.flags & kTrEcall) && target >= 10 && target <= 17) return tick_map_done(r, 2, FI_TK_NONCOUNT);
-            if ((Q.flags & kTrPgfault) && (target == Q.rs1 || target == Q.rs2))
+            if (((Q.flags & kTrEcall) && target >= 10 && target <= 17) ||
+                ((Q.flags & kTrPgfault) && (target == Q.rs1 || target == Q.rs2))) {
+                if (lit) return tick_map_to(r, golden_ninst, target, mask, A.n, trial, skip);
                 return tick_map_done(r, 2, FI_TK_NONCOUNT);
+            }
         }
         return tick_map_to(r, golden_ninst, target, mask, A.n, trial);
     }
     // the pc
-    if (g != j) return tick_map_done(r, 2, FI_TK_NONCOUNT);
+    if (g != j && !lit) return tick_map_done(r, 2, FI_TK_NONCOUNT);
     const uint64_t pc = A.pc, np = pc ^ mask;
     const bool same_word = ((pc ^ np) & ~3ULL) == 0;
     const bool commits = (A.flags & kTrCommits) != 0, end = (A.flags & kTrEnd) != 0;
     uint64_t m = 0, inst = A.n + 1;
     uint32_t tg = FI_T_PC;
+    uint32_t why = 0;   // the numInst contract's escape; the literal contract's refetch site
     if (ph == DATA) {
-        if (A.flags & kTrMacro) return tick_map_done(r, 2, FI_TK_MACRO);
+        if ((A.flags & kTrMacro) && g == j) return tick_map_done(r, 2, FI_TK_MACRO);
         m = (pc + A.len) ^ (np + 4);
-    } else if (!commits || end) {
-        if (!(ph == FETCH1 && same_word)) return tick_map_done(r, 2, FI_TK_FAULTOP);
-        m = mask; inst = A.n;
     } else if (ph == FETCH1 && same_word) {
-        m = mask; inst = A.n;
+        return tick_map_to(r, golden_ninst, FI_T_PC, mask, A.n, trial, skip);
+    } else if (!commits || end) {
+        why = FI_TK_FAULTOP;
     } else {
         if (ph == FETCH1) {
-            if (A.nfetch == 2) return tick_map_done(r, 2, FI_TK_STRADDLE1);
-            if ((pc & 3) != (np & 3)) return tick_map_done(r, 2, FI_TK_ALIGN);
+            if (A.nfetch == 2) why = FI_TK_STRADDLE1;
+            else if ((pc & 3) != (np & 3)) why = FI_TK_ALIGN;
         } else if ((np & 3) == 0) {
-            return tick_map_done(r, 2, FI_TK_STRADDLE2);
+            why = FI_TK_STRADDLE2;
         }
+        if (!why && g != j) why = FI_TK_NONCOUNT;   // (literal only: run as it lands)
         // the golden instruction executed at np: its effect, moved by np - pc
         const uint64_t imm = (uint64_t)(int64_t)A.imm;
-        switch (A.ctl) {
-        case kCtlAuipc: return tick_map_done(r, 2, FI_TK_TWO);
+        if (!why) switch (A.ctl) {
+        case kCtlAuipc: why = FI_TK_TWO; break;
         case kCtlJal:
-            if (A.rd) return tick_map_done(r, 2, FI_TK_TWO);
+            if (A.rd) why = FI_TK_TWO;
             m = (pc + imm) ^ (np + imm);
             break;
         case kCtlJalr:
@@ -113,6 +123,10 @@ FI_TM_HD inline TickMap tick_map_site(const uint64_t *done, const TickRec *rec, 
         }
         default: m = (pc + A.len) ^ (np + A.len); break;
         }
+    }
+    if (why) {
+        if (lit) return tick_map_to(r, golden_ninst, FI_T_PC, mask, A.n, trial, refetch);
+        return tick_map_done(r, 2, why);
     }
     return tick_map_to(r, golden_ninst, tg, m, inst, trial);
 }

@@ -68,7 +68,8 @@ struct LaneSave {
     int32_t watch;
     uint32_t nfail, n_priv, snap_j;
     uint32_t flags;                  // bit 0 out_bad, bits 1-2 injected, bit 3 code_dirty, bit 4 FP state,
-                                     // bit 5 VM state (VmState of the slot is live)
+                                     // bit 5 VM state (VmState of the slot is live), bits 6-31 LaneMem::tk
+                                     // (a literal tick site's decoder state, fi_trial.hip kTk*)
     uint32_t dlo, dhi;               // rewritten code bytes [code_lo + dlo, code_lo + dhi) (if code_dirty)
     uint32_t pad;                    // fflags | frm << 5
     uint64_t resv, lock;             // LR/SC: load reservation and lock record (~0 = none)
@@ -296,7 +297,8 @@ struct TickMapCtx {
     uint64_t seed, structures, first;
     uint64_t bits;                   // as SampleCtx::bits
     uint32_t burst, n_struct;
-    uint32_t gsub, gexit, gdetail, gpad_;   // the golden outcome (a disp-1 trial's record)
+    uint32_t gsub, gexit, gdetail;   // the golden outcome (a disp-1 trial's record)
+    uint32_t literal;                // fi_set_tick_contract: 1 = FI_TICK_CONTRACT_LITERAL
 };
 
 struct SampleCtx {

@@ -109,7 +109,8 @@ __global__ void __launch_bounds__(256) fi_tick_map_kernel(TickMapCtx c, uint64_t
         t.mask = (c.burst == 64 ? ~0ULL : ((1ULL << c.burst) - 1)) << b;
         t.trial = (uint32_t)id;
     }
-    const TickMap m = tick_map_site(c.done, c.rec, c.n_att, c.golden_ninst, t.inst, t.target, t.mask, t.trial);
+    const TickMap m = tick_map_site(c.done, c.rec, c.n_att, c.golden_ninst, t.inst, t.target, t.mask, t.trial,
+                                    c.literal);
     fi_outcome o;
     o.cls = 0; o.sub = 0; o.exit_code = 0; o.flags = 0; o.detail = 0; o.ninst = 0;
     if (m.disp == 1) {   // the golden run itself
@@ -174,7 +175,8 @@ __global__ void fi_forward_kernel(const fi_site *sites, uint64_t n, FwdCtx c, ui
     if (i >= n) return;
     const fi_site s = sites[i];
     uint64_t f = s.inst;
-    if (s.target >= 1 && s.target <= 31 && s.inst < (1ULL << 29)) {
+    // (a literal tick site, s.addr != 0, is applied where it lands: not forwarded)
+    if (s.target >= 1 && s.target <= 31 && s.inst < (1ULL << 29) && !s.addr) {
         const uint32_t key = (uint32_t)(4 * s.inst);   // (2t) << 1: before both events of numInst t
         uint32_t lo = c.reg_off[s.target], hi = c.reg_off[s.target + 1];
         while (lo < hi) {

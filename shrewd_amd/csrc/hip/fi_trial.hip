@@ -145,6 +145,10 @@ struct LaneMem {
     uint64_t req_vpn;              // pending copy-on-write, kNone = none
     const uint8_t *req_src;
     bool code_dirty;
+    // a literal tick site (fi_site.addr, FI_SITE_TK_*): kTk* below.  A lane with
+    // tk != 0 stays on the general path and takes no golden-snapshot exit.
+    // (tk and tkn sit in the padding the layout had: LaneMem keeps its size)
+    uint32_t tk;
     uint64_t dlo, dhi;             // bounding range of the code bytes the lane rewrote (valid if code_dirty)
     // LR/SC: the ISA's load reservation (isa.cc:1006-1064) and this context's
     // lock record in memory (abstract_mem.cc:258-345), as virtual addresses
@@ -154,8 +158,19 @@ struct LaneMem {
     bool vm;                       // VmState of the slot is live (the trial made a VM syscall)
     uint32_t vcfg;                 // vector configuration (vtype, vl) as oracle/rv64se.c vcfg_of; 0 = process start
     uint32_t nmiss;                // diagnostics: full page-table lookups (TLB misses)
+    uint32_t tkn;                  // tk after the instruction fetch_lane_tk fetched, taken at its commit (a tick
+                                   // retried for a copy-on-write fetches again)
     uint32_t *dl;                  // solo kernel: LDS copy of the slot's rewritten-code map (else NULL)
 };
+// LaneMem::tk (LaneSave::flags holds it from bit 6 on: 26 bits)
+constexpr uint32_t kTkFetch = 1;        // the pc is flipped, the next fetch still reads the old pc's word
+constexpr uint32_t kTkMid = 2;          // the decoder holds a stale first half (Decoder::moreBytes' mid)
+constexpr uint32_t kTkWait = 4;         // numInst reached the site: waiting for its non-counting attempts
+constexpr uint32_t kTkCntShift = 3;     // bits 3-9: such attempts completed while waiting
+constexpr uint32_t kTkCntMask = 0x7Fu << kTkCntShift;
+constexpr uint32_t kTkHalfShift = 10;   // bits 10-25: low half of the instruction decoded last (with kTkMid)
+constexpr uint32_t kTkHalfMask = 0xFFFFu << kTkHalfShift;
+static_assert(FI_SITE_TK_SKIP_MAX == 0x7F, "the attempt count's field");
 // solo_fast_run reads the TLB as tv0..tv3 then tp0..tp3, 8-byte aligned
 static_assert(__builtin_offsetof(LaneMem, tv0) % 8 == 0 &&
               __builtin_offsetof(LaneMem, tp0) == __builtin_offsetof(LaneMem, tv0) + 32, "LaneMem TLB layout");
@@ -651,6 +666,104 @@ __device__ int fetch_lane(KCtx *c, const WaveMem &w, LaneMem &m, uint64_t slot, 
     const uint32_t word2 = *(const uint32_t *)(page_of(p1) + (w1 & 4095));
     raw = half | ((word2 & 0xFFFF) << 16);
     return F_NONE;
+}
+
+// fetch_lane for a lane with LaneMem::tk != 0 (a literal tick site, DESIGN.md
+// §4g): TimingSimpleCPU's fetch after a pc flip at the top of a tick, and the
+// decoder state such a flip can leave behind (oracle/rv64se.c tick,
+// tk_inject_top; src/cpu/simple/timing.cc:677-898, decoder.cc:63-116).
+//   kTkFetch: pc is already the flipped pc (old = pc ^ the site's mask).  The request in
+//   flight reads the old pc's word -- its second word if the flip landed
+//   before the second fetch of a straddling instruction (FI_SITE_TK_FETCH2: the
+//   decoder then holds the old first half, and both ticks count here).
+//   moreBytes slices the word by the new pc's alignment: a 4-aligned pc takes
+//   it whole and leaves `mid` as it is (kTkMid from then on); an unaligned one
+//   joins the held half, or takes the upper half and, for a 32-bit
+//   instruction, fetches (pc & ~3) + 4 next.
+//   kTkMid: an instruction at pc % 4 != 0 is the low half of the instruction
+//   decoded last joined with the low half of the word at pc & ~3 (one tick),
+//   which clears `mid`; every other decode renews the held low half.
+// The state after this instruction goes to m.tkn; its commit takes it.  A
+// lane leaves the inner loop after each instruction the fast paths could take
+// next, and the outer loop sends it back here: slow, and rare.
+__device__ int fetch_lane_tk1(KCtx *c, const WaveMem &w, LaneMem &m, uint64_t slot, uint64_t pc, uint32_t &raw,
+                              uint32_t &ticks, uint64_t &fva);
+__device__ __noinline__ int fetch_lane_tk(KCtx *c, const WaveMem &w, LaneMem &m, uint64_t slot, uint64_t pc,
+                                          uint32_t &raw, uint32_t &ticks, uint64_t &fva) {
+    const int fr = fetch_lane_tk1(c, w, m, slot, pc, raw, ticks, fva);
+    if (fr) m.tk &= kTkWait | kTkCntMask;   // a fetch fault resets the decoder; the fetch starts over
+    return fr;
+}
+__device__ int fetch_lane_tk1(KCtx *c, const WaveMem &w, LaneMem &m, uint64_t slot, uint64_t pc, uint32_t &raw,
+                              uint32_t &ticks, uint64_t &fva) {
+    const uint32_t tk = m.tk;
+    uint32_t next = tk & (kTkWait | kTkCntMask);
+    if (tk & kTkFetch) {
+        const fi_site &s = c->sites[c->perm[slot]];   // (the lane's site: its state holds no copy of it)
+        const bool second = (s.addr & FI_SITE_TK_FETCH2) != 0;
+        const uint64_t o0 = (pc ^ s.mask) & ~3ULL, w0 = o0 + (second ? 4 : 0);
+        ticks = second ? 2 : 1;
+        const uint64_t p0 = lookup(c, w, m, slot, w0 >> 12);
+        if (!p0) { fva = w0; return F_PGFAULT; }
+        const uint32_t word = *(const uint32_t *)(page_of(p0) + (w0 & 4095));
+        if ((pc & 3) == 0) {
+            raw = ((word & 3) != 3) ? (word & 0xFFFF) : word;
+            if (second) next |= kTkMid | ((raw & 0xFFFF) << kTkHalfShift);
+        } else if (second) {
+            const uint64_t ph = lookup(c, w, m, slot, o0 >> 12);
+            if (!ph) { fva = o0; return F_PGFAULT; }
+            const uint32_t held = *(const uint32_t *)(page_of(ph) + (o0 & 4095)) >> 16;
+            raw = held | ((word & 0xFFFF) << 16);
+        } else {
+            const uint32_t half = word >> 16;
+            raw = half;
+            if ((half & 3) == 3) {
+                ticks = 2;
+                const uint64_t w1 = (pc & ~3ULL) + 4;
+                const uint64_t p1 = lookup(c, w, m, slot, w1 >> 12);
+                if (!p1) { fva = w1; return F_PGFAULT; }
+                raw = half | ((*(const uint32_t *)(page_of(p1) + (w1 & 4095)) & 0xFFFF) << 16);
+            }
+        }
+    } else if ((tk & kTkMid) && (pc & 3) != 0) {
+        const uint64_t w0 = pc & ~3ULL;
+        ticks = 1;
+        const uint64_t p0 = lookup(c, w, m, slot, w0 >> 12);
+        if (!p0) { fva = w0; return F_PGFAULT; }
+        raw = ((tk & kTkHalfMask) >> kTkHalfShift) | ((*(const uint32_t *)(page_of(p0) + (w0 & 4095)) & 0xFFFF) << 16);
+    } else {
+        const int fr = fetch_lane(c, w, m, slot, pc, raw, ticks, fva);
+        if (fr) return fr;
+        if (tk & kTkMid) next |= kTkMid | ((raw & 0xFFFF) << kTkHalfShift);
+    }
+    m.tkn = next;
+    return F_NONE;
+}
+// (the general path's fetch: one call site, as the numInst path had)
+__device__ __noinline__ int fetch_lane_g(KCtx *c, const WaveMem &w, LaneMem &m, uint64_t slot, uint64_t pc, uint32_t &raw,
+                                         uint32_t &ticks, uint64_t &fva) {
+    if (m.tk) return fetch_lane_tk(c, w, m, slot, pc, raw, ticks, fva);
+    return fetch_lane(c, w, m, slot, pc, raw, ticks, fva);
+}
+// Section B for a literal tick site: true while the flip still waits for the
+// FI_SITE_TK_SKIP non-counting attempts (ecalls, page-fault retries: tk_commit
+// counts them, not loop iterations) that share its numInst.
+__device__ __noinline__ bool tk_defer(LaneMem &m, uint32_t desc) {
+    const uint32_t k = (desc >> FI_SITE_TK_SKIP_SHIFT) & (uint32_t)FI_SITE_TK_SKIP_MAX;
+    if (((m.tk & kTkCntMask) >> kTkCntShift) < k) { m.tk |= kTkWait; return true; }
+    m.tk &= ~(kTkWait | kTkCntMask);
+    return false;
+}
+// The attempt fetch_lane_tk fetched is over (committed, or ended in a fault):
+// its decoder state; any fault resets the decoder (advancePC,
+// src/cpu/simple/base.cc:493-512) and is an attempt that does not count.
+__device__ __noinline__ void tk_commit(LaneMem &m, bool fault) {
+    uint32_t t = m.tkn;
+    if (fault) {
+        t &= kTkWait | kTkCntMask;
+        if (t & kTkWait) t += 1u << kTkCntShift;
+    }
+    m.tk = t;
 }
 
 // ------------------------------------------------------------------ syscalls
@@ -3809,6 +3922,7 @@ __device__ __forceinline__ void trial_body() {
     m.vm = false;
     m.vcfg = 0;
     m.nmiss = 0;
+    m.tk = m.tkn = 0;
     if (CX->ov_blocks && live && !resume) CX->ov_of[slot] = 0xFFFFFFFFu;   // no overflow block yet
     // the solo kernel's LDS copy of the slot's rewritten-code map
     __shared__ uint32_t DMAP[kNL == 1 ? kDmapWords : 1];
@@ -3831,6 +3945,7 @@ __device__ __forceinline__ void trial_body() {
         m.dlo = CX->code_lo + SV->dlo; m.dhi = CX->code_lo + SV->dhi;
         m.resv = SV->resv; m.lock = SV->lock;
         m.vm = (SV->flags >> 5) & 1;
+        m.tk = SV->flags >> 6;
         if (m.dl && m.code_dirty)
             for (uint32_t i = 0; i < CX->dmap_words; i++) m.dl[i] = CX->dmap[slot * CX->dmap_words + i];
     }
@@ -3891,7 +4006,7 @@ __device__ __forceinline__ void trial_body() {
     // (a constant false in the 64-lane kernel)
 #define LP_ON (kNL == 1 && LP.on != 0)
 // (eligibility for a loop probe: injected, no watched register, live)
-#define LP_ELIGIBLE (!L.done && (L.injected == 1 || L.injected == 2) && L.watch <= 0)
+#define LP_ELIGIBLE (!L.done && (L.injected == 1 || L.injected == 2) && L.watch <= 0 && !m.tk)
 #define DC_INVAL(lo_, sz_)                                                                          \
     do {                                                                                            \
         if constexpr (kNL == 1) {                                                                   \
@@ -3937,7 +4052,7 @@ __device__ __forceinline__ void trial_body() {
                 sv->dlo = m.code_dirty ? (uint32_t)(m.dlo > CX->code_lo ? m.dlo - CX->code_lo : 0) : 0;
                 sv->dhi = m.code_dirty ? (uint32_t)((m.dhi < CX->code_hi ? m.dhi : CX->code_hi) - CX->code_lo) : 0;
                 sv->flags = (L.out_bad ? 1u : 0u) | ((uint32_t)L.injected << 1) | (m.code_dirty ? 8u : 0u) |
-                            (L.fp ? 16u : 0u) | (m.vm ? 32u : 0u);
+                            (L.fp ? 16u : 0u) | (m.vm ? 32u : 0u) | (m.tk << 6);
                 sv->resv = m.resv; sv->lock = m.lock;
                 sv->pad = (uint32_t)L.fflags | ((uint32_t)L.frm << 5) | (m.vcfg << 8);
                 if (m.dl && m.code_dirty)   // the solo kernel's map lives in LDS
@@ -3980,14 +4095,19 @@ __device__ __forceinline__ void trial_body() {
         // ---- B. tick-top events: fault injection and the max-insts (hang)
         // exit both fire in serviceInstCountEvents at the first tick with
         // numInst >= n (src/cpu/simple/base.cc:321-325, src/cpu/base.cc:764-770)
+        // (a literal tick site, s.addr != 0 on a register / pc site: the flip
+        // waits for the non-counting attempts before it, tk_defer; a pc flip
+        // may leave the next fetch with the old pc's word, kTkFetch)
         if (!L.done && !L.injected && L.ninst >= s.inst) {
-            if (s.target >= 1 && s.target <= 31) {
+            if (s.addr && s.target <= FI_T_PC && tk_defer(m, (uint32_t)s.addr)) {
+            } else if (s.target >= 1 && s.target <= 31) {
                 RREG(s.target) ^= s.mask;
                 if ((CX->protect_mask >> s.target) & 1) L.watch = (int)s.target;
                 L.injected = 1;
             } else if (s.target == FI_T_PC) {
                 L.pc ^= s.mask;
                 L.injected = 1;
+                if (s.addr & FI_SITE_TK_FETCH) m.tk |= kTkFetch;
                 if ((CX->protect_mask >> 32) & 1) finish(L, FI_DETECTED, 0, 0, (uint32_t)L.pc);
             } else if (s.target == FI_T_RESULT) {
                 L.injected = 3;   // armed: the next instruction that commits (general path) is the target
@@ -4041,7 +4161,7 @@ __device__ __forceinline__ void trial_body() {
                 bool eq = grp && L.pc == S->pc && L.out_pos == S->out_pos && L.err_pos == S->err_pos &&
                           (!L.out_bad || (CX->early_exit & 2)) &&
                           m.stack_min == S->stack_min && !L.fp && L.injected != 3 && m.resv == kNone &&
-                          m.lock == kNone && !m.vm && !m.vcfg &&
+                          m.lock == kNone && !m.tk && !m.vm && !m.vcfg &&
                           // the golden suffix reads curTick: the same future needs the same tick count
                           // too (a path with other non-counting ticks -- ecalls, straddled fetches --
                           // reconverges with the same numInst but would print another time)
@@ -4142,7 +4262,7 @@ __device__ __forceinline__ void trial_body() {
         // commit.  Same counters as the fast path, per lane.
         if constexpr (kNL > 1) {
             if (CX->simt_min && !CX->record && CX->pre_ok && wait_min != kNone) {
-                const uint64_t lim = (ready && L.watch <= 0 && L.injected != 3 && m.lock == kNone && next_ev > L.ninst)
+                const uint64_t lim = (ready && L.watch <= 0 && L.injected != 3 && m.lock == kNone && !m.tk && next_ev > L.ninst)
                                          ? next_ev - L.ninst : 0;
                 bool run = lim != 0;
                 const uint32_t n0 = (uint32_t)__popcll(wballot<kNL>(run));
@@ -4274,7 +4394,7 @@ __device__ __forceinline__ void trial_body() {
             if constexpr (kNL == 1) {
                 // ---- solo: one trial, every value uniform -- no groups, no
                 // parking, plain register writes; the same exits and counters
-                if (tx_entry && mine && n_iter >= tx_skip_until && L.injected != 3 && m.lock == kNone && !LP_ON) {
+                if (tx_entry && mine && n_iter >= tx_skip_until && L.injected != 3 && m.lock == kNone && !m.tk && !LP_ON) {
                     const uint64_t rem64 = next_ev - L.ninst;
                     const uint32_t rem = rem64 > (1u << 30) ? (1u << 30) : (uint32_t)rem64;
                     const uint32_t wbud = CX->wave_budget ? CX->wave_budget - n_iter : (1u << 30);
@@ -4371,7 +4491,7 @@ __device__ __forceinline__ void trial_body() {
                     if (st) continue;
                 }
             } else if (tx_entry &&
-                       wballot<kNL>(mine && (dirty_near(m, lpc) || L.injected == 3 || m.lock != kNone)) == 0) {
+                       wballot<kNL>(mine && (dirty_near(m, lpc) || L.injected == 3 || m.lock != kNone || m.tk)) == 0) {
                 // lanes that rewrote code: every block checks its bytes against their range
                 const bool wdirty = uni32(wballot<kNL>(m.code_dirty) != 0);
                 const uint64_t ldlo = m.code_dirty ? m.dlo : kNone, ldhi = m.code_dirty ? m.dhi : 0;
@@ -4467,7 +4587,7 @@ __device__ __forceinline__ void trial_body() {
         // (an armed result fault commits in the general path, and a lane holding
         // an LR/SC lock record stays there: only its stores erase the record)
         if (!LP_ON && CX->pre_ok && lpc >= CX->text_lo && lpc < CX->text_hi &&
-            wballot<kNL>(mine && (L.injected == 3 || m.lock != kNone)) == 0) {
+            wballot<kNL>(mine && (L.injected == 3 || m.lock != kNone || m.tk)) == 0) {
             // lanes that rewrote code run here too, until they reach a rewritten
             // instruction; lanes watching a protected flipped register, until an
             // instruction reads it (the general path classifies the detection)
@@ -4714,7 +4834,9 @@ __device__ __forceinline__ void trial_body() {
         uint32_t ticks = 1;
         bool fast = false;
         const uint64_t key = (lpc & 3) ? ((lpc & ~3ULL) | 2) : lpc;
-        if (CX->pre_ok && key >= CX->text_lo && key < CX->text_hi && wballot<kNL>(mine && dirty_at(CX, m, lpc)) == 0) {
+        // (a literal tick site's lane fetches for itself: fetch_lane_tk)
+        const bool tkm = wballot<kNL>(mine && m.tk) != 0;
+        if (!tkm && CX->pre_ok && key >= CX->text_lo && key < CX->text_hi && wballot<kNL>(mine && dirty_at(CX, m, lpc)) == 0) {
             const Pre4 q = pre_load(CX->pre + ((key - CX->text_lo) >> 1));
             const uint32_t pflags = (q.w >> 8) & 0xFF;
             if (pflags & kPreValid) {
@@ -4726,7 +4848,7 @@ __device__ __forceinline__ void trial_body() {
             }
         }
         if constexpr (kNL == 1) {   // solo: rewritten code decoded before (DCT/DCE)
-            if (!fast && L.pc >= CX->code_lo && L.pc < CX->code_hi) {
+            if (!fast && !tkm && L.pc >= CX->code_lo && L.pc < CX->code_hi) {
                 const uint32_t ci = (uint32_t)(L.pc >> 1) & (kDC - 1);
                 if (DCT[ci] == (uint32_t)(L.pc - CX->text_lo)) {
                     const Pre4 q = DCE[ci];
@@ -4746,7 +4868,7 @@ __device__ __forceinline__ void trial_body() {
             uint64_t fva = 0;
             if (mine) {
                 int fr;
-                OOL(fr = fetch_lane(CX, wc_, mc_, slot, L.pc, raw, t, fva));
+                OOL(fr = fetch_lane_g(CX, wc_, mc_, slot, L.pc, raw, t, fva));
                 if (fr) {
                     // the faulting tick(s) count, nothing commits; decoder reset;
                     // GenericPageTableFault::invoke -> fixupFault (sim/faults.cc:95-105)
@@ -4764,12 +4886,12 @@ __device__ __forceinline__ void trial_body() {
             const int ld = __ffsll((unsigned long long)okm) - 1;
             const uint32_t lraw = (uint32_t)rdl32<kNL>((uint32_t)raw, ld);
             const uint32_t lt = (uint32_t)rdl32<kNL>((uint32_t)t, ld);
-            mine = mine && raw == lraw;
+            mine = mine && raw == lraw && t == lt;   // (t follows from pc and raw, but for a held half: fetch_lane_tk)
             PSTAMP(5);
             d = rv_decode(lraw);
             ticks = lt;
             if constexpr (kNL == 1) {
-                if (L.pc >= CX->code_lo && L.pc < CX->code_hi) {
+                if (!tkm && L.pc >= CX->code_lo && L.pc < CX->code_hi) {
                     Dec dd = d;
                     const uint32_t u = uop_of(dd);   // uop_of may normalise dd.imm (the fast path's form)
                     const uint32_t ci = (uint32_t)(L.pc >> 1) & (kDC - 1);
@@ -5202,6 +5324,7 @@ __device__ __forceinline__ void trial_body() {
         // ---- F. commit: countInst only on NoFault (atomic.cc:687-689), then
         // advancePC (src/cpu/simple/base.cc:493-512)
         if (f != F_NEEDPAGE) {
+        if (m.tk) tk_commit(m, f != F_NONE);
         L.ncyc += ticks;
         L.fetch_b += d.len;
         if (CX->record && (f == F_NONE || f == F_SYSCALL)) {
@@ -5472,7 +5595,7 @@ __global__ void __launch_bounds__(64) fi_debug_loop_kernel(DevCtx, const fi_debu
     tlb_flush(m);
     m.tp0 = m.tp1 = m.tp2 = m.tp3 = 0;
     m.tnext = 0; m.n_priv = 0; m.req_vpn = kNone; m.req_src = nullptr; m.code_dirty = false;
-    m.dlo = m.dhi = 0; m.resv = m.lock = kNone; m.vm = false; m.vcfg = 0; m.nmiss = 0; m.dl = nullptr;
+    m.dlo = m.dhi = 0; m.resv = m.lock = kNone; m.vm = false; m.vcfg = 0; m.nmiss = 0; m.dl = nullptr; m.tk = m.tkn = 0;
     uint64_t k = 0, fva = 0;
     const int r = loop_outcome(kx, w, m, 0, d->regs, d, d->left, k, fva);
     // the body's proof (TXHANG in solo_tx_clean_run; TXHANGU for a region

@@ -30,6 +30,7 @@ TICK_ESCAPE_NAMES = {1: "after_noncounting_tick", 2: "pc_straddle_first_fetch", 
                      7: "pc_macro_op_access", 8: "reads_curtick"}
 CPU_ATOMIC, CPU_TIMING = 0, 1
 TICK_MAPS = {"host": 0, "device": 1}   # FI_TICK_MAP_*
+TICK_CONTRACTS = {"numinst": 0, "literal": 1}   # FI_TICK_CONTRACT_*
 HANG_NAMES = {1: "max_insts", 2: "m5_quiesce"}
 END_NAMES = {0: "exit", 1: "m5_exit", 2: "m5_fail"}     # sub-codes of masked / sdc: how the run ended
 T_PC, T_MEM, T_RESULT, N_STRUCT = 32, 33, 34, 35
@@ -323,6 +324,7 @@ def lib():
         L.fi_run_tick_sites.argtypes = [vp, vp, C.c_uint64, vp, vp]
         L.fi_run_tick_trials.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
         L.fi_set_tick_map.argtypes = [vp, C.c_int]
+        L.fi_set_tick_contract.argtypes = [vp, C.c_int]
         L.fi_map_tick_sites_device.argtypes = [vp, vp, C.c_uint64, C.c_uint64, vp, vp, vp, vp]
         L.fi_run_tick_trials_device.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp]
         L.fi_translate_status.restype = C.c_char_p
@@ -516,6 +518,17 @@ class Engine:
                 raise ValueError(f"tick_map {where!r}: 'host' or 'device'")
             where = TICK_MAPS[where.lower()]
         self._chk(self.L.fi_set_tick_map(self.h, where), "fi_set_tick_map")
+
+    def set_tick_contract(self, contract: int | str):
+        """fi_set_tick_contract: 'numinst' (the default: a tick site is a plain
+        numInst site or an FI_ESC_TIMING escape) or 'literal' (the sites of
+        reasons FI_TK_NONCOUNT .. FI_TK_FAULTOP run on the device as
+        TimingSimpleCPU runs them; FI_TK_MACRO and FI_TK_CLOCK stay escapes)."""
+        if isinstance(contract, str):
+            if contract.lower() not in TICK_CONTRACTS:
+                raise ValueError(f"tick_contract {contract!r}: 'numinst' or 'literal'")
+            contract = TICK_CONTRACTS[contract.lower()]
+        self._chk(self.L.fi_set_tick_contract(self.h, contract), "fi_set_tick_contract")
 
     def map_tick_sites_device(self, ts: np.ndarray | None = None, first: int = 0, n: int | None = None):
         """The device map alone: ts (TICK_SITE_DT) mapped, or with ts None the
@@ -761,7 +774,11 @@ class FaultCampaign:
     script's NoCache + SingleChannelDDR3_1600 board -- simple_binary_run.py's
     CPUTypes.TIMING -- mapped to the instruction in flight) and timing_params;
     tick_map ("host", the default, or "device": where a timing campaign
-    samples and maps its sites, Engine.set_tick_map; outcomes are the same).
+    samples and maps its sites, Engine.set_tick_map; outcomes are the same);
+    tick_contract ("numinst", the default, or "literal": a timing campaign
+    runs the sites where TimingSimpleCPU differs from a numInst flip on the
+    device instead of reporting them as escape/timing,
+    Engine.set_tick_contract).
     """
 
     def __init__(self, workload: str, cmd: Sequence[str] | None = None, env: Sequence[str] | None = None,
@@ -770,7 +787,8 @@ class FaultCampaign:
                  device: int = 0, private_pages: int = 16, protect_opclasses=(), bits=None,
                  shadow_fu_model: bool = False, priority_to_shadow: bool = False, issue_params: dict | None = None,
                  checkpoint: str = "", executable: str | None = None, input: str = "cin",
-                 cpu_type: str = "atomic", timing_params: TimingParams | None = None, tick_map: str = "host"):
+                 cpu_type: str = "atomic", timing_params: TimingParams | None = None, tick_map: str = "host",
+                 tick_contract: str = "numinst"):
         self.cpu_type = cpu_type.lower().removesuffix("simplecpu")
         if self.cpu_type not in ("atomic", "timing"):
             raise ValueError(f"cpu_type {cpu_type!r}: 'atomic' or 'timing'")
@@ -779,6 +797,11 @@ class FaultCampaign:
             raise ValueError(f"tick_map {tick_map!r}: 'host' or 'device'")
         if self.tick_map != "host" and self.cpu_type != "timing":
             raise ValueError(f"tick_map {tick_map!r} needs cpu_type='timing'")
+        self.tick_contract = tick_contract.lower()
+        if self.tick_contract not in TICK_CONTRACTS:
+            raise ValueError(f"tick_contract {tick_contract!r}: 'numinst' or 'literal'")
+        if self.tick_contract != "numinst" and self.cpu_type != "timing":
+            raise ValueError(f"tick_contract {tick_contract!r} needs cpu_type='timing'")
         self.workload, self.cmd, self.env = workload, list(cmd or [workload]), list(env or [])
         self.trials, self.seed, self.structures, self.burst = trials, seed, structures, burst
         self.protect_mask, self.num_gpus, self.output = protect_mask, num_gpus, output
@@ -813,6 +836,7 @@ class FaultCampaign:
         if self.cpu_type == "timing" and self.engine.tick_info()["status"]:
             raise EngineError(f"cpu_type='timing': {self.engine.tick_info()['status']}")
         self.engine.set_tick_map(self.tick_map)
+        self.engine.set_tick_contract(self.tick_contract)
         self.engine.set_campaign(seed, structures, burst)
         self.bits = bits_mask(bits)
         self.engine.set_bits(self.bits)

@@ -151,6 +151,10 @@ Campaign::Campaign(const CampaignParams &p) : p_(p) {
     if (p_.tick_map != "host" && p_.tick_map != "device")
         throw std::runtime_error("tick_map: 'host' or 'device', not '" + p_.tick_map + "'");
     if (p_.tick_map != "host" && !timing) throw std::runtime_error("tick_map '" + p_.tick_map + "' needs cpu_type 'timing'");
+    if (p_.tick_contract != "numinst" && p_.tick_contract != "literal")
+        throw std::runtime_error("tick_contract: 'numinst' or 'literal', not '" + p_.tick_contract + "'");
+    if (p_.tick_contract != "numinst" && !timing)
+        throw std::runtime_error("tick_contract '" + p_.tick_contract + "' needs cpu_type 'timing'");
     std::vector<int32_t> devs = p_.devices;
     if (devs.empty())
         for (uint32_t g = 0; g < p_.num_gpus; g++) devs.push_back((int32_t)(p_.first_device + g));
@@ -182,6 +186,9 @@ Campaign::Campaign(const CampaignParams &p) : p_(p) {
             if (ti.status[0]) throw std::runtime_error(std::string("cpu_type timing: ") + ti.status);
             check(e, fi_set_tick_map(e, p_.tick_map == "device" ? FI_TICK_MAP_DEVICE : FI_TICK_MAP_HOST),
                   "fi_set_tick_map");
+            check(e, fi_set_tick_contract(e, p_.tick_contract == "literal" ? FI_TICK_CONTRACT_LITERAL
+                                                                           : FI_TICK_CONTRACT_NUMINST),
+                  "fi_set_tick_contract");
         }
         check(e, fi_set_campaign(e, p_.seed, smask, p_.burst), "fi_set_campaign");
         check(e, fi_set_bits(e, bits_mask(p_.bits)), "fi_set_bits");

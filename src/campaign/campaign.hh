@@ -53,6 +53,9 @@ struct CampaignParams {
                                           // TimingSimpleCPU run on the reference board (fi_set_cpu_model)
     std::string tick_map = "host";        // cpu_type "timing": where the tick sites are sampled and mapped,
                                           // "host" or "device" (fi_set_tick_map; the outcomes are the same)
+    std::string tick_contract = "numinst";   // cpu_type "timing": "numinst", or "literal" -- the sites where the
+                                          // timing CPU is not a numInst flip run on the device instead of
+                                          // ending as escape/timing (fi_set_tick_contract)
 };
 
 // 'int_reg' (x1..x31), 'pc', 'mem', 'xN' or ABI register names -> bitmask

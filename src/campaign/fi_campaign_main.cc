@@ -6,7 +6,7 @@
 //               [--burst K] [--bits 0-31,63] [--protect-mask M] [--protect-opclasses IntAlu,IntMult] [--num-gpus G] [--device D]
 //               [--max-insts-factor F] [--private-pages P] [--output PREFIX]
 //               [--executable PATH] [--input FILE|cin] [--devices 0,0,1]
-//               [--cpu-type atomic|timing] [--tick-map host|device]
+//               [--cpu-type atomic|timing] [--tick-map host|device] [--tick-contract numinst|literal]
 //
 // Prints one JSON summary line; with --output also writes PREFIX.outcomes.bin
 // (fi_outcome records in trial order), PREFIX.hist.bin and PREFIX.json.
@@ -62,6 +62,13 @@ int main(int argc, char **argv) {
         else if (k == "--tick-map") {
             if (v != "host" && v != "device") { fprintf(stderr, "--tick-map: host or device, not %s\n", v.c_str()); return 2; }
             p.tick_map = v;
+        }
+        else if (k == "--tick-contract") {
+            if (v != "numinst" && v != "literal") {
+                fprintf(stderr, "--tick-contract: numinst or literal, not %s\n", v.c_str());
+                return 2;
+            }
+            p.tick_contract = v;
         }
         else if (k == "--load-latency") p.load_latency = (uint32_t)strtoul(v.c_str(), nullptr, 0);
         else if (k == "--num-gpus") p.num_gpus = (uint32_t)strtoul(v.c_str(), nullptr, 0);

@@ -63,6 +63,10 @@ class FaultCampaign(SimObject):
     tick_map = Param.String(
         "host", "cpu_type 'timing': where the tick sites are sampled and mapped to the instruction "
         "in flight, 'host' or 'device' (fi_set_tick_map; the outcomes are the same)")
+    tick_contract = Param.String(
+        "numinst", "cpu_type 'timing': 'numinst' (a tick site is a numInst site or an escape/timing record) "
+        "or 'literal' (the sites where TimingSimpleCPU is not a numInst flip run on the device, "
+        "fi_set_tick_contract)")
     num_gpus = Param.UInt32(1, "MI355X devices used by this process")
     first_gpu = Param.UInt32(0, "first HIP device ordinal")
     max_insts_factor = Param.Float(

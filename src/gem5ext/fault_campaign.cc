@@ -35,6 +35,7 @@ FaultCampaign::init()
     cp.issue_width = params().issue_width;
     cp.cpu_type = params().cpu_type;
     cp.tick_map = params().tick_map;
+    cp.tick_contract = params().tick_contract;
     cp.load_latency = params().load_latency;
     cp.num_gpus = params().num_gpus;
     cp.first_device = params().first_gpu;

@@ -6,6 +6,10 @@
 //   g++ -std=c++17 -fsanitize=address,undefined -D__HIP_PLATFORM_AMD__ -I$ROCM_PATH/include -Iinclude \
 //       -Ishrewd_amd/csrc -Ishrewd_amd/csrc/hip tools/tick_map_check.cpp shrewd_amd/csrc/fi_tick.cpp -o tick_map_check
 // (tests/test_tick_device_cpu.py does).  Exit status 0 and "ok" on agreement.
+//   tick_map_check SEED           the numInst contract
+//   tick_map_check SEED literal   the literal contract (fi_set_tick_contract): the two maps agree on the
+//                                 tick descriptors too, the only escapes left are FI_TK_MACRO and sites past
+//                                 FI_SITE_TK_SKIP_MAX attempts, and each kind of descriptor occurred
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -18,6 +22,9 @@ using namespace fi;
 
 int main(int argc, char **argv) {
     const uint64_t seed = argc > 1 ? strtoull(argv[1], nullptr, 0) : 1;
+    const bool literal = argc > 2 && !strcmp(argv[2], "literal");
+    if (argc > 2 && !literal) { printf("usage: tick_map_check [SEED [literal]]\n"); return 2; }
+    uint64_t by_desc[3] = {0, 0, 0};   // literal: sites with a skip count, a fetch override, a second-fetch one
     std::mt19937_64 rng(seed);
     auto rnd = [&](uint64_t n) { return n ? rng() % n : 0; };
     uint64_t checked = 0, by_disp[3] = {0, 0, 0};
@@ -73,8 +80,9 @@ int main(int argc, char **argv) {
             const uint32_t target = tr == 0 ? FI_T_RESULT : tr < 4 ? FI_T_PC : (uint32_t)(1 + rnd(31));
             const uint64_t mask = rnd(4) ? 1ULL << rnd(64) : (rng() | 1);
             const uint32_t trial = (uint32_t)rng();
-            const TickMapped a = map_tick_site(att, ticks, golden_ninst, tick, target, mask, trial);
-            const TickMap b = tick_map_site(done.data(), rec.data(), n, golden_ninst, tick, target, mask, trial);
+            const TickMapped a = map_tick_site(att, ticks, golden_ninst, tick, target, mask, trial, literal);
+            const TickMap b = tick_map_site(done.data(), rec.data(), n, golden_ninst, tick, target, mask, trial,
+                                            literal ? 1u : 0u);
             const bool same = (uint32_t)a.disp == b.disp && a.attempt == b.attempt &&
                               (a.disp != 2 || a.reason == b.reason) && !memcmp(&a.site, &b.site, sizeof(fi_site));
             if (!same) {
@@ -87,11 +95,28 @@ int main(int argc, char **argv) {
                        (unsigned long long)b.site.mask, b.site.target);
                 return 1;
             }
+            if (literal) {
+                if (b.disp == 2 && b.reason != FI_TK_MACRO &&
+                    !(b.reason == FI_TK_NONCOUNT && b.attempt - rec[b.attempt].g > FI_SITE_TK_SKIP_MAX)) {
+                    printf("seed %llu table %d: tick %llu target %u: reason %u is still an escape\n",
+                           (unsigned long long)seed, table, (unsigned long long)tick, target, b.reason);
+                    return 1;
+                }
+                if (b.disp == 0) {
+                    by_desc[0] += (b.site.addr >> FI_SITE_TK_SKIP_SHIFT) != 0;
+                    by_desc[1] += (b.site.addr & FI_SITE_TK_FETCH) != 0;
+                    by_desc[2] += (b.site.addr & FI_SITE_TK_FETCH2) != 0;
+                }
+            } else if (b.site.addr) {
+                printf("seed %llu table %d: a tick descriptor under the numInst contract\n", (unsigned long long)seed, table);
+                return 1;
+            }
             checked++;
             by_disp[b.disp]++;
         }
     }
     if (!by_disp[0] || !by_disp[1] || !by_disp[2]) { printf("a disposition never occurred\n"); return 1; }
+    if (literal && (!by_desc[0] || !by_desc[1] || !by_desc[2])) { printf("a tick descriptor never occurred\n"); return 1; }
     printf("ok %llu sites (run %llu, golden %llu, escape %llu)\n", (unsigned long long)checked,
            (unsigned long long)by_disp[0], (unsigned long long)by_disp[1], (unsigned long long)by_disp[2]);
     return 0;
