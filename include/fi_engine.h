@@ -558,10 +558,11 @@ fi_status fi_run_tick_trials(fi_engine *e, uint64_t first_trial, uint64_t n, fi_
 /* Where fi_run_tick_sites / fi_run_tick_trials sample and map their sites.
  * FI_TICK_MAP_HOST (the default): on the host, as described above; only the
  * trials that run reach the device.  FI_TICK_MAP_DEVICE: a kernel draws and
- * maps every site from a packed copy of the golden attempts (built at the
- * first such call after fi_golden_run); golden-equal and escape trials keep
- * their slot and end at once in the trial kernels, the histogram is built on
- * the device, and only outcomes and the histogram are copied back.  Same
+ * maps every site -- the same draw and the same map function over the same
+ * packed golden attempts, uploaded at the first such call after fi_golden_run;
+ * golden-equal and escape trials keep their slot and end at once in the trial
+ * kernels, the histogram is built on the device, and only outcomes and the
+ * histogram are copied back.  Same
  * checks and error texts, same outcomes, same counts / crash_sub / escape_sub /
  * trials / guest_insts; the histogram's traffic diagnostics (fetch_bytes,
  * data_bytes, cow_pages, device_insts) may differ by what the parked trials
@@ -580,7 +581,8 @@ fi_status fi_set_tick_map(fi_engine *e, int where);
 #define FI_TICK_CONTRACT_NUMINST 0
 #define FI_TICK_CONTRACT_LITERAL 1
 fi_status fi_set_tick_contract(fi_engine *e, int contract);
-/* The device map alone, for comparison with fi_map_tick_sites: ts = NULL
+/* The device map alone, for comparison with fi_map_tick_sites (one function
+ * compiled for both: what differs is the table upload and the kernel): ts = NULL
  * samples trials [first_trial, first_trial + n) on the device, else ts[0..n)
  * are mapped (first_trial unused).  ts_out (may be NULL) receives the tick
  * sites; sites, disp and host_out (may be NULL) are fi_map_tick_sites'. */

@@ -27,7 +27,9 @@
 
 #include "fi_checkpoint.h"
 #include "fi_debug.h"
+#include "fi_site_draw.h"
 #include "fi_tick.h"
+#include "fi_tick_map.h"
 #include "fi_types.h"
 #include "rv64_isa.h"
 
@@ -245,25 +247,22 @@ struct fi_engine {
     std::vector<uint64_t> alloc_order;   // process-start pages in allocation order (fi_load_elf's writes)
     bool golden_unmapped = false;        // the golden run freed frames (munmap / brk shrink)
     std::vector<fi_timing_op> t_ops;     // the golden run's attempts as requests
-    std::vector<TickAttempt> t_att;
     std::vector<fi_timing_ticks> t_ticks;
     fi_timing_stats t_stats{};
     std::string t_status = "no golden run";
-    uint32_t clk_esc = 0;                // DevCtx::clk_esc while tick trials run
-    // the device map (fi_set_tick_map; fi_tick_map.h): the packed attempt table, built at its first use
-    int tick_map = FI_TICK_MAP_HOST;
+    // the site map's table (fi_tick_map.h): the attempts and their ticks, packed with the tick model
+    std::vector<uint64_t> tk_done;
+    std::vector<TickRec> tk_rec;
+    int tick_map = FI_TICK_MAP_HOST;                // fi_set_tick_map
     int tick_contract = FI_TICK_CONTRACT_NUMINST;   // fi_set_tick_contract
-    uint64_t *d_tk_done = nullptr;
+    uint64_t *d_tk_done = nullptr;                  // the device map's copy of the table, made at its first use
     TickRec *d_tk_rec = nullptr;
-    uint64_t tk_n = 0;
     // ... and its per-chunk-slot work buffers (ensure_tick_work), [cap] each: the tick sites in fi_site
     // layout, the dispositions, the disp 1 / 2 outcomes, uploaded explicit sites
     fi_site *d_tk_sites[2] = {nullptr, nullptr};
     uint8_t *d_tk_disp[2] = {nullptr, nullptr};
     fi_outcome *d_tk_res[2] = {nullptr, nullptr};
     fi_tick_site *d_tk_in[2] = {nullptr, nullptr};
-    bool tk_run = false;                 // run_chunks maps tick sites (a device tick run is being enqueued)
-    const fi_tick_site *tk_in = nullptr; //   its explicit sites (host; NULL: sampled)
 
     // work buffers, sized for `cap` trials per launch
     uint64_t cap = 0;
@@ -451,7 +450,6 @@ static void free_mem_index(fi_engine *e) {
 }
 static void free_tick_table(fi_engine *e) {
     dfree(e->d_tk_done); dfree(e->d_tk_rec);
-    e->tk_n = 0;
 }
 static void free_fw(fi_engine *e) {
     dfree(e->d_fw_off); dfree(e->d_fw_ev); dfree(e->d_loops);
@@ -995,7 +993,6 @@ static DevCtx base_ctx(fi_engine *e) {
     c.exe_path = e->d_exe; c.exe_len = e->d_exe ? e->exe_path.size() : 0;
     c.tick0 = e->tick0;
     c.clk_until = e->clk_until;
-    c.clk_esc = e->clk_esc;
     c.stdin_data = e->stdin_on ? e->d_stdin : nullptr;
     c.stdin_len = e->stdin_on ? e->stdin_data.size() : 0;
     c.in_pos = e->d_inpos;
@@ -1111,7 +1108,7 @@ static fi_status build_mem_index(fi_engine *e, const std::vector<MemEv> &mev, bo
 // The golden run under TimingSimpleCPU (fi_tick.cpp, fi_timing.cpp): its
 // attempts as requests, then their ticks.  t_status says why not, if not.
 static void tick_prepare(fi_engine *e, const std::vector<MemEv> &mev, bool mev_ok) {
-    e->t_ops.clear(); e->t_att.clear(); e->t_ticks.clear(); e->t_stats = fi_timing_stats{};
+    e->t_ops.clear(); e->t_ticks.clear(); e->tk_done.clear(); e->tk_rec.clear(); e->t_stats = fi_timing_stats{};
     if (e->cpu_model != FI_CPU_TIMING) { e->t_status = "the CPU model is AtomicSimpleCPU (fi_set_cpu_model)"; return; }
     if (e->alloc_order.empty()) { e->t_status = "a checkpoint start: its frame order is not known"; return; }
     if (e->clk_until) { e->t_status = "the golden run reads curTick: its output depends on the CPU model"; return; }
@@ -1119,17 +1116,19 @@ static void tick_prepare(fi_engine *e, const std::vector<MemEv> &mev, bool mev_o
     if (!mev_ok || e->g_trace.empty()) { e->t_status = "the golden access record is incomplete"; return; }
     TickGoldenIn in{&e->g_trace, &e->g_pre, e->text_lo, &mev, &e->alloc_order, e->stack_min0, e->svma_lo,
                     e->svma_hi, kStackBase, kMaxStack, e->golden.ninst, e->golden.ncycles};
-    std::string why = build_tick_attempts(in, e->t_ops, e->t_att);
+    std::vector<TickAttempt> att;
+    std::string why = build_tick_attempts(in, e->t_ops, att);
     if (why.empty()) {
         e->t_ticks.resize(e->t_ops.size());
         if (fi_timing_model_run(e->t_ops.data(), e->t_ops.size(), &e->tparams, e->t_ticks.data(), &e->t_stats))
             why = "the timing model rejected the golden requests (a state gem5 asserts on)";
     }
     if (!why.empty()) {
-        e->t_ops.clear(); e->t_att.clear(); e->t_ticks.clear();
+        e->t_ops.clear(); e->t_ticks.clear();
         e->t_status = why;
         return;
     }
+    pack_tick_table(att, e->t_ticks, e->tk_done, e->tk_rec);
     e->t_status = "";
 }
 
@@ -1141,8 +1140,8 @@ fi_status fi_golden_run(fi_engine *e, fi_golden_info *out) {
     if (st) return st;
     // back to the process-start image only
     e->t_status = "no golden run";
-    e->t_ops.clear(); e->t_att.clear(); e->t_ticks.clear();
-    free_tick_table(e);   // (rebuilt from the new golden run at the next device map)
+    e->t_ops.clear(); e->t_ticks.clear(); e->tk_done.clear(); e->tk_rec.clear();
+    free_tick_table(e);   // (uploaded again from the new golden run's at the next device map)
     e->snaps.resize(1);
     e->tab.resize(e->n_start_frames);
     e->pool.resize((uint64_t)e->n_start_frames * kPage);
@@ -1535,16 +1534,16 @@ fi_status fi_shadow_map(fi_engine *e, uint8_t *shadow, uint64_t cap, uint64_t *n
     return FI_OK;
 }
 
+// The campaign's draw from trial `first` on (fi_site_draw.h); memory words only where there are some
+static DrawCtx campaign_draw(fi_engine *e, uint64_t first) {
+    const uint64_t structures = e->mem_pages.empty() ? e->structures & ~(1ULL << FI_T_MEM) : e->structures;
+    return draw_ctx(e->seed, structures, first, e->bits, e->burst);
+}
+
 static SampleCtx sample_ctx(fi_engine *e, uint64_t first) {
     SampleCtx s{};
-    s.seed = e->seed;
-    s.structures = e->structures;
-    s.bits = e->bits & (e->burst == 1 ? ~0ULL : ((2ULL << (64 - e->burst)) - 1));
-    if (e->mem_pages.empty()) s.structures &= ~(1ULL << FI_T_MEM);
+    s.d = campaign_draw(e, first);
     s.golden_ninst = e->golden.ninst;
-    s.first = first;
-    s.burst = e->burst;
-    s.n_struct = (uint32_t)__builtin_popcountll(s.structures);
     s.mem_pages = e->d_mem_pages;
     s.n_mem_pages = e->mem_pages.size();
     return s;
@@ -1601,10 +1600,12 @@ static std::pair<hipEvent_t, hipEvent_t> &timer_slot(fi_engine *e, uint32_t kind
 
 // One pass over sites[0..k) (keys/perm set) with P private pages per slot:
 // forwarding, sort by inject time, the epochs.  Outcomes to d_out.
-// disp (tick-domain chunks, else NULL): trials with disp[i] != 0 are parked --
+// tick: the sites are mapped tick sites -- this engine's clock is
+// AtomicSimpleCPU's, so a curTick read escapes (DevCtx::clk_esc).
+// disp (device-mapped chunks, else NULL): trials with disp[i] != 0 are parked --
 // dead at injection, so the trial kernels end them at once as the golden run.
 static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *d_out, uint32_t P, hipStream_t st,
-                          const uint8_t *disp = nullptr) {
+                          bool tick, const uint8_t *disp = nullptr) {
     int end_bit = 64 - __builtin_clzll(std::max<uint64_t>(e->golden.ninst, 1));
     // (a dead site ends at injection: an early exit, so not with FI_CFG_NO_EARLY_EXIT)
     const bool fwd = e->fw_ok && !(e->cfg.flags & (FI_CFG_NO_FORWARD | FI_CFG_NO_EARLY_EXIT));
@@ -1632,6 +1633,7 @@ static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *
     c.n_slots = (uint32_t)k;
     c.save = e->d_save;
     c.priv_pages = P;
+    c.clk_esc = tick ? 1u : 0u;
     if (P != e->cfg.private_pages) c.ov_blocks = 0;   // the second pass has its own P' (chunk_end)
     if (c.ov_blocks) HIPCHK(hipMemsetAsync(e->d_ov_next, 0, 4, st));
     HIPCHK(hipMemsetAsync(e->d_cnt, 0, 16 * 4, st));
@@ -1749,7 +1751,8 @@ struct Chunk {
     fi_site *sites = nullptr;
     fi_outcome *out = nullptr;
     fi_outcome *host_out = nullptr;   // run_common: where the outcomes go on the host
-    // a tick-domain chunk (else NULL): the tick sites as fi_site, dispositions, disp 1 / 2 outcomes
+    bool tick = false;                // its sites are mapped tick sites (run_pass)
+    // a chunk mapped on the device (else NULL): the tick sites as fi_site, dispositions, disp 1 / 2 outcomes
     const fi_site *tsites = nullptr;
     const uint8_t *disp = nullptr;
     const fi_outcome *res = nullptr;
@@ -1757,7 +1760,7 @@ struct Chunk {
 };
 
 static fi_status chunk_begin(fi_engine *e, const Chunk &ch, hipStream_t st) {
-    fi_status s = run_pass(e, ch.sites, ch.k, ch.out, e->cfg.private_pages, st, ch.disp);
+    fi_status s = run_pass(e, ch.sites, ch.k, ch.out, e->cfg.private_pages, st, ch.tick, ch.disp);
     if (s) return s;
     if (!(e->cfg.flags & FI_CFG_NO_REDO)) {
         uint32_t *cnt = e->d_redo_cnt + ch.slot;
@@ -1782,7 +1785,7 @@ static fi_status chunk_end(fi_engine *e, const Chunk &ch, fi_histogram *d_hist, 
             for (uint64_t d = 0; d < nr; d += B) {
                 const uint64_t b = std::min(B, nr - d);
                 HIPCHK(launch_redo_gather(ch.sites, idx + d, b, e->d_redo_sites, e->d_keys, e->d_perm, st));
-                fi_status s = run_pass(e, e->d_redo_sites, b, e->d_redo_out, (uint32_t)P2, st);
+                fi_status s = run_pass(e, e->d_redo_sites, b, e->d_redo_out, (uint32_t)P2, st, ch.tick);
                 if (s) return s;
                 HIPCHK(launch_redo_scatter(idx + d, b, e->d_redo_out, ch.out, st));
             }
@@ -1818,23 +1821,31 @@ static void hist_add(fi_histogram *dst, const fi_histogram *src) {
 // golden outcome.  in = uploaded explicit sites (NULL: sample from `first`).
 static TickMapCtx tick_map_ctx(fi_engine *e, uint64_t first, const fi_tick_site *in) {
     TickMapCtx c{};
-    c.done = e->d_tk_done; c.rec = e->d_tk_rec; c.n_att = e->tk_n;
+    c.done = e->d_tk_done; c.rec = e->d_tk_rec; c.n_att = e->tk_done.size();
     c.golden_ninst = e->golden.ninst; c.golden_ticks = e->t_stats.ticks;
     c.in = in;
-    c.seed = e->seed; c.structures = e->structures; c.first = first;
-    c.burst = e->burst;
-    c.bits = e->bits & (e->burst == 1 ? ~0ULL : ((2ULL << (64 - e->burst)) - 1));
-    c.n_struct = (uint32_t)__builtin_popcountll(e->structures);
+    c.d = campaign_draw(e, first);
     c.gsub = e->gsub; c.gexit = e->golden.exit_code; c.gdetail = e->gdetail;
     c.literal = e->tick_contract == FI_TICK_CONTRACT_LITERAL ? 1u : 0u;
     return c;
 }
 
-// Trials [first, first + n) (sampled on the device) or the given sites, in
-// chunks of at most e->cap; outcomes to out_dev (device, n entries) or
-// out_host (through the alternating device buffers), histogram added to
-// d_hist.  The event pair ev0 / ev1 spans the whole call.
-static fi_status run_chunks(fi_engine *e, uint64_t first, const fi_site *sites, uint64_t n, fi_outcome *out_dev,
+// Where a run's sites come from: given (host arrays of n entries), or sampled
+// on the device as trials first, first + 1, ...  A tick run's sites are tick
+// sites: mapped by the caller (sites) or, in the sampler's place, on the
+// device (ticks / sampled).
+struct SiteSource {
+    const fi_site *sites = nullptr;
+    const fi_tick_site *ticks = nullptr;
+    bool sampled = false;
+    bool tick = false;
+};
+
+// Trials [first, first + n) or the given sites (src), in chunks of at most
+// e->cap; outcomes to out_dev (device, n entries) or out_host (through the
+// alternating device buffers), histogram added to d_hist.  The event pair
+// ev0 / ev1 spans the whole call.
+static fi_status run_chunks(fi_engine *e, uint64_t first, const SiteSource &src, uint64_t n, fi_outcome *out_dev,
                             fi_outcome *out_host, fi_histogram *d_hist, hipStream_t st) {
     HIPCHK(hipMemsetAsync(e->d_stats, 0, kNStats * sizeof(unsigned long long), st));
     HIPCHK(hipEventRecord(e->ev0, st));
@@ -1849,19 +1860,20 @@ static fi_status run_chunks(fi_engine *e, uint64_t first, const fi_site *sites, 
         ch.sites = ch.slot ? e->d_sites_alt : e->d_sites;
         ch.out = out_dev ? out_dev + done : ch.slot ? e->d_out_alt : e->d_out;
         ch.host_out = out_host ? out_host + done : nullptr;
-        if (e->tk_run) {   // tick sites: the mapper takes the sampler's place
+        ch.tick = src.tick;
+        if (src.sites) {
+            HIPCHK(hipMemcpyAsync(ch.sites, src.sites + done, ch.k * sizeof(fi_site), hipMemcpyHostToDevice, st));
+            HIPCHK(launch_keys(ch.sites, ch.k, e->d_keys, e->d_perm, st));
+        } else if (src.tick) {   // tick sites: the mapper takes the sampler's place
             ch.tsites = e->d_tk_sites[ch.slot]; ch.disp = e->d_tk_disp[ch.slot]; ch.res = e->d_tk_res[ch.slot];
             const fi_tick_site *in = nullptr;
-            if (e->tk_in) {
-                HIPCHK(hipMemcpyAsync(e->d_tk_in[ch.slot], e->tk_in + done, ch.k * sizeof(fi_tick_site),
+            if (src.ticks) {
+                HIPCHK(hipMemcpyAsync(e->d_tk_in[ch.slot], src.ticks + done, ch.k * sizeof(fi_tick_site),
                                       hipMemcpyHostToDevice, st));
                 in = e->d_tk_in[ch.slot];
             }
             HIPCHK(launch_tick_map(tick_map_ctx(e, first + done, in), ch.k, ch.sites, e->d_keys, e->d_perm,
                                    e->d_tk_sites[ch.slot], e->d_tk_disp[ch.slot], e->d_tk_res[ch.slot], st));
-        } else if (sites) {
-            HIPCHK(hipMemcpyAsync(ch.sites, sites + done, ch.k * sizeof(fi_site), hipMemcpyHostToDevice, st));
-            HIPCHK(launch_keys(ch.sites, ch.k, e->d_keys, e->d_perm, st));
         } else {
             HIPCHK(launch_sample(sample_ctx(e, first + done), ch.k, ch.sites, e->d_keys, e->d_perm, st));
         }
@@ -1891,18 +1903,9 @@ static fi_status run_chunks(fi_engine *e, uint64_t first, const fi_site *sites, 
     return FI_OK;
 }
 
-static fi_status run_common(fi_engine *e, uint64_t first, const fi_site *sites, uint64_t n, fi_outcome *out,
-                            fi_histogram *hist) {
-    if (!e) return FI_E_ARG;
-    if (!e->have_golden) return fail(e, FI_E_STATE, "golden run required");
-    if (!sites && !e->structures) return fail(e, FI_E_STATE, "fi_set_campaign first");
-    HIPCHK(hipSetDevice(e->dev));
-    const uint64_t chunk = e->cfg.max_trials_per_launch;
-    fi_status s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), chunk));
-    if (s) return s;
-    HIPCHK(hipMemsetAsync(e->d_hist, 0, sizeof(fi_histogram), e->stream));
-    s = run_chunks(e, first, sites, n, nullptr, out, e->d_hist, e->stream);
-    if (s) return s;
+// The end of a blocking run on e->stream into e->d_hist: wait for it, its
+// device time (ev0 .. ev1) to last_ms, its histogram added to hist.
+static fi_status run_finish(fi_engine *e, fi_histogram *hist) {
     HIPCHK(hipStreamSynchronize(e->stream));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
@@ -1913,6 +1916,20 @@ static fi_status run_common(fi_engine *e, uint64_t first, const fi_site *sites, 
         hist_add(hist, &h);
     }
     return FI_OK;
+}
+
+static fi_status run_common(fi_engine *e, uint64_t first, const SiteSource &src, uint64_t n, fi_outcome *out,
+                            fi_histogram *hist) {
+    if (!e) return FI_E_ARG;
+    if (!e->have_golden) return fail(e, FI_E_STATE, "golden run required");
+    if (src.sampled && !e->structures) return fail(e, FI_E_STATE, "fi_set_campaign first");
+    HIPCHK(hipSetDevice(e->dev));
+    const uint64_t chunk = e->cfg.max_trials_per_launch;
+    fi_status s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), chunk));
+    if (s) return s;
+    HIPCHK(hipMemsetAsync(e->d_hist, 0, sizeof(fi_histogram), e->stream));
+    s = run_chunks(e, first, src, n, nullptr, out, e->d_hist, e->stream);
+    return s ? s : run_finish(e, hist);
 }
 
 fi_status fi_wait_translation(fi_engine *e, fi_golden_info *out) {
@@ -1926,12 +1943,13 @@ fi_status fi_wait_translation(fi_engine *e, fi_golden_info *out) {
 }
 
 fi_status fi_run_trials(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist) {
-    return run_common(e, first, nullptr, n, out, hist);
+    return run_common(e, first, SiteSource{nullptr, nullptr, true, false}, n, out, hist);
 }
 
 fi_status fi_run_sites(fi_engine *e, const fi_site *sites, uint64_t n, fi_outcome *out, fi_histogram *hist) {
     if (!sites && n) return FI_E_ARG;
-    return run_common(e, 0, sites, n, out, hist);
+    // (no sites: an empty sampled run)
+    return run_common(e, 0, SiteSource{sites, nullptr, !sites, false}, n, out, hist);
 }
 
 // ---------------------------------------------------- tick-domain injection
@@ -1964,83 +1982,69 @@ fi_status fi_tick_trace(fi_engine *e, fi_timing_op *ops, fi_timing_ticks *ticks,
     return FI_OK;
 }
 
-static uint64_t splitmix_host(uint64_t &s) {   // the sampler's SplitMix64 (fi_kernels.hip)
-    uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-static uint64_t mulhi64(uint64_t a, uint64_t b) { return (uint64_t)(((unsigned __int128)a * b) >> 64); }
-
 static fi_status tick_ready(fi_engine *e) {
     if (!e->have_golden) return fail(e, FI_E_STATE, "golden run required");
     if (!e->t_status.empty()) return fail(e, FI_E_STATE, "tick model: %s", e->t_status.c_str());
     return FI_OK;
 }
 
-fi_status fi_sample_tick_sites(fi_engine *e, uint64_t first, uint64_t n, fi_tick_site *out) {
-    if (!e || (!out && n)) return FI_E_ARG;
+// What every tick entry point refuses, host map or device map, in one order
+// and one wording: the campaign's draw (sampled), a run's restrictions (run),
+// then each explicit site (ts; NULL: none).
+static fi_status tick_check(fi_engine *e, const fi_tick_site *ts, uint64_t n, bool sampled, bool run) {
     fi_status st = tick_ready(e);
     if (st) return st;
-    if (!e->structures) return fail(e, FI_E_STATE, "fi_set_campaign first");
-    if (e->structures & (1ULL << FI_T_MEM)) return fail(e, FI_E_ARG, "tick sites: memory words are not supported");
-    const uint64_t structures = e->structures;
-    const uint32_t nt = (uint32_t)__builtin_popcountll(structures), burst = e->burst;
-    const uint64_t valid = burst == 1 ? ~0ULL : ((2ULL << (64 - burst)) - 1);
-    for (uint64_t i = 0; i < n; i++) {   // fi_sample_kernel's draw with the golden run's ticks for numInst
-        const uint64_t id = first + i;
-        uint64_t s = e->seed ^ (id * 0xD6E8FEB86659FD93ULL);
-        const uint64_t r0 = splitmix_host(s), r1 = splitmix_host(s), r2 = splitmix_host(s);
-        fi_tick_site &o = out[i];
-        o.tick = mulhi64(r0, e->t_stats.ticks);
-        const uint64_t k = mulhi64(r1, nt);
-        uint64_t m = structures;
-        for (uint64_t j = 0; j < k; j++) m &= m - 1;
-        o.target = (uint32_t)__builtin_ctzll(m);
-        uint64_t b;
-        if ((e->bits & valid) == valid) {
-            b = mulhi64(r2, 65 - burst);
-        } else {
-            uint64_t mm = e->bits & valid;
-            const uint64_t kk = mulhi64(r2, (uint64_t)__builtin_popcountll(mm));
-            for (uint64_t j = 0; j < kk; j++) mm &= mm - 1;
-            b = (uint64_t)__builtin_ctzll(mm);
-        }
-        o.mask = (burst == 64 ? ~0ULL : ((1ULL << burst) - 1)) << b;
-        o.trial = (uint32_t)id;
+    if (sampled) {
+        if (!e->structures) return fail(e, FI_E_STATE, "fi_set_campaign first");
+        if (e->structures & (1ULL << FI_T_MEM)) return fail(e, FI_E_ARG, "tick sites: memory words are not supported");
     }
-    return FI_OK;
-}
-
-fi_status fi_map_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi_site *sites, uint8_t *disp,
-                            fi_outcome *host_out) {
-    if (!e || (n && (!ts || !sites || !disp))) return FI_E_ARG;
-    fi_status st = tick_ready(e);
-    if (st) return st;
-    for (uint64_t i = 0; i < n; i++) {
+    if (run && (e->protect || e->protect_opc))
+        return fail(e, FI_E_ARG, "tick sites: selective replication (fi_set_protect*) is not supported");
+    for (uint64_t i = 0; ts && i < n; i++) {
         const fi_tick_site &t = ts[i];
         const bool target_ok = (t.target >= 1 && t.target <= FI_T_PC) || t.target == FI_T_RESULT;
         if (!t.mask || !target_ok || t.tick >= e->t_stats.ticks)
             return fail(e, FI_E_ARG, "tick site %llu: target %u, tick %llu (golden run %llu ticks)",
                         (unsigned long long)i, t.target, (unsigned long long)t.tick,
                         (unsigned long long)e->t_stats.ticks);
-        const TickMapped m = map_tick_site(e->t_att, e->t_ticks, e->golden.ninst, t.tick, t.target, t.mask, t.trial,
-                                           e->tick_contract == FI_TICK_CONTRACT_LITERAL);
+    }
+    return FI_OK;
+}
+
+fi_status fi_sample_tick_sites(fi_engine *e, uint64_t first, uint64_t n, fi_tick_site *out) {
+    if (!e || (!out && n)) return FI_E_ARG;
+    fi_status st = tick_check(e, nullptr, n, true, false);
+    if (st) return st;
+    const DrawCtx d = campaign_draw(e, first);   // the sampler's draw with the golden run's ticks for numInst
+    for (uint64_t i = 0; i < n; i++) {
+        const SiteDraw s = draw_site(d, i, e->t_stats.ticks);
+        out[i] = fi_tick_site{s.when, s.mask, s.target, s.trial};
+    }
+    return FI_OK;
+}
+
+// The host map over checked sites (tick_check)
+static void map_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi_site *sites, uint8_t *disp,
+                           fi_outcome *host_out) {
+    const uint32_t literal = e->tick_contract == FI_TICK_CONTRACT_LITERAL ? 1u : 0u;
+    for (uint64_t i = 0; i < n; i++) {
+        const fi_tick_site &t = ts[i];
+        const TickMap m = tick_map_site(e->tk_done.data(), e->tk_rec.data(), e->tk_done.size(), e->golden.ninst,
+                                        t.tick, t.target, t.mask, t.trial, literal);
         disp[i] = (uint8_t)m.disp;
         sites[i] = m.site;
-        if (host_out) {
-            fi_outcome o{};
-            if (m.disp == 1) {   // the golden run itself
-                o.cls = FI_MASKED; o.sub = (uint8_t)e->gsub; o.exit_code = (uint8_t)e->golden.exit_code;
-                o.flags = 1; o.detail = e->gdetail; o.ninst = e->golden.ninst;
-            } else if (m.disp == 2) {
-                const TickAttempt &A = e->t_att[m.attempt];
-                o.cls = FI_ESCAPE; o.sub = FI_ESC_TIMING; o.exit_code = (uint8_t)m.reason;
-                o.flags = 1; o.detail = (uint32_t)A.pc; o.ninst = A.n;
-            }
-            host_out[i] = o;
-        }
+        if (host_out)
+            host_out[i] = tick_map_outcome(m, e->tk_rec[m.attempt], e->gsub, e->golden.exit_code, e->gdetail,
+                                           e->golden.ninst);
     }
+}
+
+fi_status fi_map_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi_site *sites, uint8_t *disp,
+                            fi_outcome *host_out) {
+    if (!e || (n && (!ts || !sites || !disp))) return FI_E_ARG;
+    fi_status st = tick_check(e, ts, n, false, false);
+    if (st) return st;
+    map_tick_sites(e, ts, n, sites, disp, host_out);
     return FI_OK;
 }
 
@@ -2060,19 +2064,15 @@ fi_status fi_set_tick_contract(fi_engine *e, int contract) {
     return FI_OK;
 }
 
-// The packed attempt table on the device, built from the golden run's
-// attempts at the first device map after it (fi_golden_run drops it).
+// The packed attempt table on the device: the host map's own, uploaded at the
+// first device map after a golden run (fi_golden_run drops the copy).
 static fi_status ensure_tick_table(fi_engine *e) {
     if (e->d_tk_done) return FI_OK;
-    std::vector<uint64_t> done;
-    std::vector<TickRec> rec;
-    pack_tick_table(e->t_att, e->t_ticks, done, rec);
-    if (done.empty()) return fail(e, FI_E_STATE, "tick model: no attempts");
-    HIPCHK(hipMalloc(&e->d_tk_done, done.size() * sizeof(uint64_t)));
-    HIPCHK(hipMalloc(&e->d_tk_rec, rec.size() * sizeof(TickRec)));
-    HIPCHK(hipMemcpy(e->d_tk_done, done.data(), done.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_tk_rec, rec.data(), rec.size() * sizeof(TickRec), hipMemcpyHostToDevice));
-    e->tk_n = done.size();
+    if (e->tk_done.empty()) return fail(e, FI_E_STATE, "tick model: no attempts");
+    HIPCHK(hipMalloc(&e->d_tk_done, e->tk_done.size() * sizeof(uint64_t)));
+    HIPCHK(hipMalloc(&e->d_tk_rec, e->tk_rec.size() * sizeof(TickRec)));
+    HIPCHK(hipMemcpy(e->d_tk_done, e->tk_done.data(), e->tk_done.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(e->d_tk_rec, e->tk_rec.data(), e->tk_rec.size() * sizeof(TickRec), hipMemcpyHostToDevice));
     return FI_OK;
 }
 
@@ -2089,29 +2089,6 @@ static fi_status ensure_tick_work(fi_engine *e) {
     return FI_OK;
 }
 
-// The host path's checks, in its order and words: a sampled run's
-// (fi_sample_tick_sites, then fi_run_tick_sites) or an explicit one's
-// (fi_run_tick_sites, then fi_map_tick_sites site by site).
-static fi_status tick_check(fi_engine *e, const fi_tick_site *ts, uint64_t n, bool run) {
-    fi_status st = tick_ready(e);
-    if (st) return st;
-    if (!ts) {
-        if (!e->structures) return fail(e, FI_E_STATE, "fi_set_campaign first");
-        if (e->structures & (1ULL << FI_T_MEM)) return fail(e, FI_E_ARG, "tick sites: memory words are not supported");
-    }
-    if (run && (e->protect || e->protect_opc))
-        return fail(e, FI_E_ARG, "tick sites: selective replication (fi_set_protect*) is not supported");
-    for (uint64_t i = 0; ts && i < n; i++) {
-        const fi_tick_site &t = ts[i];
-        const bool target_ok = (t.target >= 1 && t.target <= FI_T_PC) || t.target == FI_T_RESULT;
-        if (!t.mask || !target_ok || t.tick >= e->t_stats.ticks)
-            return fail(e, FI_E_ARG, "tick site %llu: target %u, tick %llu (golden run %llu ticks)",
-                        (unsigned long long)i, t.target, (unsigned long long)t.tick,
-                        (unsigned long long)e->t_stats.ticks);
-    }
-    return FI_OK;
-}
-
 static fi_status tick_device_prepare(fi_engine *e, uint64_t n) {
     HIPCHK(hipSetDevice(e->dev));
     fi_status s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch));
@@ -2120,55 +2097,33 @@ static fi_status tick_device_prepare(fi_engine *e, uint64_t n) {
     return s;
 }
 
-// Enqueue a device tick run: run_chunks with the mapper in the sampler's
-// place.  DevCtx::clk_esc is 1 in every launch of the run (a DevCtx is copied
-// at its launch) and 0 again on every way out.
-static fi_status tick_run_chunks(fi_engine *e, uint64_t first, const fi_tick_site *ts, uint64_t n, fi_outcome *out_dev,
-                                 fi_outcome *out_host, fi_histogram *d_hist, hipStream_t st) {
-    e->tk_run = true;
-    e->tk_in = ts;
-    e->clk_esc = 1;   // this engine's clock is AtomicSimpleCPU's: a curTick read escapes
-    const fi_status s = run_chunks(e, first, nullptr, n, out_dev, out_host, d_hist, st);
-    e->clk_esc = 0;
-    e->tk_in = nullptr;
-    e->tk_run = false;
-    return s;
-}
-
-// fi_run_tick_sites / fi_run_tick_trials with the device map: only outcomes
+// fi_run_tick_sites / fi_run_tick_trials with the device map (ts NULL:
+// sampled): run_chunks with the mapper in the sampler's place; only outcomes
 // and the histogram come back.
 static fi_status tick_run_device(fi_engine *e, uint64_t first, const fi_tick_site *ts, uint64_t n, fi_outcome *out,
                                  fi_histogram *hist) {
-    fi_status s = tick_check(e, ts, n, true);
+    fi_status s = tick_check(e, ts, n, !ts, true);
     if (s || !n) return s;
     if ((s = tick_device_prepare(e, n))) return s;
     HIPCHK(hipMemsetAsync(e->d_hist, 0, sizeof(fi_histogram), e->stream));
-    if ((s = tick_run_chunks(e, first, ts, n, nullptr, out, e->d_hist, e->stream))) return s;
-    HIPCHK(hipStreamSynchronize(e->stream));
-    float ms = 0;
-    HIPCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    e->last_ms = ms;
-    if (hist) {
-        fi_histogram h;
-        HIPCHK(hipMemcpy(&h, e->d_hist, sizeof h, hipMemcpyDeviceToHost));
-        hist_add(hist, &h);
-    }
-    return FI_OK;
+    s = run_chunks(e, first, SiteSource{nullptr, ts, !ts, true}, n, nullptr, out, e->d_hist, e->stream);
+    return s ? s : run_finish(e, hist);
 }
 
 fi_status fi_run_tick_trials_device(fi_engine *e, uint64_t first, uint64_t n, void *d_out, void *d_hist, void *stream) {
     if (!e || !d_out || !d_hist) return FI_E_ARG;
-    fi_status s = tick_check(e, nullptr, n, true);
+    fi_status s = tick_check(e, nullptr, n, true, true);
     if (s || !n) return s;
     if ((s = tick_device_prepare(e, n))) return s;
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    return tick_run_chunks(e, first, nullptr, n, (fi_outcome *)d_out, nullptr, (fi_histogram *)d_hist, st);
+    return run_chunks(e, first, SiteSource{nullptr, nullptr, true, true}, n, (fi_outcome *)d_out, nullptr,
+                      (fi_histogram *)d_hist, st);
 }
 
 fi_status fi_map_tick_sites_device(fi_engine *e, const fi_tick_site *ts, uint64_t first, uint64_t n,
                                    fi_tick_site *ts_out, fi_site *sites, uint8_t *disp, fi_outcome *host_out) {
     if (!e || (n && (!sites || !disp))) return FI_E_ARG;
-    fi_status s = tick_check(e, ts, n, false);
+    fi_status s = tick_check(e, ts, n, !ts, false);
     if (s || !n) return s;
     if ((s = tick_device_prepare(e, n))) return s;
     std::vector<fi_site> tsv(ts_out ? std::min<uint64_t>(n, e->cap) : 0);
@@ -2196,15 +2151,12 @@ fi_status fi_map_tick_sites_device(fi_engine *e, const fi_tick_site *ts, uint64_
 fi_status fi_run_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi_outcome *out, fi_histogram *hist) {
     if (!e || (n && !ts)) return FI_E_ARG;
     if (e->tick_map == FI_TICK_MAP_DEVICE && n) return tick_run_device(e, 0, ts, n, out, hist);
-    fi_status st = tick_ready(e);
+    fi_status st = tick_check(e, ts, n, false, true);
     if (st) return st;
-    if (e->protect || e->protect_opc)
-        return fail(e, FI_E_ARG, "tick sites: selective replication (fi_set_protect*) is not supported");
     std::vector<fi_site> sites(n);
     std::vector<uint8_t> disp(n);
     std::vector<fi_outcome> res(n);
-    st = fi_map_tick_sites(e, ts, n, sites.data(), disp.data(), res.data());
-    if (st) return st;
+    map_tick_sites(e, ts, n, sites.data(), disp.data(), res.data());
     std::vector<fi_site> run;
     std::vector<uint64_t> idx;
     for (uint64_t i = 0; i < n; i++)
@@ -2212,9 +2164,7 @@ fi_status fi_run_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi
     fi_histogram dh{};
     if (!run.empty()) {
         std::vector<fi_outcome> ro(run.size());
-        e->clk_esc = 1;   // this engine's clock is AtomicSimpleCPU's: a curTick read escapes
-        st = run_common(e, 0, run.data(), run.size(), ro.data(), &dh);
-        e->clk_esc = 0;
+        st = run_common(e, 0, SiteSource{run.data(), nullptr, false, true}, run.size(), ro.data(), &dh);
         if (st) return st;
         for (size_t q = 0; q < idx.size(); q++) res[idx[q]] = ro[q];
     }
@@ -2253,7 +2203,8 @@ fi_status fi_run_trials_device(fi_engine *e, uint64_t first, uint64_t n, void *d
     const uint64_t chunk = e->cfg.max_trials_per_launch;
     fi_status s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), chunk));
     if (s) return s;
-    return run_chunks(e, first, nullptr, n, (fi_outcome *)d_out, nullptr, (fi_histogram *)d_hist, st);
+    return run_chunks(e, first, SiteSource{nullptr, nullptr, true, false}, n, (fi_outcome *)d_out, nullptr,
+                      (fi_histogram *)d_hist, st);
 }
 
 fi_status fi_sync(fi_engine *e) {

@@ -1,5 +1,6 @@
-// Tick-domain injection: the golden request list and the tick -> numInst site
-// map (fi_tick.h; include/fi_engine.h "Tick-domain injection").
+// Tick-domain injection: the golden request list, and its attempts packed for
+// the tick -> numInst site map (fi_tick.h; the map itself: fi_tick_map.h;
+// include/fi_engine.h "Tick-domain injection").
 //
 // The golden request list.  TimingSimpleCPU runs the same instructions as
 // AtomicSimpleCPU; what it adds is a fetch-execute *attempt* per atomic tick
@@ -15,25 +16,6 @@
 // memory (Process::allocateMem -> MemPool, sim/process.cc:318-343,
 // sim/mem_pool.cc:96-102): the image as initState writes it, argsInit's
 // stack, then each page a fault or a syscall write fixes up.
-//
-// The site map.  A flip at tick t happens before every event of tick t; the
-// attempt in flight is the first whose last event is at or after t.  Before
-// it executes (its fetch outstanding) a register flip is a numInst injection
-// at its numInst; while its data access is outstanding the sources are read,
-// so the flip takes effect from the next instruction on -- unless the
-// completion writes that register (TimingSimpleCPU::completeDataAccess ->
-// completeAcc).  A pc flip while the fetch is outstanding leaves the
-// instruction fetched from the old word: executed at the new pc (decode sets
-// npc, decoder.cc:135-173), its effect is the golden instruction's with the
-// next pc, a link or a branch target moved by the difference -- one numInst
-// site after it; a pc flip during the data access goes through
-// PCState::set, npc = pc + 4, which advancePC then takes.  The cases that are
-// not one numInst site are FI_ESC_TIMING (FI_TK_*) -- or, under the literal
-// contract (fi_set_tick_contract), sites with a tick descriptor in
-// fi_site.addr (FI_SITE_TK_*) that the trial kernels run as the timing CPU
-// does: the flip applied after the non-counting attempts before it, the next
-// fetch reading the old pc's word (fi_trial.hip fetch_lane_tk).  FI_TK_MACRO
-// stays an escape there, as does FI_TK_CLOCK at run time.
 #include "fi_tick.h"
 
 #include <algorithm>
@@ -244,79 +226,6 @@ void pack_tick_table(const std::vector<TickAttempt> &att, const std::vector<fi_t
                             (a.end ? kTrEnd : 0) | (a.macro ? kTrMacro : 0) |
                             (a.next_pc != a.pc + a.len ? kTrTaken : 0));
         rec[i] = r;
-    }
-}
-
-TickMapped map_tick_site(const std::vector<TickAttempt> &att, const std::vector<fi_timing_ticks> &ticks,
-                         uint64_t golden_ninst, uint64_t t, uint32_t target, uint64_t mask, uint32_t trial,
-                         bool literal) {
-    TickMapped r;
-    // the attempt in flight: the first whose last event is at or after t
-    const auto it = std::lower_bound(ticks.begin(), ticks.end(), t,
-                                     [](const fi_timing_ticks &x, uint64_t v) { return x.done < v; });
-    const uint64_t j = (uint64_t)(it - ticks.begin());
-    r.attempt = j;
-    const TickAttempt &A = att[j];
-    const fi_timing_ticks &T = ticks[j];
-    enum { FETCH1, FETCH2, DATA } ph = (A.nfetch == 2 && t <= T.fetch_done[0]) ? FETCH1
-                                     : t <= T.exec ? (A.nfetch == 2 ? FETCH2 : FETCH1) : DATA;
-    uint64_t g = j;   // the attempts since the last commit (ecalls, page-fault retries)
-    while (g > 0 && !att[g - 1].commits) g--;
-    // the literal contract: the flip applied after the j - g attempts before it
-    // (FI_SITE_TK_SKIP); a pc flip whose fetch went out with the old pc
-    // (FI_SITE_TK_FETCH: the fetch override, then the decoder's own state)
-    const bool lit = literal && j - g <= FI_SITE_TK_SKIP_MAX;
-    const uint64_t skip = (j - g) << FI_SITE_TK_SKIP_SHIFT;
-    auto site = [&](uint32_t tg, uint64_t m, uint64_t inst, uint64_t desc = 0) {
-        r.disp = 0;
-        r.site.inst = inst; r.site.mask = m; r.site.addr = desc; r.site.target = tg; r.site.trial = trial;
-        if (inst > golden_ninst) r.disp = 1;   // after the run's last commit: the golden run
-        return r;
-    };
-    auto golden = [&]() { r.disp = 1; return r; };
-    auto escape = [&](uint32_t why) { r.disp = 2; r.reason = why; return r; };
-    auto refetch = [&]() {
-        return site(FI_T_PC, mask, A.n, skip | FI_SITE_TK_FETCH | (ph == FETCH2 ? FI_SITE_TK_FETCH2 : 0));
-    };
-    if (target == FI_T_RESULT) return site(FI_T_RESULT, mask, A.n);   // the first commit at or after t
-    if (target >= 1 && target <= 31) {
-        if (ph == DATA) return A.done_rd == target ? golden() : site(target, mask, A.n + 1);
-        for (uint64_t q = g; q < j; q++) {   // the flip lands after these: it must commute with them
-            const TickAttempt &Q = att[q];
-            if ((Q.ecall && target >= 10 && target <= 17) || (Q.pgfault && (target == Q.rs1 || target == Q.rs2)))
-                return lit ? site(target, mask, A.n, skip) : escape(FI_TK_NONCOUNT);
-        }
-        return site(target, mask, A.n);
-    }
-    // the pc
-    if (g != j && !lit) return escape(FI_TK_NONCOUNT);
-    const uint64_t pc = A.pc, np = pc ^ mask;
-    const bool same_word = ((pc ^ np) & ~3ULL) == 0;
-    // (after non-counting attempts the literal contract takes the oracle's order: its literal run is the reference)
-    if (ph == DATA) return (A.macro && g == j) ? escape(FI_TK_MACRO) : site(FI_T_PC, (pc + A.len) ^ (np + 4), A.n + 1);
-    if (ph == FETCH1 && same_word) return site(FI_T_PC, mask, A.n, skip);
-    if (!A.commits || A.end) return lit ? refetch() : escape(FI_TK_FAULTOP);
-    if (ph == FETCH1) {
-        if (A.nfetch == 2) return lit ? refetch() : escape(FI_TK_STRADDLE1);
-        if ((pc & 3) != (np & 3)) return lit ? refetch() : escape(FI_TK_ALIGN);
-    } else if ((np & 3) == 0) {
-        return lit ? refetch() : escape(FI_TK_STRADDLE2);
-    }
-    if (g != j) return refetch();
-    // the golden instruction executed at np: its effect, moved by np - pc
-    switch (A.ctl) {
-    case kCtlAuipc: return lit ? refetch() : escape(FI_TK_TWO);
-    case kCtlJal:
-        if (A.rd) return lit ? refetch() : escape(FI_TK_TWO);
-        return site(FI_T_PC, (pc + (uint64_t)A.imm) ^ (np + (uint64_t)A.imm), A.n + 1);
-    case kCtlJalr:
-        if (!A.rd) return golden();   // the target comes from rs1
-        return site(A.rd, (pc + A.len) ^ (np + A.len), A.n + 1);
-    case kCtlBranch: {
-        const uint64_t x = A.next_pc != pc + A.len ? (uint64_t)A.imm : A.len;
-        return site(FI_T_PC, (pc + x) ^ (np + x), A.n + 1);
-    }
-    default: return site(FI_T_PC, (pc + A.len) ^ (np + A.len), A.n + 1);
     }
 }
 

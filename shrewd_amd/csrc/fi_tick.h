@@ -1,7 +1,8 @@
 // Tick-domain injection under TimingSimpleCPU (include/fi_engine.h,
 // "Tick-domain injection"): the golden run's fetch-execute attempts as
-// requests for the timing model (fi_timing.cpp), and the map from a fault at
-// tick t to the numInst site the trial kernels run.  Host code.
+// requests for the timing model (fi_timing.cpp), and the same attempts with
+// their ticks packed for the map from a fault at tick t to the numInst site
+// the trial kernels run (fi_tick_map.h).  Host code.
 #pragma once
 
 #include <cstdint>
@@ -13,7 +14,8 @@
 
 namespace fi {
 
-// One fetch-execute attempt of the golden run, as the site map needs it.
+// One fetch-execute attempt of the golden run, as the site map needs it
+// (pack_tick_table's input).
 struct TickAttempt {
     uint64_t pc = 0, next_pc = 0;   // its pc; the next attempt's pc
     uint64_t n = 0;                 // numInst before it
@@ -43,23 +45,10 @@ struct TickGoldenIn {
 std::string build_tick_attempts(const TickGoldenIn &in, std::vector<fi_timing_op> &ops,
                                 std::vector<TickAttempt> &att);
 
-// The attempts and their ticks packed for the device map (fi_tick_map.h):
+// The attempts and their ticks packed for the site map (fi_tick_map.h):
 // done[i] = ticks[i].done, rec[i] = attempt i with its ticks and the index of
 // the first attempt since the last commit.
 void pack_tick_table(const std::vector<TickAttempt> &att, const std::vector<fi_timing_ticks> &ticks,
                      std::vector<uint64_t> &done, std::vector<TickRec> &rec);
-
-// The site map: disposition 0 run `site`, 1 golden-equal, 2 escape (reason).
-struct TickMapped {
-    int disp = 0;
-    uint32_t reason = 0;
-    fi_site site{};
-    uint64_t attempt = 0;
-};
-// literal (fi_set_tick_contract FI_TICK_CONTRACT_LITERAL): the FI_TK_NONCOUNT ..
-// FI_TK_FAULTOP cases become sites with a tick descriptor (fi_site.addr).
-TickMapped map_tick_site(const std::vector<TickAttempt> &att, const std::vector<fi_timing_ticks> &ticks,
-                         uint64_t golden_ninst, uint64_t t, uint32_t target, uint64_t mask, uint32_t trial,
-                         bool literal = false);
 
 }  // namespace fi

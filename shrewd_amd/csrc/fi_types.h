@@ -289,22 +289,33 @@ static_assert(sizeof(TickRec) == 48, "TickRec layout");
 constexpr uint8_t kTrCommits = 1, kTrEcall = 2, kTrPgfault = 4, kTrEnd = 8, kTrMacro = 16;
 constexpr uint8_t kTrTaken = 32;     // the next attempt's pc is not pc + len
 
+// host + device functions shared with plain host builds (fi_site_draw.h, fi_tick_map.h)
+#if defined(__HIPCC__) || defined(__CUDACC__)
+#define FI_TM_HD __host__ __device__
+#else
+#define FI_TM_HD
+#endif
+
+// The campaign's site draw (fi_site_draw.h; filled by draw_ctx there)
+struct DrawCtx {
+    uint64_t seed, structures, first;
+    uint64_t bits;                   // eligible lowest-bit positions (already limited to 0..64-burst)
+    uint32_t burst, n_struct;
+};
+
 struct TickMapCtx {
     const uint64_t *done;            // [n_att] ascending
     const TickRec *rec;              // [n_att]
     uint64_t n_att, golden_ninst, golden_ticks;
-    const fi_tick_site *in;          // explicit tick sites; NULL = sample trials first, first + 1, ...
-    uint64_t seed, structures, first;
-    uint64_t bits;                   // as SampleCtx::bits
-    uint32_t burst, n_struct;
+    const fi_tick_site *in;          // explicit tick sites; NULL = sample trials d.first, d.first + 1, ...
+    DrawCtx d;
     uint32_t gsub, gexit, gdetail;   // the golden outcome (a disp-1 trial's record)
     uint32_t literal;                // fi_set_tick_contract: 1 = FI_TICK_CONTRACT_LITERAL
 };
 
 struct SampleCtx {
-    uint64_t seed, structures, golden_ninst, first;
-    uint32_t burst, n_struct;
-    uint64_t bits;                   // eligible lowest-bit positions (already limited to 0..64-burst)
+    DrawCtx d;
+    uint64_t golden_ninst;
     const uint64_t *mem_pages;
     uint64_t n_mem_pages;
 };

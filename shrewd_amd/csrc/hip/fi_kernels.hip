@@ -12,6 +12,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "fi_types.h"
+#include "fi_site_draw.h"
 #include "fi_tick_map.h"
 #include "fi_device.h"
 #include "rv64_isa.h"
@@ -20,43 +21,18 @@
 
 namespace fi {
 
-// SplitMix64 (Steele, Lea & Flood 2014)
-__host__ __device__ inline uint64_t splitmix(uint64_t &s) {
-    uint64_t z = (s += 0x9E3779B97F4A7C15ULL);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
 // ------------------------------------------------------------------ sampler
 __global__ void fi_sample_kernel(SampleCtx c, uint64_t n, fi_site *sites, uint64_t *keys, uint32_t *perm) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const uint64_t id = c.first + i;
-    uint64_t st = c.seed ^ (id * 0xD6E8FEB86659FD93ULL);
-    const uint64_t r0 = splitmix(st), r1 = splitmix(st), r2 = splitmix(st), r3 = splitmix(st);
+    const SiteDraw d = draw_site(c.d, i, c.golden_ninst);
     fi_site s;
-    s.inst = __umul64hi(r0, c.golden_ninst);
-    uint64_t k = __umul64hi(r1, (uint64_t)c.n_struct);
-    uint64_t m = c.structures;
-    for (uint64_t j = 0; j < k; j++) m &= m - 1;
-    s.target = (uint32_t)__builtin_ctzll(m);
-    uint64_t b;
-    if (c.bits == (c.burst == 1 ? ~0ULL : ((2ULL << (64 - c.burst)) - 1))) {
-        b = __umul64hi(r2, (uint64_t)(65 - c.burst));   // every position
-    } else {                                             // the k-th eligible position
-        uint64_t mm = c.bits;
-        const uint64_t kk = __umul64hi(r2, (uint64_t)__popcll(mm));
-        for (uint64_t j = 0; j < kk; j++) mm &= mm - 1;
-        b = (uint64_t)__builtin_ctzll(mm);
-    }
-    s.mask = (c.burst == 64 ? ~0ULL : ((1ULL << c.burst) - 1)) << b;
+    s.inst = d.when; s.mask = d.mask; s.target = d.target; s.trial = d.trial;
     s.addr = 0;
     if (s.target == FI_T_MEM) {
-        const uint64_t w = __umul64hi(r3, c.n_mem_pages * 512);
+        const uint64_t w = mulhi64(d.r3, c.n_mem_pages * 512);
         s.addr = c.mem_pages[w / 512] + (w % 512) * 8;
     }
-    s.trial = (uint32_t)id;
     sites[i] = s;
     keys[i] = s.inst;
     perm[i] = (uint32_t)i;
@@ -71,8 +47,8 @@ __global__ void fi_keys_kernel(const fi_site *sites, uint64_t n, uint64_t *keys,
 
 // ------------------------------------------------------------------ tick-domain sites
 // One trial per thread (DESIGN.md §4g "device map"): the tick site -- drawn
-// with fi_sample_kernel's own draw, golden_ticks in place of numInst, or read
-// from c.in -- is mapped to the numInst site the trial kernels run
+// with fi_sample_kernel's draw (fi_site_draw.h), golden_ticks in place of
+// numInst, or read from c.in -- is mapped to the numInst site the trial kernels run
 // (fi_tick_map.h).  Every trial keeps its slot: disp[i] != 0 (golden-equal,
 // escape) is parked by fi_tick_park_kernel and, for an escape, given res[i]
 // by fi_tick_fix_kernel.  tsites[i] is the tick site in fi_site layout
@@ -89,44 +65,17 @@ __global__ void __launch_bounds__(256) fi_tick_map_kernel(TickMapCtx c, uint64_t
         const fi_tick_site x = c.in[i];
         t.inst = x.tick; t.mask = x.mask; t.target = x.target; t.trial = x.trial;
     } else {
-        const uint64_t id = c.first + i;
-        uint64_t st = c.seed ^ (id * 0xD6E8FEB86659FD93ULL);
-        const uint64_t r0 = splitmix(st), r1 = splitmix(st), r2 = splitmix(st);
-        t.inst = __umul64hi(r0, c.golden_ticks);
-        const uint64_t k = __umul64hi(r1, (uint64_t)c.n_struct);
-        uint64_t m = c.structures;
-        for (uint64_t j = 0; j < k; j++) m &= m - 1;
-        t.target = (uint32_t)__builtin_ctzll(m);
-        uint64_t b;
-        if (c.bits == (c.burst == 1 ? ~0ULL : ((2ULL << (64 - c.burst)) - 1))) {
-            b = __umul64hi(r2, (uint64_t)(65 - c.burst));   // every position
-        } else {                                             // the k-th eligible position
-            uint64_t mm = c.bits;
-            const uint64_t kk = __umul64hi(r2, (uint64_t)__popcll(mm));
-            for (uint64_t j = 0; j < kk; j++) mm &= mm - 1;
-            b = (uint64_t)__builtin_ctzll(mm);
-        }
-        t.mask = (c.burst == 64 ? ~0ULL : ((1ULL << c.burst) - 1)) << b;
-        t.trial = (uint32_t)id;
+        const SiteDraw d = draw_site(c.d, i, c.golden_ticks);
+        t.inst = d.when; t.mask = d.mask; t.target = d.target; t.trial = d.trial;
     }
     const TickMap m = tick_map_site(c.done, c.rec, c.n_att, c.golden_ninst, t.inst, t.target, t.mask, t.trial,
                                     c.literal);
-    fi_outcome o;
-    o.cls = 0; o.sub = 0; o.exit_code = 0; o.flags = 0; o.detail = 0; o.ninst = 0;
-    if (m.disp == 1) {   // the golden run itself
-        o.cls = FI_MASKED; o.sub = (uint8_t)c.gsub; o.exit_code = (uint8_t)c.gexit;
-        o.flags = 1; o.detail = c.gdetail; o.ninst = c.golden_ninst;
-    } else if (m.disp == 2) {
-        const TickRec A = c.rec[m.attempt];
-        o.cls = FI_ESCAPE; o.sub = FI_ESC_TIMING; o.exit_code = (uint8_t)m.reason;
-        o.flags = 1; o.detail = (uint32_t)A.pc; o.ninst = A.n;
-    }
     sites[i] = m.site;
     keys[i] = m.site.inst;
     perm[i] = (uint32_t)i;
     tsites[i] = t;
     disp[i] = (uint8_t)m.disp;
-    res[i] = o;
+    res[i] = tick_map_outcome(m, c.rec[m.attempt], c.gsub, c.gexit, c.gdetail, c.golden_ninst);
 }
 
 // After fi_forward_kernel (or in its place: fill = 1 writes the identity for

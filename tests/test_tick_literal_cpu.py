@@ -1,9 +1,9 @@
 """CPU checks of the literal tick contract (fi_set_tick_contract): the library
 exports its entry point, the command-line driver and FaultCampaign refuse bad
-values before a device is asked for, and the two statements of the literal
-map (fi_tick.cpp map_tick_site, fi_tick_map.h tick_map_site) agree on random
-attempt tables -- tools/tick_map_check.cpp in its literal mode, as a
-stand-alone host program under AddressSanitizer and UBSan."""
+values before a device is asked for, and the literal map (fi_tick_map.h
+tick_map_site) gives the recorded results on random attempt tables
+(tests/golden/tick_map.json) -- tools/tick_map_check.cpp in its literal mode,
+as a stand-alone host program under AddressSanitizer and UBSan."""
 import ctypes
 import os
 import subprocess
@@ -11,6 +11,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from test_tick_device_cpu import build_tick_map_check, recorded_tick_map
 
 
 def test_library_exports_tick_contract():
@@ -38,15 +39,16 @@ def test_fault_campaign_rejects_tick_contract_without_timing(tmp_path):
             FaultCampaign(str(tmp_path / "absent.elf"), **kw)
 
 
-def test_literal_maps_agree(tmp_path):
-    csrc = os.path.join(ROOT, "shrewd_amd", "csrc")
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    exe = str(tmp_path / "tick_map_check")
-    subprocess.run([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
-                    "-I" + os.path.join(ROOT, "include"), "-I" + csrc, "-I" + os.path.join(csrc, "hip"),
-                    os.path.join(ROOT, "tools", "tick_map_check.cpp"), os.path.join(csrc, "fi_tick.cpp"),
-                    "-o", exe], check=True, timeout=300)
-    for seed in ("1", "7"):
+def test_literal_tick_map_equals_recorded_host_map(tmp_path):
+    """As test_tick_device_cpu.py test_tick_map_equals_recorded_host_map, under
+    the literal contract: the recording is the former host statement's
+    (fi_tick.cpp's, with literal set), with which the packed-table map agreed
+    on the tick descriptors too.  The tool itself asserts that the only escapes
+    left are FI_TK_MACRO and sites past FI_SITE_TK_SKIP_MAX attempts and that
+    each kind of descriptor occurred."""
+    exe = build_tick_map_check(tmp_path)
+    for seed, want in recorded_tick_map("literal").items():
+        assert len(want) == 41 and want[-1].startswith("ok 160000 sites")
         r = subprocess.run([exe, seed, "literal"], capture_output=True, text=True, timeout=120)
-        assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout + r.stderr
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert r.stdout.splitlines() == want
