@@ -601,6 +601,34 @@ fi_status fi_run_trials(fi_engine *e, uint64_t first_trial, uint64_t n, fi_outco
 /* Explicit sites (parity tests, replay of a gem5-side site list). */
 fi_status fi_run_sites(fi_engine *e, const fi_site *sites, uint64_t n, fi_outcome *out, fi_histogram *hist);
 
+/* Output capture.  A trial's stdout (stderr) stream is every byte its run
+ * writes to fd 1 (fd 2) from process start (or the checkpoint restore point)
+ * to its end: what the serial gem5 run of that site leaves in its output
+ * file, whatever shortcut the engine took.
+ *  - A trial started from a golden snapshot has written the golden bytes
+ *    before that snapshot's output position.
+ *  - A trial the engine ends as "the golden run from here on" (dead at
+ *    injection by forwarding or by memory liveness, equal to a golden
+ *    snapshot -- masked or SDC) has its bytes so far followed by the golden
+ *    stream's from that position; its length is the golden length.
+ *  - Every other end (exit, m5_exit / m5_fail, crash, hang, detected,
+ *    escape) has the bytes written before it; a hang or crash ended by a loop
+ *    proof the same bytes as one that ran on (the proved loops make no
+ *    syscall).
+ * Epochs, the second pass with more private pages and the overflow pool
+ * neither lose nor duplicate bytes. */
+typedef struct { uint64_t out_len, err_len; } fi_stream_len;   /* full lengths, may exceed cap_bytes */
+/* fi_run_sites, and each trial's output streams besides: out_buf / err_buf hold n x cap_bytes bytes
+ * (trial i at i * cap_bytes: its first min(len, cap_bytes) bytes, zeros after); err_buf and lens may be
+ * NULL.  cap_bytes 1 .. 1 MiB.  Outcomes and histogram are those of fi_run_sites on the same sites.
+ * The capture buffers are grown on demand and kept like the other work buffers; a call's chunks are
+ * sized so that they take at most a quarter of the free device memory (and at most 256 MiB per stream:
+ * the pinned staging mirrors them). */
+#define FI_CAPTURE_MAX_BYTES (1u << 20)
+fi_status fi_run_sites_capture(fi_engine *e, const fi_site *sites, uint64_t n, uint32_t cap_bytes,
+                               fi_outcome *out, fi_histogram *hist, uint8_t *out_buf, uint8_t *err_buf,
+                               fi_stream_len *lens);
+
 /* Device-resident variant for multi-GPU drivers: d_out (n fi_outcome) and
  * d_hist (one fi_histogram, accumulated) are device pointers; stream is a
  * hipStream_t (NULL = engine stream).  Asynchronous: nothing is copied back. */

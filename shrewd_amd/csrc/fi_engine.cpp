@@ -25,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "fi_capture.h"
 #include "fi_checkpoint.h"
 #include "fi_debug.h"
 #include "fi_site_draw.h"
@@ -66,6 +67,10 @@ hipError_t launch_redo_gather(const fi_site *sites, const uint32_t *idx, uint64_
                               uint32_t *perm, hipStream_t st);
 hipError_t launch_redo_scatter(const uint32_t *idx, uint64_t n, const fi_outcome *rout, fi_outcome *out,
                                hipStream_t st);
+hipError_t launch_capture_init(uint8_t *rows, uint64_t n, uint32_t stride, uint32_t cap, const uint8_t *gold,
+                               uint64_t glen, hipStream_t st);
+hipError_t launch_capture_finish(uint8_t *rows, uint64_t n, uint32_t stride, uint32_t cap, const fi_stream_len *lens,
+                                 uint32_t err, hipStream_t st);
 hipError_t launch_surv_keys(const LaneSave *save, const uint32_t *list, const uint32_t *cnt, uint64_t cap,
                             uint64_t text_lo, uint64_t *keys, uint32_t *vals, uint32_t *n_odd, uint32_t solo,
                             uint64_t golden_ninst, uint32_t nb, const LoopEst *loops, uint32_t n_loops,
@@ -307,6 +312,20 @@ struct fi_engine {
     hipEvent_t ev_stage[2] = {nullptr, nullptr};
     fi_site *d_redo_sites = nullptr;
     fi_outcome *d_redo_out = nullptr;
+    // output capture (fi_run_sites_capture): on only while such a call runs (bytes != 0);
+    // its buffers are grown on demand and kept until free_work.  Rows alternate between the two chunks in flight like the site and outcome
+    // buffers; the pinned staging mirrors them.
+    struct Capture {
+        uint32_t bytes = 0, stride = 0;   // bytes kept per stream; device row pitch (bytes rounded up to 16)
+        uint64_t rows = 0;                // trials per chunk
+        uint64_t held_b = 0, held_rows = 0;   // what is allocated: bytes per row buffer, entries per length buffer
+        uint8_t *d_out[2] = {nullptr, nullptr}, *d_err[2] = {nullptr, nullptr};
+        fi_stream_len *d_len[2] = {nullptr, nullptr};
+        uint8_t *h_out[2] = {nullptr, nullptr}, *h_err[2] = {nullptr, nullptr};
+        fi_stream_len *h_len[2] = {nullptr, nullptr};
+        uint8_t *out = nullptr, *err = nullptr;   // the caller's arrays (err, lens may be NULL)
+        fi_stream_len *lens = nullptr;
+    } cx;
 };
 
 static fi_status fail(fi_engine *e, fi_status code, const char *fmt, ...) {
@@ -427,7 +446,17 @@ fi_status fi_create(const fi_config *cfg, fi_engine **out) {
     return FI_OK;
 }
 
+static void free_capture(fi_engine *e) {
+    for (int i = 0; i < 2; i++) {
+        dfree(e->cx.d_out[i]); dfree(e->cx.d_err[i]); dfree(e->cx.d_len[i]);
+        for (void **h : {(void **)&e->cx.h_out[i], (void **)&e->cx.h_err[i], (void **)&e->cx.h_len[i]})
+            if (*h) { (void)hipHostFree(*h); *h = nullptr; }
+    }
+    e->cx = fi_engine::Capture{};
+}
+
 static void free_work(fi_engine *e) {
+    free_capture(e);
     dfree(e->d_sites); dfree(e->d_sites_alt); dfree(e->d_out_alt); dfree(e->d_keys); dfree(e->d_keys2); dfree(e->d_perm); dfree(e->d_perm2);
     dfree(e->d_tmp); dfree(e->d_out); dfree(e->d_hist); dfree(e->d_stats); dfree(e->d_wave_dbg); dfree(e->d_fregs);
     dfree(e->d_inpos);
@@ -1604,8 +1633,10 @@ static std::pair<hipEvent_t, hipEvent_t> &timer_slot(fi_engine *e, uint32_t kind
 // AtomicSimpleCPU's, so a curTick read escapes (DevCtx::clk_esc).
 // disp (device-mapped chunks, else NULL): trials with disp[i] != 0 are parked --
 // dead at injection, so the trial kernels end them at once as the golden run.
+// cslot (a capture call's chunks, else -1): the trials' output goes to that
+// pair of capture buffers, trial i of sites to row cidx[i] (NULL: row i).
 static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *d_out, uint32_t P, hipStream_t st,
-                          bool tick, const uint8_t *disp = nullptr) {
+                          bool tick, const uint8_t *disp = nullptr, int cslot = -1, const uint32_t *cidx = nullptr) {
     int end_bit = 64 - __builtin_clzll(std::max<uint64_t>(e->golden.ninst, 1));
     // (a dead site ends at injection: an early exit, so not with FI_CFG_NO_EARLY_EXIT)
     const bool fwd = e->fw_ok && !(e->cfg.flags & (FI_CFG_NO_FORWARD | FI_CFG_NO_EARLY_EXIT));
@@ -1634,6 +1665,11 @@ static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *
     c.save = e->d_save;
     c.priv_pages = P;
     c.clk_esc = tick ? 1u : 0u;
+    if (cslot >= 0) {
+        c.cap_out = e->cx.d_out[cslot]; c.cap_err = e->cx.d_err[cslot]; c.cap_len = e->cx.d_len[cslot];
+        c.cap_idx = cidx;
+        c.cap_bytes = e->cx.bytes; c.cap_stride = e->cx.stride;
+    }
     if (P != e->cfg.private_pages) c.ov_blocks = 0;   // the second pass has its own P' (chunk_end)
     if (c.ov_blocks) HIPCHK(hipMemsetAsync(e->d_ov_next, 0, 4, st));
     HIPCHK(hipMemsetAsync(e->d_cnt, 0, 16 * 4, st));
@@ -1757,10 +1793,18 @@ struct Chunk {
     const uint8_t *disp = nullptr;
     const fi_outcome *res = nullptr;
     uint32_t slot = 0;                // redo list / count / event pair
+    uint64_t off = 0;                 // a capture call: the chunk's first trial (row of the caller's arrays)
+    bool capture = false;             //   and its output goes to the capture buffers of `slot`
 };
 
 static fi_status chunk_begin(fi_engine *e, const Chunk &ch, hipStream_t st) {
-    fi_status s = run_pass(e, ch.sites, ch.k, ch.out, e->cfg.private_pages, st, ch.tick, ch.disp);
+    if (ch.capture) {   // every row = the golden stream (the prefix and golden-suffix rules)
+        const fi_engine::Capture &x = e->cx;
+        HIPCHK(launch_capture_init(x.d_out[ch.slot], ch.k, x.stride, x.bytes, e->d_gout, e->gout.size(), st));
+        HIPCHK(launch_capture_init(x.d_err[ch.slot], ch.k, x.stride, x.bytes, e->d_gerr, e->gerr.size(), st));
+    }
+    fi_status s = run_pass(e, ch.sites, ch.k, ch.out, e->cfg.private_pages, st, ch.tick, ch.disp,
+                           ch.capture ? (int)ch.slot : -1);
     if (s) return s;
     if (!(e->cfg.flags & FI_CFG_NO_REDO)) {
         uint32_t *cnt = e->d_redo_cnt + ch.slot;
@@ -1785,7 +1829,9 @@ static fi_status chunk_end(fi_engine *e, const Chunk &ch, fi_histogram *d_hist, 
             for (uint64_t d = 0; d < nr; d += B) {
                 const uint64_t b = std::min(B, nr - d);
                 HIPCHK(launch_redo_gather(ch.sites, idx + d, b, e->d_redo_sites, e->d_keys, e->d_perm, st));
-                fi_status s = run_pass(e, e->d_redo_sites, b, e->d_redo_out, (uint32_t)P2, st, ch.tick);
+                // (capture: the same deterministic run, only longer, into the trial's own row again)
+                fi_status s = run_pass(e, e->d_redo_sites, b, e->d_redo_out, (uint32_t)P2, st, ch.tick, nullptr,
+                                       ch.capture ? (int)ch.slot : -1, idx + d);
                 if (s) return s;
                 HIPCHK(launch_redo_scatter(idx + d, b, e->d_redo_out, ch.out, st));
             }
@@ -1797,6 +1843,18 @@ static fi_status chunk_end(fi_engine *e, const Chunk &ch, fi_histogram *d_hist, 
     if (ch.host_out) {
         if (!e->h_stage[ch.slot]) HIPCHK(hipHostMalloc(&e->h_stage[ch.slot], e->cap * sizeof(fi_outcome)));
         HIPCHK(hipMemcpyAsync(e->h_stage[ch.slot], ch.out, ch.k * sizeof(fi_outcome), hipMemcpyDeviceToHost, st));
+        if (ch.capture) {   // zeros past each stream's end, then rows and lengths to their staging
+            const fi_engine::Capture &x = e->cx;
+            const uint32_t sl = ch.slot;
+            HIPCHK(launch_capture_finish(x.d_out[sl], ch.k, x.stride, x.bytes, x.d_len[sl], 0u, st));
+            HIPCHK(hipMemcpyAsync(x.h_out[sl], x.d_out[sl], ch.k * x.stride, hipMemcpyDeviceToHost, st));
+            if (x.err) {
+                HIPCHK(launch_capture_finish(x.d_err[sl], ch.k, x.stride, x.bytes, x.d_len[sl], 1u, st));
+                HIPCHK(hipMemcpyAsync(x.h_err[sl], x.d_err[sl], ch.k * x.stride, hipMemcpyDeviceToHost, st));
+            }
+            if (x.lens)
+                HIPCHK(hipMemcpyAsync(x.h_len[sl], x.d_len[sl], ch.k * sizeof(fi_stream_len), hipMemcpyDeviceToHost, st));
+        }
         HIPCHK(hipEventRecord(e->ev_stage[ch.slot], st));
     }
     return FI_OK;
@@ -1807,6 +1865,12 @@ static fi_status chunk_deliver(fi_engine *e, Chunk &ch) {
     if (!ch.host_out || !ch.k) return FI_OK;
     HIPCHK(hipEventSynchronize(e->ev_stage[ch.slot]));
     memcpy(ch.host_out, e->h_stage[ch.slot], ch.k * sizeof(fi_outcome));
+    if (ch.capture) {
+        const fi_engine::Capture &x = e->cx;
+        capture_rows(x.out + ch.off * x.bytes, x.h_out[ch.slot], ch.k, x.bytes, x.stride);
+        if (x.err) capture_rows(x.err + ch.off * x.bytes, x.h_err[ch.slot], ch.k, x.bytes, x.stride);
+        if (x.lens) memcpy(x.lens + ch.off, x.h_len[ch.slot], ch.k * sizeof(fi_stream_len));
+    }
     ch.k = 0;
     return FI_OK;
 }
@@ -1856,6 +1920,7 @@ static fi_status run_chunks(fi_engine *e, uint64_t first, const SiteSource &src,
         jit_install(e, st, false);   // the translated kernels, once their build has landed
         Chunk ch;
         ch.k = std::min<uint64_t>({n - done, e->cap, e->jit ? kJitWindowChunk : e->cap});
+        if (e->cx.bytes) { ch.k = std::min(ch.k, e->cx.rows); ch.capture = true; ch.off = done; }
         ch.slot = i & 1;
         ch.sites = ch.slot ? e->d_sites_alt : e->d_sites;
         ch.out = out_dev ? out_dev + done : ch.slot ? e->d_out_alt : e->d_out;
@@ -1950,6 +2015,61 @@ fi_status fi_run_sites(fi_engine *e, const fi_site *sites, uint64_t n, fi_outcom
     if (!sites && n) return FI_E_ARG;
     // (no sites: an empty sampled run)
     return run_common(e, 0, SiteSource{sites, nullptr, !sites, false}, n, out, hist);
+}
+
+// Output capture (the sizing and the staging copy: fi_capture.h).
+// The rows and their pinned mirror are grown on demand like the other work
+// buffers and released with them (free_work).
+static fi_status ensure_capture(fi_engine *e, uint64_t rows, uint32_t stride) {
+    fi_engine::Capture &x = e->cx;
+    if (rows * stride <= x.held_b && rows <= x.held_rows) return FI_OK;
+    const uint64_t b = std::max(x.held_b, rows * stride), r = std::max(x.held_rows, rows);
+    free_capture(e);
+    for (int i = 0; i < 2; i++) {
+        HIPCHK(hipMalloc(&x.d_out[i], b));
+        HIPCHK(hipMalloc(&x.d_err[i], b));
+        HIPCHK(hipMalloc(&x.d_len[i], r * sizeof(fi_stream_len)));
+        HIPCHK(hipHostMalloc(&x.h_out[i], b));
+        HIPCHK(hipHostMalloc(&x.h_err[i], b));
+        HIPCHK(hipHostMalloc(&x.h_len[i], r * sizeof(fi_stream_len)));
+    }
+    x.held_b = b; x.held_rows = r;
+    return FI_OK;
+}
+
+fi_status fi_run_sites_capture(fi_engine *e, const fi_site *sites, uint64_t n, uint32_t cap_bytes, fi_outcome *out,
+                               fi_histogram *hist, uint8_t *out_buf, uint8_t *err_buf, fi_stream_len *lens) {
+    if (!e) return FI_E_ARG;
+    if (const char *why = capture_args_error(sites, n, cap_bytes, out_buf))
+        return fail(e, FI_E_ARG, "fi_run_sites_capture: %s", why);
+    if (!e->have_golden) return fail(e, FI_E_STATE, "golden run required");
+    if (n == 0) return FI_OK;
+    HIPCHK(hipSetDevice(e->dev));
+    const uint32_t stride = capture_stride(cap_bytes);
+    // the work buffers first, at run_common's own size (growing them frees and reallocates everything, so
+    // not once the rows exist), then the rows within a quarter of what is free
+    const uint64_t want = std::min<uint64_t>(n, e->cfg.max_trials_per_launch);
+    fi_status s = ensure_work(e, want);
+    if (s) return s;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    // (what an earlier call left is counted as free: it is reused or replaced)
+    const uint64_t held = 4 * e->cx.held_b + 2 * e->cx.held_rows * sizeof(fi_stream_len);
+    const uint64_t rows = capture_rows_for(want, ((uint64_t)free_b + held) / 4, stride);
+    std::vector<fi_outcome> own;   // the rows travel with the outcomes' staging: the run has a host array
+    if (!out) { own.resize(n); out = own.data(); }
+    s = ensure_capture(e, rows, stride);
+    if (!s) {
+        fi_engine::Capture &x = e->cx;
+        x.rows = rows; x.stride = stride;
+        x.out = out_buf; x.err = err_buf; x.lens = lens;
+        x.bytes = cap_bytes;   // capture is on
+        s = run_common(e, 0, SiteSource{sites, nullptr, false, false}, n, out, hist);
+        if (s) (void)hipStreamSynchronize(e->stream);   // nothing in flight still writes the caller's arrays
+        x.bytes = 0;           // ... and off again for every other entry point
+        x.out = x.err = nullptr; x.lens = nullptr;
+    }
+    return s;
 }
 
 // ---------------------------------------------------- tick-domain injection

@@ -269,6 +269,14 @@ struct DevCtx {
                                      // [32..39] FI_PROF phase cycles
                                      // [40 + 4k + {0,1,2,3}] fetch B, data B, pages, device insts of kernel k
                                      // (0 the 64-lane kernel, 1 solo, 2 solo-odd)
+    // output capture (fi_run_sites_capture; cap_bytes 0 = off): each trial of the chunk
+    // owns one row of cap_stride bytes in cap_out / cap_err, preset to the golden streams
+    // (fi_capture_init_kernel); write() stores its bytes over them and the lane that ends a trial its
+    // lengths.  (Last, so that every field above keeps its offset in the kernarg segment.)
+    uint8_t *cap_out, *cap_err;      // [trials of the chunk][cap_stride]
+    fi_stream_len *cap_len;          // [trials of the chunk]
+    const uint32_t *cap_idx;         // index into sites -> row (the second pass's gathered subset); NULL = the same
+    uint32_t cap_bytes, cap_stride;  // bytes kept per stream; row pitch (cap_bytes rounded up to 16)
 };
 
 // Tick-domain sites mapped on the device (fi_tick_map.h, fi_tick_map_kernel):

@@ -391,6 +391,54 @@ __global__ void fi_redo_scatter_kernel(const uint32_t *idx, uint64_t n, const fi
     if (j < n) out[idx[j]] = rout[j];
 }
 
+// Output capture (fi_run_sites_capture).  Rows of `stride`
+// bytes (a multiple of 16), one per trial of the chunk and stream; one thread
+// per 16-byte piece of a row, so a wave stores 1 KiB contiguously.
+// Before the pass: every row = the first cap bytes of the golden stream,
+// zeros after -- a golden byte sits at the same offset in a trial's stream
+// whether the trial started after it (snapshot start) or ended before it
+// (the golden-suffix ends), so neither case copies a byte later.
+__global__ void __launch_bounds__(256) fi_capture_init_kernel(uint8_t *rows, uint64_t n, uint32_t stride, uint32_t cap,
+                                                              const uint8_t *gold, uint64_t glen) {
+    const uint32_t per = stride / 16;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * per) return;
+    const uint64_t o = (i % per) * 16;
+    const uint64_t lim = glen < cap ? glen : cap;   // golden bytes a row holds
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (o + 16 <= lim) {
+        v = *(const uint4 *)(gold + o);   // (gold is the start of an allocation: 16-byte aligned)
+    } else if (o < lim) {
+        uint32_t wds[4] = {0, 0, 0, 0};
+        for (uint64_t b = o; b < lim; b++) wds[(b - o) >> 2] |= (uint32_t)gold[b] << (8 * ((b - o) & 3));
+        v = make_uint4(wds[0], wds[1], wds[2], wds[3]);
+    }
+    *(uint4 *)(rows + i * 16) = v;
+}
+// After the pass and its second pass: zeros from min(len, cap) to the end of
+// each row (the golden bytes a shorter trial never reached), so that the
+// returned bytes are a function of the site alone.  err = 0: stdout rows.
+__global__ void __launch_bounds__(256) fi_capture_finish_kernel(uint8_t *rows, uint64_t n, uint32_t stride, uint32_t cap,
+                                                                const fi_stream_len *lens, uint32_t err) {
+    const uint32_t per = stride / 16;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * per) return;
+    const uint64_t o = (i % per) * 16;
+    const fi_stream_len sl = lens[i / per];
+    uint64_t len = err ? sl.err_len : sl.out_len;
+    if (len > cap) len = cap;
+    if (o + 16 <= len) return;
+    uint4 *p = (uint4 *)(rows + i * 16);
+    uint4 v = make_uint4(0, 0, 0, 0);
+    if (o < len) {
+        v = *p;
+        uint32_t wds[4] = {v.x, v.y, v.z, v.w};
+        for (uint32_t b = (uint32_t)(len - o); b < 16; b++) wds[b >> 2] &= ~(0xFFu << (8 * (b & 3)));
+        v = make_uint4(wds[0], wds[1], wds[2], wds[3]);
+    }
+    *p = v;
+}
+
 __global__ void fi_hist_stats_kernel(const unsigned long long *stats, fi_histogram *h) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         h->fetch_bytes += stats[0];
@@ -469,6 +517,18 @@ hipError_t launch_redo_gather(const fi_site *sites, const uint32_t *idx, uint64_
 hipError_t launch_redo_scatter(const uint32_t *idx, uint64_t n, const fi_outcome *rout, fi_outcome *out,
                                hipStream_t st) {
     hipLaunchKernelGGL(fi_redo_scatter_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, idx, n, rout, out);
+    return hipGetLastError();
+}
+hipError_t launch_capture_init(uint8_t *rows, uint64_t n, uint32_t stride, uint32_t cap, const uint8_t *gold,
+                               uint64_t glen, hipStream_t st) {
+    hipLaunchKernelGGL(fi_capture_init_kernel, dim3(nblk(n * (stride / 16), 256)), dim3(256), 0, st, rows, n, stride,
+                       cap, gold, glen);
+    return hipGetLastError();
+}
+hipError_t launch_capture_finish(uint8_t *rows, uint64_t n, uint32_t stride, uint32_t cap, const fi_stream_len *lens,
+                                 uint32_t err, hipStream_t st) {
+    hipLaunchKernelGGL(fi_capture_finish_kernel, dim3(nblk(n * (stride / 16), 256)), dim3(256), 0, st, rows, n, stride,
+                       cap, lens, err);
     return hipGetLastError();
 }
 hipError_t launch_surv_keys(const LaneSave *save, const uint32_t *list, const uint32_t *cnt, uint64_t cap,

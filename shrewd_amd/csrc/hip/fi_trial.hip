@@ -1022,6 +1022,29 @@ __device__ __noinline__ bool mem_dead(const KCtx *c, uint64_t addr, uint64_t mas
     return true;
 }
 
+// Output capture: the stream lengths of a trial that has just
+// ended, stored by the lane that stores its outcome.  res_ninst is the
+// record's numInst, ninst the lane's own.  The four ends that stand for "the
+// golden run from here on" (dead at injection by forwarding, the two
+// memory-liveness ends, the early exit at a snapshot) are those that put the
+// golden numInst into the record where finish() had put the lane's own:
+// their streams run on to the golden lengths.  This rests on two invariants
+// of trial_body: only finish() and those four places write res.ninst, and
+// nothing advances a lane's numInst once finish() has run (the loop proofs
+// add their skipped instructions before they call it).  Were both counts
+// equal at such an end, no golden instruction would be left to write a byte:
+// the lane's positions, equal to the golden run's there, are the golden
+// lengths.
+__device__ __noinline__ void capture_lens(KCtx *c, uint32_t sidx, uint64_t res_ninst, uint64_t ninst, uint64_t out_pos,
+                                          uint64_t err_pos) {
+    if (!c->cap_bytes || c->record) return;
+    const bool gold = res_ninst != ninst;
+    fi_stream_len sl;
+    sl.out_len = gold ? c->gout_len : out_pos;
+    sl.err_len = gold ? c->gerr_len : err_pos;
+    c->cap_len[c->cap_idx ? c->cap_idx[sidx] : sidx] = sl;
+}
+
 #define RREG(r) R[(uint32_t)(r) * kNL + lane]
 
 // The syscall path of one lane: EmuLinux::syscall (se_workload.cc:95-106)
@@ -1050,6 +1073,12 @@ __device__ __noinline__ bool do_syscall(KCtx *c, WaveMem w, Lane &L, LaneMem &m,
         uint64_t cur_vpn = kNone;
         const uint8_t *pg = nullptr;
         if (c->record) rec_mem(c, buf, n, L.ninst | kMemEvProxy, 1u);
+        // output capture: the trial's row, preset to the golden stream
+        uint8_t *row = nullptr;
+        if (c->cap_bytes && !c->record) {
+            const uint32_t si = c->perm[slot];
+            row = (fd == 1 ? c->cap_out : c->cap_err) + (uint64_t)(c->cap_idx ? c->cap_idx[si] : si) * c->cap_stride;
+        }
         for (uint64_t i = 0; i < n; i++) {
             const uint64_t a = buf + i;
             if ((a >> 12) != cur_vpn) { cur_vpn = a >> 12; pg = page_of(lookup(c, w, m, slot, cur_vpn)); }
@@ -1060,6 +1089,7 @@ __device__ __noinline__ bool do_syscall(KCtx *c, WaveMem w, Lane &L, LaneMem &m,
             } else if (p >= glen || gold[p] != ch) {
                 L.out_bad = true;
             }
+            if (row && p < c->cap_bytes) row[p] = ch;
         }
         pos += n;
     };
@@ -5466,6 +5496,10 @@ __device__ __forceinline__ void trial_body() {
     }
 
     if (live && !suspended) CX->out[CX->record ? 0 : sidx] = L.res;
+    // output capture: the ended trial's stream lengths (out of line, and the
+    // launch context through the opaque pointer in the solo kernel too: nothing
+    // of it is held in registers across the loop)
+    if (live && !suspended) capture_lens(opq(kc), sidx, L.res.ninst, L.ninst, L.out_pos, L.err_pos);
     if (CX->record && live) {
         CX->stats[3] = L.ncyc;
         CX->stats[4] = L.out_pos;

@@ -41,6 +41,25 @@ SITE_DT = np.dtype([("inst", "<u8"), ("mask", "<u8"), ("addr", "<u8"), ("target"
 HIST_DT = np.dtype([("counts", "<u8", (N_STRUCT, 64, 6)), ("crash_sub", "<u8", (16,)), ("escape_sub", "<u8", (8,)),
                     ("trials", "<u8"), ("guest_insts", "<u8"), ("fetch_bytes", "<u8"), ("data_bytes", "<u8"),
                     ("cow_pages", "<u8"), ("device_insts", "<u8")])
+STREAM_LEN_DT = np.dtype([("out_len", "<u8"), ("err_len", "<u8")])
+
+
+class Capture:
+    """What the trials of a capture run printed (Engine.run_sites_capture):
+    out / err are uint8 [n, cap_bytes] arrays (err None without stderr), row i
+    the first min(len, cap_bytes) bytes of trial i's stream and zeros after;
+    out_len / err_len the streams' full lengths, which may exceed cap_bytes."""
+
+    def __init__(self, cap_bytes: int, out: np.ndarray, err, out_len: np.ndarray, err_len: np.ndarray):
+        self.cap_bytes, self.out, self.err, self.out_len, self.err_len = cap_bytes, out, err, out_len, err_len
+
+    def stdout(self, i: int) -> bytes:
+        return self.out[i, :min(int(self.out_len[i]), self.cap_bytes)].tobytes()
+
+    def stderr(self, i: int) -> bytes:
+        if self.err is None:
+            raise ValueError("this capture ran with stderr=False")
+        return self.err[i, :min(int(self.err_len[i]), self.cap_bytes)].tobytes()
 
 ABI_NAMES = {"zero": 0, "ra": 1, "sp": 2, "gp": 3, "tp": 4, "t0": 5, "t1": 6, "t2": 7, "s0": 8, "fp": 8, "s1": 9,
              **{f"a{i}": 10 + i for i in range(8)}, **{f"s{i}": 16 + i for i in range(2, 12)},
@@ -288,6 +307,7 @@ def lib():
         L.fi_sample_sites.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
         L.fi_run_trials.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
         L.fi_run_sites.argtypes = [vp, vp, C.c_uint64, vp, vp]
+        L.fi_run_sites_capture.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp]
         L.fi_run_trials_device.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp]
         L.fi_sync.argtypes = [vp]
         L.fi_last_kernel_ms.restype = C.c_double
@@ -573,6 +593,24 @@ class Engine:
         self._chk(self.L.fi_run_sites(self.h, sites.ctypes.data, len(sites), out.ctypes.data, hist.ctypes.data),
                   "fi_run_sites")
         return out, hist[0]
+
+    def run_sites_capture(self, sites: np.ndarray, cap_bytes: int = 4096, stderr: bool = True):
+        """run_sites, and what each trial printed besides -> (outcomes, hist,
+        Capture): the first cap_bytes of every trial's stdout (and stderr)
+        stream and the streams' full lengths (fi_engine.h, output capture)."""
+        sites = np.ascontiguousarray(sites, SITE_DT)
+        n = len(sites)
+        out = np.zeros(n, OUTCOME_DT)
+        hist = np.zeros(1, HIST_DT)
+        rows = max(int(cap_bytes), 0)
+        obuf = np.zeros((n, rows), np.uint8)
+        ebuf = np.zeros((n, rows), np.uint8) if stderr else None
+        lens = np.zeros(n, STREAM_LEN_DT)
+        self._chk(self.L.fi_run_sites_capture(self.h, sites.ctypes.data, n, cap_bytes, out.ctypes.data,
+                                              hist.ctypes.data, obuf.ctypes.data if n else None,
+                                              ebuf.ctypes.data if stderr and n else None, lens.ctypes.data),
+                  "fi_run_sites_capture")
+        return out, hist[0], Capture(cap_bytes, obuf, ebuf, lens["out_len"].copy(), lens["err_len"].copy())
 
     def run_trials_device(self, first: int, n: int, d_out: int, d_hist: int, stream: int | None = None):
         self._chk(self.L.fi_run_trials_device(self.h, first, n, d_out, d_hist, stream), "fi_run_trials_device")
@@ -885,6 +923,23 @@ class FaultCampaign:
         if self.output:
             np.save(self.output if world == 1 else f"{self.output}.rank{rank}", self.outcomes)
         return self.outcomes
+
+    def outputs(self, trials, max_bytes: int = 4096) -> dict:
+        """What the given trials printed: {trial: (outcome, stdout, stderr)},
+        the streams cut to max_bytes.  trials are campaign trial ids -- for
+        the SDCs of the last run(), self.first + the indices with cls == 1.
+        Their sites are drawn again with the campaign's sampler (one draw over
+        the id range, then a select) and run once more with output capture."""
+        if self.cpu_type == "timing":
+            raise ValueError("outputs(): output capture runs numInst sites; a cpu_type='timing' campaign's "
+                             "tick sites are not captured")
+        ids = np.asarray(list(trials), np.int64)
+        if ids.size == 0:
+            return {}
+        lo = int(ids.min())
+        sites = self.engine.sample(lo, int(ids.max()) - lo + 1)[ids - lo]
+        out, _, cap = self.engine.run_sites_capture(sites, cap_bytes=max_bytes)
+        return {int(t): (out[i], cap.stdout(i), cap.stderr(i)) for i, t in enumerate(ids)}
 
     def histogram(self):
         return self._hist

@@ -24,6 +24,12 @@ run_tick_sites of an engine with cpu_type "timing"): each trial runs on
 TimingSimpleCPU with the fault at its tick (--cpu timing --tick); trials the
 engine reports as FI_ESC_TIMING are skipped, and --golden-ticks (the engine's
 fi_tick_info.golden_ticks) is compared with the fault-free run's final tick.
+
+--stdouts FILE.npz (optional): the arrays of a capture run over the same sites,
+  out, _, cap = Engine.run_sites_capture(sites)
+  np.savez("stdouts.npz", out=cap.out, out_len=cap.out_len)
+Each trial's gem5 `stdout` file must then also equal the engine's captured
+stdout; trials whose full length exceeds the capture's cap_bytes are skipped.
 """
 import argparse
 import json
@@ -101,6 +107,17 @@ def classify(rec, golden):
     return 2, 0, rec["rc"] & 0xFF
 
 
+def stdout_check(gem5_stdout: bytes, row, out_len: int):
+    """A trial's gem5 stdout file against the engine's captured stdout: row =
+    the trial's cap_bytes captured bytes, out_len = the stream's full length.
+    -> None when the stream did not fit the cap (skipped), else whether the
+    two are equal."""
+    row = bytes(bytearray(row))
+    if out_len > len(row):
+        return None
+    return gem5_stdout == row[:out_len]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gem5", required=True)
@@ -114,6 +131,8 @@ def main():
     ap.add_argument("--max-insts", type=int, default=0, help="0: 2 x golden numInst + 1000 (engine default)")
     ap.add_argument("--golden-ticks", type=int, default=0,
                     help="tick sites: the engine's golden run length in ticks, checked against gem5's")
+    ap.add_argument("--stdouts", default="",
+                    help="npz of a capture run over the same sites (out, out_len): compare each trial's stdout too")
     args = ap.parse_args()
     raw = np.load(args.sites)
     args.tick_sites = "tick" in (raw.dtype.names or ())
@@ -126,16 +145,29 @@ def main():
             and not (args.tick_sites and eng[i]["cls"] == 5 and eng[i]["sub"] == 7)]
     with ThreadPoolExecutor(args.jobs) as ex:
         recs = list(ex.map(lambda i: run_one(args, sites[i], str(i)), keep))
+    cap = np.load(args.stdouts) if args.stdouts else None
     bad = []
+    n_stdout = 0
     for i, rec in zip(keep, recs):
         cls, sub, code = classify(rec, golden)
         e = eng[i]
         want = (int(e["cls"]), int(e["sub"]) if e["cls"] == 2 else 0, int(e["exit_code"]))
         got = (cls, sub if cls == 2 else 0, code)
-        if want != got or (rec["ninst"] >= 0 and rec["ninst"] != int(e["ninst"])):
-            bad.append({"trial": int(sites[i]["trial"]), "engine": want, "gem5": got,
-                        "engine_ninst": int(e["ninst"]), "gem5_ninst": rec["ninst"]})
+        same = None
+        if cap is not None:
+            same = stdout_check(rec["stdout"], cap["out"][i], int(cap["out_len"][i]))
+            n_stdout += same is not None
+        # one record per mismatching trial, whatever differs
+        if want != got or (rec["ninst"] >= 0 and rec["ninst"] != int(e["ninst"])) or same is False:
+            b = {"trial": int(sites[i]["trial"]), "engine": want, "gem5": got,
+                 "engine_ninst": int(e["ninst"]), "gem5_ninst": rec["ninst"]}
+            if same is False:
+                b["engine_stdout"] = bytes(bytearray(cap["out"][i][:int(cap["out_len"][i])])).hex()
+                b["gem5_stdout"] = rec["stdout"].hex()
+            bad.append(b)
     res = {"checked": len(keep), "mismatches": len(bad), "first": bad[:20]}
+    if cap is not None:
+        res["stdout_checked"] = n_stdout
     if args.tick_sites and args.golden_ticks:
         res["golden_ticks"] = {"engine": args.golden_ticks, "gem5": golden.get("tick", -1)}
         if golden.get("tick", -1) != args.golden_ticks:
