@@ -240,6 +240,15 @@ typedef struct {
  * flipped bound or pointer).  This flag drops the loop term (A/B; the order
  * never changes an outcome). */
 #define FI_CFG_NO_LOOP_ORDER 65536u
+/* The clean solo body issues a stepping loop's next load one pass ahead: in a
+ * store-free block that branches to itself, a load at an induction register
+ * plus a constant also loads the address of its next pass into a held
+ * register, tagged with that address, and takes its value from there when
+ * the tag matches (fi_translate.cpp).  This flag generates the
+ * text without it (A/B and parity checks; outcomes are identical).  The
+ * code-object caches are keyed by the generated text, so neither variant is
+ * ever loaded for the other. */
+#define FI_CFG_NO_LOAD_AHEAD 131072u
 
 typedef struct {
     uint64_t ninst, ncycles;

@@ -79,7 +79,8 @@ hipError_t launch_odd_split(const uint32_t *cnt, const uint32_t *n_odd, uint32_t
                             hipStream_t st);
 std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, const std::vector<uint32_t> &trace,
                              const std::vector<uint64_t> &extra_pcs, std::vector<uint32_t> &leaders_out,
-                             uint32_t &n_insts, bool odd_streams, std::vector<LoopEst> *loops_out = nullptr);
+                             uint32_t &n_insts, bool odd_streams, std::vector<LoopEst> *loops_out = nullptr,
+                             bool load_ahead = true);
 std::vector<fi_issue_op> issue_ops_from_trace(const std::vector<PreInst> &pre, const std::vector<uint32_t> &trace);
 std::string jit_compile(const std::string &body, const char *arch, std::vector<char> &code, bool &cached, int part,
                         bool use_cache);
@@ -1406,11 +1407,12 @@ fi_status fi_golden_run(fi_engine *e, fi_golden_info *out) {
         std::vector<uint32_t> leaders;
         std::vector<LoopEst> loops;
         uint32_t n_tx = 0;
-        std::string body = translate_blocks(pre, e->text_lo, trace, pcs, leaders, n_tx, true, &loops);
+        const bool ahead = !(e->cfg.flags & FI_CFG_NO_LOAD_AHEAD);   // (part of the text, which keys the code-object caches)
+        std::string body = translate_blocks(pre, e->text_lo, trace, pcs, leaders, n_tx, true, &loops, ahead);
         if (n_tx > 24000) {   // the odd-pc streams make it too large: without them
             leaders.clear();
             loops.clear();
-            body = translate_blocks(pre, e->text_lo, trace, pcs, leaders, n_tx, false, &loops);
+            body = translate_blocks(pre, e->text_lo, trace, pcs, leaders, n_tx, false, &loops, ahead);
         }
         if (!loops.empty() && !(e->cfg.flags & FI_CFG_NO_LOOP_ORDER)) {
             HIPCHK(hipMalloc(&e->d_loops, loops.size() * sizeof(LoopEst)));
@@ -2418,12 +2420,18 @@ fi_status fi_debug_loop_est(const void *pre, uint64_t n_pre, uint64_t text_lo, c
 
 fi_status fi_debug_translate(const void *pre, uint64_t n_pre, uint64_t text_lo, const uint32_t *trace,
                              uint64_t n_trace, char *out, uint64_t cap, uint64_t *len) {
+    return fi_debug_translate_flags(pre, n_pre, text_lo, trace, n_trace, 0, out, cap, len);
+}
+
+fi_status fi_debug_translate_flags(const void *pre, uint64_t n_pre, uint64_t text_lo, const uint32_t *trace,
+                                   uint64_t n_trace, uint32_t flags, char *out, uint64_t cap, uint64_t *len) {
     if (!pre || !trace) return FI_E_ARG;
     std::vector<PreInst> p((const PreInst *)pre, (const PreInst *)pre + n_pre);
     std::vector<uint32_t> t(trace, trace + n_trace);
     std::vector<uint32_t> leaders;
     uint32_t n_tx = 0;
-    const std::string body = translate_blocks(p, text_lo, t, {}, leaders, n_tx, true);
+    const std::string body = translate_blocks(p, text_lo, t, {}, leaders, n_tx, true, nullptr,
+                                              !(flags & FI_CFG_NO_LOAD_AHEAD));
     if (out && cap) {
         const uint64_t n = std::min<uint64_t>(cap - 1, body.size());
         memcpy(out, body.data(), n);

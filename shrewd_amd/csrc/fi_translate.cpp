@@ -367,7 +367,7 @@ struct Block {
 // takes the full solo body).
 std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, const std::vector<uint32_t> &trace,
                              const std::vector<uint64_t> &extra_pcs, std::vector<uint32_t> &leaders_out,
-                             uint32_t &n_insts, bool odd_streams, std::vector<LoopEst> *loops_out) {
+                             uint32_t &n_insts, bool odd_streams, std::vector<LoopEst> *loops_out, bool load_ahead) {
     std::set<uint32_t> executed, leaders;
     auto valid = [&](uint32_t h) { return h < pre.size() && (pre[h].flags & kPreValid); };
     // only code the golden run executed more than once is translated: straight-
@@ -594,6 +594,11 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
     // blocks, so a hit equals tlb_find) -- at most kSiteCaches of them
     constexpr uint32_t kSiteCaches = 8;
     uint32_t n_sites = 0;
+    // site caches that also hold a load issued one pass ahead (HV_i / HT_i) -> the load's size.  The
+    // held value keeps the width the load instruction delivers (32 bits up to a word): widened to 64
+    // bits at the load, the conversion -- and with it the wait for the load -- lands in the pass
+    // that issues it, not in the one that uses it
+    std::map<uint32_t, uint32_t> ahead_sites;
     n_insts = 0;
     auto hex = [](uint64_t v) {
         char b[32];
@@ -678,6 +683,90 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
         return av_ok(AVal{AV_BND, 0, a.lo << k, a.hi << k});
     };
     auto av_const = [&](int64_t lo, int64_t hi) { return av_ok(AVal{AV_BND, 0, lo, hi}); };
+    // The run-off block's address analysis: E branches to itself, writes[r]
+    // counts its writes of r, reg is its counter (0: not known -- the counter
+    // then counts as one more induction register).  loads: every access it
+    // could place; ok: it placed them all (the proof needs that).
+    struct RunOff { bool ok = true, stores = false; std::vector<ProofLoad> loads; };
+    auto runoff_walk = [&](const Block &E, const uint32_t *writes, uint32_t reg) {
+        RunOff ro;
+        AVal av[32];
+        for (uint32_t r = 0; r < 32; r++) av[r] = writes[r] ? AVal{AV_TOP, 0, 0, 0} : AVal{AV_BND, r, 0, 0};
+        // other induction registers: written once per iteration, by
+        // addi r, r, c -- an access at r walks memory with its own step
+        // (kinds 3 / 4: the step travels in the span field)
+        int ind_step[32] = {0};
+        for (size_t i = 0; i < E.insts.size(); i++) {
+            const PreInst &p = pre[E.insts[i]];
+            if ((p.op == OP_addi || p.op == OP_c_addi) && p.rd && p.rd == p.rs1 && p.rd != reg && writes[p.rd] == 1 &&
+                p.imm != 0 && p.imm >= -2048 && p.imm <= 2048) {
+                ind_step[p.rd] = p.imm;
+                av[p.rd] = AVal{AV_IND, p.rd, 0, 0};
+            }
+        }
+        if (reg) av[reg] = AVal{AV_CNT, 0, 0, 0};
+        for (size_t i = 0; i < E.insts.size(); i++) {
+            std::string e;
+            uint32_t sz;
+            int sx;
+            const char *cond;
+            const PreInst &p = pre[E.insts[i]];
+            const Cls k = classify(p, e, sz, sx, cond);
+            const AVal A = av[p.rs1], B = av[p.rs2];
+            const int64_t imm = p.imm;
+            if (k == C_LOAD) {
+                if (A.k == AV_CNT) ro.loads.push_back({reg, 0u, sz, (uint32_t)i, A.lo + imm, 0u});
+                else if (A.k == AV_IND)
+                    ro.loads.push_back({A.base, 3u, sz, (uint32_t)i, A.lo + imm, (uint64_t)(uint32_t)ind_step[A.base]});
+                else if (A.k == AV_BND) ro.loads.push_back({A.base, 1u, sz, (uint32_t)i, A.lo + imm, (uint64_t)(A.hi - A.lo)});
+                else ro.ok = false;
+                if (p.rd) av[p.rd] = AVal{AV_TOP, 0, 0, 0};
+                continue;
+            }
+            // a store at the counter plus a constant walks memory like a
+            // counter load (kind 2: loop_outcome also keeps it out of the
+            // code range); its data never steers the loop, whose exit
+            // depends on the counter alone.  Any other store: no proof.
+            if (k == C_STORE) {
+                ro.stores = true;
+                if (A.k == AV_CNT) ro.loads.push_back({reg, 2u, sz, (uint32_t)i, A.lo + imm, 0u});
+                else if (A.k == AV_IND)
+                    ro.loads.push_back({A.base, 4u, sz, (uint32_t)i, A.lo + imm, (uint64_t)(uint32_t)ind_step[A.base]});
+                else ro.ok = false;
+                continue;
+            }
+            if (!p.rd || (k != C_ALU && k != C_JAL)) continue;
+            AVal v{AV_TOP, 0, 0, 0};
+            if (k == C_ALU) switch (p.op) {
+            case OP_addi: case OP_c_addi: case OP_c_addi4spn: case OP_c_addi16sp:
+                if (A.k == AV_CNT) v = AVal{AV_CNT, 0, A.lo + imm, A.lo + imm};
+                else if (A.k == AV_IND && p.rd == A.base) v = AVal{AV_IND, A.base, A.lo + imm, A.lo + imm};
+                else v = av_add(A, av_const(imm, imm));
+                break;
+            case OP_add: case OP_c_add: v = av_add(A, B); break;
+            case OP_c_mv: v = B; break;
+            case OP_andi: case OP_c_andi: if (imm >= 0) v = av_const(0, imm); break;
+            case OP_c_zext_b: v = av_const(0, 0xFF); break;
+            case OP_c_zext_h: v = av_const(0, 0xFFFF); break;
+            case OP_slli: case OP_c_slli: v = av_shl(A, imm); break;
+            case OP_srli: case OP_c_srli: if (imm >= 44 && imm < 64) v = av_const(0, (int64_t)((1ULL << (64 - imm)) - 1)); break;
+            case OP_sh1add: v = av_add(av_shl(A, 1), B); break;
+            case OP_sh2add: v = av_add(av_shl(A, 2), B); break;
+            case OP_sh3add: v = av_add(av_shl(A, 3), B); break;
+            case OP_c_li: case OP_lui: v = av_const(imm, imm); break;
+            default: break;
+            }
+            av[p.rd] = v;
+        }
+        return ro;
+    };
+    // ---- loads one pass ahead (clean body).  In a store-free
+    // block that branches to itself, a load whose address is an induction
+    // register of the walk above plus an immediate reads, one pass later, the
+    // address it reads now plus the register's step: its site issues that load
+    // now (ahead_at: the load's pre-decoded index -> the step).  This needs
+    // none of the proof's other conditions (one exit, a counter, its steps).
+    std::map<uint32_t, int> ahead_at;
     for (uint32_t H : S.headers) {
         std::vector<uint32_t> cyc;
         bool nested = false;
@@ -721,6 +810,15 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
             }
             if (ok && !b.term) to(text_lo + 2ULL * b.insts.back() + pre[b.insts.back()].len, false);
         }
+        if (load_ahead && ok && in.size() == 1 && !nx[H].empty()) {
+            const Block &L = *bl[H];
+            const RunOff ro = runoff_walk(L, writes, 0);
+            for (const ProofLoad &l : ro.loads) {
+                const PreInst &p = pre[L.insts[l.pos]];
+                if (!ro.stores && l.kind == 3 && p.rs1 == l.reg && p.rd && p.rd != l.reg)
+                    ahead_at[L.insts[l.pos]] = (int)(int32_t)(uint32_t)l.span;
+            }
+        }
         if (!ok || n_exit != 1) continue;
         const Block &E = *bl[eblk];
         const PreInst &br = pre[E.insts.back()];
@@ -749,73 +847,9 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
         // run-off block: the loads' addresses
         std::vector<ProofLoad> loads;
         if (in.size() == 1) {
-            AVal av[32];
-            for (uint32_t r = 0; r < 32; r++) av[r] = writes[r] ? AVal{AV_TOP, 0, 0, 0} : AVal{AV_BND, r, 0, 0};
-            // other induction registers: written once per iteration, by
-            // addi r, r, c -- an access at r walks memory with its own step
-            // (kinds 3 / 4: the step travels in the span field)
-            int ind_step[32] = {0};
-            for (size_t i = 0; i < E.insts.size(); i++) {
-                const PreInst &p = pre[E.insts[i]];
-                if ((p.op == OP_addi || p.op == OP_c_addi) && p.rd && p.rd == p.rs1 && p.rd != reg && writes[p.rd] == 1 &&
-                    p.imm != 0 && p.imm >= -2048 && p.imm <= 2048) {
-                    ind_step[p.rd] = p.imm;
-                    av[p.rd] = AVal{AV_IND, p.rd, 0, 0};
-                }
-            }
-            av[reg] = AVal{AV_CNT, 0, 0, 0};
-            for (size_t i = 0; i < E.insts.size() && ok; i++) {
-                std::string e;
-                uint32_t sz;
-                int sx;
-                const char *cond;
-                const PreInst &p = pre[E.insts[i]];
-                const Cls k = classify(p, e, sz, sx, cond);
-                const AVal A = av[p.rs1], B = av[p.rs2];
-                const int64_t imm = p.imm;
-                if (k == C_LOAD) {
-                    if (A.k == AV_CNT) loads.push_back({reg, 0u, sz, (uint32_t)i, A.lo + imm, 0u});
-                    else if (A.k == AV_IND)
-                        loads.push_back({A.base, 3u, sz, (uint32_t)i, A.lo + imm, (uint64_t)(uint32_t)ind_step[A.base]});
-                    else if (A.k == AV_BND) loads.push_back({A.base, 1u, sz, (uint32_t)i, A.lo + imm, (uint64_t)(A.hi - A.lo)});
-                    else ok = false;
-                    if (p.rd) av[p.rd] = AVal{AV_TOP, 0, 0, 0};
-                    continue;
-                }
-                // a store at the counter plus a constant walks memory like a
-                // counter load (kind 2: loop_outcome also keeps it out of the
-                // code range); its data never steers the loop, whose exit
-                // depends on the counter alone.  Any other store: no proof.
-                if (k == C_STORE) {
-                    if (A.k == AV_CNT) loads.push_back({reg, 2u, sz, (uint32_t)i, A.lo + imm, 0u});
-                    else if (A.k == AV_IND)
-                        loads.push_back({A.base, 4u, sz, (uint32_t)i, A.lo + imm, (uint64_t)(uint32_t)ind_step[A.base]});
-                    else ok = false;
-                    continue;
-                }
-                if (!p.rd || (k != C_ALU && k != C_JAL)) continue;
-                AVal v{AV_TOP, 0, 0, 0};
-                if (k == C_ALU) switch (p.op) {
-                case OP_addi: case OP_c_addi: case OP_c_addi4spn: case OP_c_addi16sp:
-                    if (A.k == AV_CNT) v = AVal{AV_CNT, 0, A.lo + imm, A.lo + imm};
-                    else if (A.k == AV_IND && p.rd == A.base) v = AVal{AV_IND, A.base, A.lo + imm, A.lo + imm};
-                    else v = av_add(A, av_const(imm, imm));
-                    break;
-                case OP_add: case OP_c_add: v = av_add(A, B); break;
-                case OP_c_mv: v = B; break;
-                case OP_andi: case OP_c_andi: if (imm >= 0) v = av_const(0, imm); break;
-                case OP_c_zext_b: v = av_const(0, 0xFF); break;
-                case OP_c_zext_h: v = av_const(0, 0xFFFF); break;
-                case OP_slli: case OP_c_slli: v = av_shl(A, imm); break;
-                case OP_srli: case OP_c_srli: if (imm >= 44 && imm < 64) v = av_const(0, (int64_t)((1ULL << (64 - imm)) - 1)); break;
-                case OP_sh1add: v = av_add(av_shl(A, 1), B); break;
-                case OP_sh2add: v = av_add(av_shl(A, 2), B); break;
-                case OP_sh3add: v = av_add(av_shl(A, 3), B); break;
-                case OP_c_li: case OP_lui: v = av_const(imm, imm); break;
-                default: break;
-                }
-                av[p.rd] = v;
-            }
+            const RunOff ro = runoff_walk(E, writes, reg);
+            ok = ro.ok;
+            loads = ro.loads;
             for (const ProofLoad &l : loads)
                 if (l.off <= -((int64_t)1 << 31) || l.off >= ((int64_t)1 << 31) || (l.kind < 3 && l.span >= (1u << 20)))
                     ok = false;
@@ -1213,6 +1247,26 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
                     (unsigned long long)pc0);
         else
             sboth(sfmt("%s%u: { // pc 0x%llx, %u insts\n", SB.c_str(), h0, (unsigned long long)pc0, n));
+        // clean body: the block's loads that run one pass ahead (instruction ->
+        // site cache), their tags dropped on every entry but the block's own
+        // back edge, which enters below the reset (S_<h>_L)
+        std::map<uint32_t, uint32_t> blk_ahead;
+        const size_t sc_at = sc.out.size();
+        if (!oddon && !cur_odd && S.chain.count(h0)) {
+            uint32_t ns = n_sites;
+            for (uint32_t i = 0; i < n && ns < kSiteCaches; i++) {
+                std::string e;
+                uint32_t sz;
+                int sx;
+                const char *cond;
+                const Cls k = classify(pre[insts[i]], e, sz, sx, cond);
+                if (k != C_LOAD && k != C_STORE) continue;
+                if (k == C_LOAD && ahead_at.count(insts[i])) blk_ahead[i] = ns;
+                ns++;
+            }
+            for (const auto &kv : blk_ahead) sc.put("  HT%u = ~0ULL;\n", kv.second);
+            if (!blk_ahead.empty()) sc.put("%s%u_L: ;\n", SB.c_str(), h0);
+        }
         if (!cur_odd && S.headers.count(h0)) {   // a cycle header routes an entry into its cycle one level on (etgt)
             std::string rw_, rs_, rc_;
             for (uint32_t x : leaders) {
@@ -1281,6 +1335,8 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
             const PreInst &p = pre[insts[i]];
             const uint64_t pc = cur_odd ? b.opcs[i] : g.pc_of(insts[i]);
             const uint64_t ft = pc + p.len;
+            const uint32_t i_inst = i;
+            int sc_site = -1;   // the clean body's site cache of this access
             std::string e;
             uint32_t sz;
             int sx;
@@ -1315,9 +1371,12 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
                     if (!oddon) {
                         if (S.chain.count(h0) && n_sites < kSiteCaches) {
                             const uint32_t i = n_sites++;
+                            sc_site = (int)i;
+                            const std::string drop = blk_ahead.count(i_inst) ? sfmt("HT%u = ~0ULL; ", i) : std::string();
                             sc.put("  { uint8_t *p_; bool pv_; const uint64_t ea_ = %s + %s, vp_ = ea_ >> 12;\n"
                                    "    if (%s(vp_ != CV%u)) { const uint64_t e_ = tlb_find(m, vp_); if (SCOND(!e_)) %s "
-                                   "SC_SET(%u, vp_, e_); }\n", A.c_str(), immb, cold, i, sleave_here.c_str(), i);
+                                   "SC_SET(%u, vp_, e_); %s}\n", A.c_str(), immb, cold, i, sleave_here.c_str(), i,
+                                   drop.c_str());
                             if (sz > 1)
                                 sc.put("    if (%s(((uint32_t)ea_ & 4095u) > %uu)) %s\n", cold, 4096u - sz, sleave_here.c_str());
                             sc.put("    p_ = SC_PTR(%u, ea_); pv_ = SC_PRIV(%u);\n", i, i);
@@ -1328,8 +1387,23 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
                 }
                 if (p.rd) {
                     g.put("    p_ = ok_ ? p_ : const_cast<uint8_t *>(zp);\n");
-                    sboth(sfmt("    uint64_t v_; if (SPRIV(pv_)) v_ = *(const g_%s *)p_; else v_ = tx_sload(p_, %uu);\n",
-                               gtype(sz), sz));
+                    const std::string ld = sfmt("    uint64_t v_; if (SPRIV(pv_)) v_ = *(const g_%s *)p_; else v_ = tx_sload(p_, %uu);\n",
+                                                gtype(sz), sz);
+                    so_.out += ld;
+                    if (!oddon && sc_site >= 0 && blk_ahead.count(i_inst)) {
+                        // the value: the one held from the last pass if it was loaded from
+                        // this address, else from memory; then the next pass's load, if it
+                        // lies in this page (one unsigned compare, either sign of the step)
+                        const int stp = ahead_at[insts[i_inst]];
+                        sc.put("    uint64_t v_; if (HT%d == ea_) v_ = HV%d; else v_ = *(const g_%s *)p_;\n", sc_site, sc_site,
+                               gtype(sz));
+                        sc.put("    if (%s(((uint32_t)ea_ & 4095u) + (uint32_t)%d > %uu)) HT%d = ~0ULL;\n"
+                               "    else { HV%d = *(const g_%s *)(p_ + %d); HT%d = ea_ + (uint64_t)(int64_t)%d; }\n", cold, stp,
+                               4096u - sz, sc_site, sc_site, gtype(sz), stp, sc_site, stp);
+                        ahead_sites[(uint32_t)sc_site] = sz;
+                    } else if (!oddon) {
+                        sc.out += ld;
+                    }
                     if (sx) {
                         g.put("    TXSET(%u, (int64_t)(int%d_t)*(const g_%s *)p_); }\n", p.rd, sx, gtype(sz));
                         sboth(sfmt("    X%u = (uint64_t)(int64_t)(int%d_t)v_; }\n", p.rd, sx));
@@ -1442,6 +1516,11 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
         }
         g.put("}\n");
         sboth("}\n");
+        if (!blk_ahead.empty()) {   // the block's own edges to itself: below the reset
+            const std::string from = sfmt("goto %s%u;", SB.c_str(), h0), to = sfmt("goto %s%u_L;", SB.c_str(), h0);
+            for (size_t at = sc.out.find(from, sc_at); at != std::string::npos; at = sc.out.find(from, at + to.size()))
+                sc.out.replace(at, from.size(), to);
+        }
         if (cur_odd) g.out.swap(g_keep);
     }
     if (oddon) g.out.swap(g_mode);
@@ -1458,6 +1537,8 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
                "#define SOVER(n_) __builtin_expect(brem < (n_), 0)\n#define SDONE() (bud - brem)\n"
                "#define SCOLD(x) __builtin_expect(!!(x), 0)\n";
     for (uint32_t i = 0; i < kSiteCaches; i++) sc_head += sfmt("  uint64_t CV%u, CP%u; uint32_t CQ%u;\n", i, i, i);
+    for (const auto &kv : ahead_sites)
+        sc_head += sfmt("  %s HV%u; uint64_t HT%u;\n", kv.second == 8 ? "uint64_t" : "uint32_t", kv.first, kv.first);
     sc_head += "S_entry:\n";
     for (uint32_t i = 0; i < kSiteCaches; i++) sc_head += sfmt("  CV%u = ~0ULL; CP%u = 0; CQ%u = 0;\n", i, i, i);
     sc_head += "  goto S_dispatch;\n";

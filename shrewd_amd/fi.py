@@ -140,6 +140,7 @@ CFG_JIT_NO_CACHE = 8192
 CFG_NO_HANG_PROOF = 16384
 CFG_NO_OVERFLOW = 32768
 CFG_NO_LOOP_ORDER = 65536
+CFG_NO_LOAD_AHEAD = 131072
 
 
 class GoldenInfo(C.Structure):
@@ -329,6 +330,8 @@ def lib():
                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.fi_debug_translate.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_char_p, C.c_uint64,
                                          C.POINTER(C.c_uint64)]
+        L.fi_debug_translate_flags.argtypes = [vp, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint32, C.c_char_p,
+                                               C.c_uint64, C.POINTER(C.c_uint64)]
         L.fi_debug_translation.argtypes = [vp, C.c_char_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.fi_issue_default_params.argtypes = [C.POINTER(IssueParams)]
         L.fi_issue_model_run.argtypes = [vp, C.c_uint64, C.POINTER(IssueParams), vp, C.POINTER(IssueStats)]
