@@ -11,20 +11,23 @@ extern "C" {
  * the interpreter's pre-decode and slow fetch path use); out receives n
  * 16-byte records {u32 raw; u8 op, rd, rs1, rs2; i32 imm; u8 len, flags; u16 aux}. */
 fi_status fi_debug_decode(fi_engine *e, const uint32_t *raws, uint64_t n, void *out);
-/* Counters of the last interpreter launch (layout: DevCtx::stats in
- * shrewd_amd/csrc/fi_types.h): fetch/data bytes, private pages, golden
- * cycles/output, loop iterations, lane-instructions, slow fetches, min-PC
- * reductions, snapshot comparisons and early exits, translated instructions
- * and entries, the slowest wave, wave-0 clock, per-kernel bytes; [32..39]
- * -DFI_PROF builds only.  64 entries. */
+/* Counters of the last interpreter launch: 64 entries, one per slot of the
+ * table FI_STAT_SLOTS in shrewd_amd/csrc/fi_types.h (slot, name, what it
+ * counts); a slot the table does not name stays 0. */
 fi_status fi_debug_stats(fi_engine *e, uint64_t *out64);
+/* The name of a slot of fi_debug_stats in that table, NULL for an unnamed one
+ * (and for slot >= 64).  Needs no engine and no device. */
+const char *fi_debug_stat_name(uint32_t slot);
 /* The engine's IEEE arithmetic port (shrewd_amd/csrc/hip/fi_softfp.h) over
  * operand vectors, on the host (on_device = 0) or the device: op / fmt codes of
  * fi::sf::op; out = result bits, fl = fflags raised. */
 fi_status fi_debug_softfp(int op, int fmt, int rm, const uint64_t *a, const uint64_t *b, const uint64_t *c,
                           uint64_t n, uint64_t *out, uint32_t *fl, int on_device);
-/* Per wave of the last launch: {s_memtime cycles, loop iterations,
- * translated instructions, slow fetches} (4 x u64 each). */
+/* Per wave of the last launch, 10 x u64 each (fi_types.h WaveDbg):
+ * {s_memtime cycles, loop iterations, translated instructions,
+ * slow fetches | min-PC reductions << 32, s_memrealtime (100 MHz) at the
+ * wave's start, at its end, lane 0's trial (~0: none), its instructions in
+ * this dispatch, translated-code entries, lane 0's full page-table lookups}. */
 fi_status fi_debug_waves(fi_engine *e, uint64_t *out, uint64_t n_waves);
 /* Device time of each interpreter dispatch since fi_kernel_timer_reset, in
  * launch order (epochs of each chunk); *n = dispatches (at most cap written). */

@@ -28,6 +28,7 @@
 #include "fi_capture.h"
 #include "fi_checkpoint.h"
 #include "fi_debug.h"
+#include "fi_golden_host.h"
 #include "fi_site_draw.h"
 #include "fi_tick.h"
 #include "fi_tick_map.h"
@@ -350,6 +351,34 @@ static void dfree(T *&p) {
     if (p) { (void)hipFree((void *)p); p = nullptr; }
 }
 
+// A function-local device allocation of n elements: freed at reset() or at the
+// end of its scope, so that no return path has to free it.  (The engine's
+// persistent d_* buffers have one owner and one free path already.)
+template <typename T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { reset(); }
+    hipError_t alloc(uint64_t n) {
+        reset();
+        return hipMalloc(&p_, n * sizeof(T));
+    }
+    T *get() const { return p_; }
+    void reset() {
+        if (p_) { (void)hipFree((void *)p_); p_ = nullptr; }
+    }
+
+private:
+    T *p_ = nullptr;
+};
+
 // Diagnostics (SHREWD_FI_TRACE): a native backtrace on SIGSEGV.
 #include <execinfo.h>
 #include <csignal>
@@ -436,7 +465,7 @@ fi_status fi_create(const fi_config *cfg, fi_engine **out) {
         // (one block of P' - P pages per 2048 slots)
         size_t free_b = 0, total_b = 0;
         const uint64_t P = e->cfg.private_pages, P2 = redo_pages(P);
-        const uint64_t slot_b = 3 * sizeof(fi_site) + 3 * sizeof(fi_outcome) + 8 * 8 + 8 * 4 + 10 * 8 +
+        const uint64_t slot_b = 3 * sizeof(fi_site) + 3 * sizeof(fi_outcome) + 8 * 8 + 8 * 4 + kWaveDbgWords * 8 +
                                 sizeof(LaneSave) + sizeof(VmState) + 33 * 8 + kDmapWords * 4 + 4 + 64;
         const uint64_t per = P * (kPage + 8) + slot_b + (P2 > P ? (P2 - P) * (kPage + 8) / 2048 + 1 : 0);
         uint64_t cap = 65536;
@@ -930,7 +959,7 @@ static fi_status ensure_work(fi_engine *e, uint64_t n) {
     HIPCHK(hipMalloc(&e->d_eff, c * 8));
     HIPCHK(hipMalloc(&e->d_hist, sizeof(fi_histogram)));
     HIPCHK(hipMalloc(&e->d_stats, kNStats * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&e->d_wave_dbg, c * 10 * sizeof(uint64_t)));
+    HIPCHK(hipMalloc(&e->d_wave_dbg, c * kWaveDbgWords * sizeof(uint64_t)));
     HIPCHK(hipMalloc(&e->d_priv, c * e->cfg.private_pages * kPage));
     HIPCHK(hipMalloc(&e->d_priv_vpn, c * e->cfg.private_pages * 8));
     HIPCHK(hipMalloc(&e->d_save, c * sizeof(LaneSave)));
@@ -1043,15 +1072,14 @@ static fi_status golden_launch(fi_engine *e, uint32_t P, uint64_t rec_I, uint32_
                                uint8_t *d_rp, uint64_t *d_rv, uint32_t *d_trace, uint32_t trace_cap, uint8_t *d_ro,
                                uint8_t *d_re, uint64_t rec_cap, fi_outcome &o, unsigned long long *stats,
                                MemEv *d_mem = nullptr, uint32_t mem_cap = 0) {
-    uint8_t *d_gpriv = nullptr;
-    uint64_t *d_gvpn = nullptr;
-    HIPCHK(hipMalloc(&d_gpriv, (uint64_t)P * kPage));
-    HIPCHK(hipMalloc(&d_gvpn, (uint64_t)P * 8));
-    uint64_t *d_gfregs = nullptr;
-    HIPCHK(hipMalloc(&d_gfregs, 33 * sizeof(uint64_t)));   // 32 FP registers + fd 0's offset
+    DevBuf<uint64_t> gvpn, gfregs;   // (declared so that they are freed in the order gpriv, gfregs, gvpn)
+    DevBuf<uint8_t> gpriv;
+    HIPCHK(gpriv.alloc((uint64_t)P * kPage));
+    HIPCHK(gvpn.alloc(P));
+    HIPCHK(gfregs.alloc(33));   // 32 FP registers + fd 0's offset
     DevCtx c = base_ctx(e);
-    c.fregs = d_gfregs;
-    c.in_pos = d_gfregs + 32;
+    c.fregs = gfregs.get();
+    c.in_pos = gfregs.get() + 32;
     c.dmap = nullptr;
     c.ov_blocks = 0;   // (the golden run has its own P pages, no overflow pool)
     c.record = 1;
@@ -1059,7 +1087,7 @@ static fi_status golden_launch(fi_engine *e, uint32_t P, uint64_t rec_I, uint32_
     c.snap_start = 0;
     c.rec_out = d_ro; c.rec_err = d_re; c.rec_cap = rec_cap;
     c.hang_cap = 1ULL << 30;   // golden safety cap
-    c.priv_pages = P; c.priv_frames = d_gpriv; c.priv_vpn = d_gvpn;
+    c.priv_pages = P; c.priv_frames = gpriv.get(); c.priv_vpn = gvpn.get();
     c.rec_snaps = d_rs; c.rec_pages = d_rp; c.rec_vpns = d_rv; c.rec_interval = rec_I; c.rec_max_snaps = rec_max;
     c.rec_trace = d_trace; c.rec_trace_cap = d_trace ? trace_cap : 0;
     c.rec_mem = d_mem; c.rec_mem_cap = d_mem ? mem_cap : 0;
@@ -1077,9 +1105,6 @@ static fi_status golden_launch(fi_engine *e, uint32_t P, uint64_t rec_I, uint32_
     if (err == hipSuccess) err = hipEventElapsedTime(&ms, e->ev0, e->ev1);
     if (err == hipSuccess) err = hipMemcpy(&o, e->d_out, sizeof o, hipMemcpyDeviceToHost);
     if (err == hipSuccess) err = hipMemcpy(stats, e->d_stats, kNStats * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    (void)hipFree(d_gpriv);
-    (void)hipFree(d_gfregs);
-    (void)hipFree(d_gvpn);
     if (err != hipSuccess) return fail(e, FI_E_HIP, "golden launch: %s", hipGetErrorString(err));
     e->last_ms = ms;
     if (o.cls != FI_MASKED)
@@ -1162,13 +1187,10 @@ static void tick_prepare(fi_engine *e, const std::vector<MemEv> &mev, bool mev_o
     e->t_status = "";
 }
 
-fi_status fi_golden_run(fi_engine *e, fi_golden_info *out) {
-    if (!e) return FI_E_ARG;
-    if (!e->loaded) return fail(e, FI_E_STATE, "fi_golden_run: no workload loaded");
-    HIPCHK(hipSetDevice(e->dev));
-    fi_status st = ensure_work(e, 64);
-    if (st) return st;
-    // back to the process-start image only
+// ---- fi_golden_run's steps, in the order it takes them
+
+// Step 1: back to the process-start image only.
+static fi_status golden_reset(fi_engine *e) {
     e->t_status = "no golden run";
     e->t_ops.clear(); e->t_ticks.clear(); e->tk_done.clear(); e->tk_rec.clear();
     free_tick_table(e);   // (uploaded again from the new golden run's at the next device map)
@@ -1178,35 +1200,32 @@ fi_status fi_golden_run(fi_engine *e, fi_golden_info *out) {
     e->snap_I = 1ULL << 62;
     e->pre_ok = true;
     e->have_golden = false;
-    st = upload_snaps(e);
-    if (st) return st;
+    return upload_snaps(e);
+}
 
-    // ---- pass 1: the golden run itself (output, instruction count, footprint)
-    const uint64_t rec_cap = 1 << 24;
+constexpr uint64_t kGoldenRecCap = 1 << 24;   // bytes of stdout / stderr the golden launches record
+
+// Step 2, pass 1: the golden run itself (output, instruction count,
+// footprint) into e->golden and the golden streams.  rec_out / rec_err stay
+// allocated for pass 2.
+static fi_status golden_pass1(fi_engine *e, DevBuf<uint8_t> &rec_out, DevBuf<uint8_t> &rec_err, fi_outcome &o,
+                              uint64_t &gpages) {
     const uint32_t kGoldenPages = 4096;   // 16 MiB of written pages
-    uint8_t *d_rec_out = nullptr, *d_rec_err = nullptr;
-    HIPCHK(hipMalloc(&d_rec_out, rec_cap));
-    HIPCHK(hipMalloc(&d_rec_err, rec_cap));
-    fi_outcome o;
+    HIPCHK(rec_out.alloc(kGoldenRecCap));
+    HIPCHK(rec_err.alloc(kGoldenRecCap));
     unsigned long long stats[kNStats];
-    st = golden_launch(e, kGoldenPages, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, d_rec_out, d_rec_err, rec_cap, o,
-                       stats);
-    if (st) { (void)hipFree(d_rec_out); (void)hipFree(d_rec_err); return st; }
-    const double golden_ms = e->last_ms;
-    const uint64_t ol = stats[4], el = stats[5];
-    const uint64_t gpages = stats[2];
-    if (ol > rec_cap || el > rec_cap) {
-        (void)hipFree(d_rec_out); (void)hipFree(d_rec_err);
-        return fail(e, FI_E_GOLDEN, "golden output exceeds %llu bytes", (unsigned long long)rec_cap);
-    }
-    if (gpages >= kGoldenPages) {
-        (void)hipFree(d_rec_out); (void)hipFree(d_rec_err);
-        return fail(e, FI_E_GOLDEN, "golden run writes more than %u pages", kGoldenPages);
-    }
+    fi_status st = golden_launch(e, kGoldenPages, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, rec_out.get(),
+                                 rec_err.get(), kGoldenRecCap, o, stats);
+    if (st) return st;
+    const uint64_t ol = stats[ST_GOLDEN_OUT_LEN], el = stats[ST_GOLDEN_ERR_LEN];
+    gpages = stats[ST_PAGES];
+    if (ol > kGoldenRecCap || el > kGoldenRecCap)
+        return fail(e, FI_E_GOLDEN, "golden output exceeds %llu bytes", (unsigned long long)kGoldenRecCap);
+    if (gpages >= kGoldenPages) return fail(e, FI_E_GOLDEN, "golden run writes more than %u pages", kGoldenPages);
     e->gout.assign(ol, 0);
     e->gerr.assign(el, 0);
-    if (ol) HIPCHK(hipMemcpy(e->gout.data(), d_rec_out, ol, hipMemcpyDeviceToHost));
-    if (el) HIPCHK(hipMemcpy(e->gerr.data(), d_rec_err, el, hipMemcpyDeviceToHost));
+    if (ol) HIPCHK(hipMemcpy(e->gout.data(), rec_out.get(), ol, hipMemcpyDeviceToHost));
+    if (el) HIPCHK(hipMemcpy(e->gerr.data(), rec_err.get(), el, hipMemcpyDeviceToHost));
     dfree(e->d_gout); dfree(e->d_gerr);
     HIPCHK(hipMalloc(&e->d_gout, std::max<uint64_t>(ol, 1)));
     HIPCHK(hipMalloc(&e->d_gerr, std::max<uint64_t>(el, 1)));
@@ -1214,191 +1233,149 @@ fi_status fi_golden_run(fi_engine *e, fi_golden_info *out) {
     if (el) HIPCHK(hipMemcpy(e->d_gerr, e->gerr.data(), el, hipMemcpyHostToDevice));
     e->golden = fi_golden_info{};
     e->golden.ninst = o.ninst;
-    e->golden.ncycles = stats[3];
+    e->golden.ncycles = stats[ST_GOLDEN_NCYCLES];
     e->golden.exit_code = o.exit_code;
     e->golden.stdout_len = ol;
     e->golden.stderr_len = el;
-    e->golden.fetch_bytes = stats[0];
-    e->golden.data_bytes = stats[1];
+    e->golden.fetch_bytes = stats[ST_FETCH_BYTES];
+    e->golden.data_bytes = stats[ST_DATA_BYTES];
     e->gdetail = o.detail;
     e->gsub = o.sub;
-    e->golden_fp = stats[22] != 0;
-    e->clk_until = stats[52];
+    e->golden_fp = stats[ST_GOLDEN_EXTRA_STATE] != 0;
+    e->clk_until = stats[ST_CLK_UNTIL];
+    return FI_OK;
+}
 
-    // ---- pass 2: the same run again, capturing a snapshot every I committed
-    // instructions (state + every page written so far), within ~1 GiB
+// What pass 2 brings back to the host.
+struct GoldenCapture {
+    uint64_t I = 0;                  // snapshot interval
+    uint32_t P = 0;                  // pages captured per snapshot (row pitch of pages / vpns)
+    fi_outcome o{};                  // the capture run's outcome
+    uint64_t n_snaps = 0;            // snapshots it took (ST_SNAPS_CAPTURED)
+    uint64_t n_events = 0;           // its trace events (ST_TRACE_EVENTS; trace is empty if they overflowed)
+    bool mem_ok = false;             // its access events fit their buffer: mev holds them all
+    bool unmapped = false;           // ST_GOLDEN_UNMAPPED
+    std::vector<SnapState> snaps;    // tab_n = pages captured with the snapshot
+    std::vector<uint8_t> pages;
+    std::vector<uint64_t> vpns;
+    std::vector<uint32_t> trace;
+    std::vector<PreInst> pre;        // the pre-decoded text, leader flags cleared
+    std::vector<MemEv> mev;
+};
+
+// Step 3, pass 2: the same run again, capturing a snapshot every I committed
+// instructions (state + every page written so far), within ~1 GiB; with it
+// the golden trace and data accesses.  Releases rec_out / rec_err.
+static fi_status golden_pass2(fi_engine *e, const fi_outcome &o, uint64_t gpages, DevBuf<uint8_t> &rec_out,
+                              DevBuf<uint8_t> &rec_err, GoldenCapture &g) {
     uint64_t I = std::max<uint64_t>(e->cfg.snapshot_interval ? e->cfg.snapshot_interval : 256, 16);
     const uint32_t P = (uint32_t)std::max<uint64_t>(gpages, 1);
     while (o.ninst / I + 2 > 65536 || (o.ninst / I + 2) * P * kPage > (1ULL << 30)) I *= 2;
     const uint32_t rec_max = (uint32_t)(o.ninst / I + 2);
-    SnapState *d_rs = nullptr;
-    uint8_t *d_rp = nullptr;
-    uint64_t *d_rv = nullptr;
-    HIPCHK(hipMalloc(&d_rs, (uint64_t)rec_max * sizeof(SnapState)));
-    HIPCHK(hipMalloc(&d_rp, (uint64_t)rec_max * P * kPage));
-    HIPCHK(hipMalloc(&d_rv, (uint64_t)rec_max * P * 8));
+    DevBuf<uint64_t> d_rv;   // (declared so that they are freed in the order d_rs, d_rp, d_rv)
+    DevBuf<uint8_t> d_rp;
+    DevBuf<SnapState> d_rs;
+    HIPCHK(d_rs.alloc(rec_max));
+    HIPCHK(d_rp.alloc((uint64_t)rec_max * P * kPage));
+    HIPCHK(d_rv.alloc((uint64_t)rec_max * P));
     // golden trace for the register liveness pass: one entry per committed
     // instruction and ecall (capped; without it every register counts as live)
     const uint32_t trace_cap = (uint32_t)std::min<uint64_t>(o.ninst + 4096, 1ULL << 26);
-    uint32_t *d_trace = nullptr;
-    HIPCHK(hipMalloc(&d_trace, (uint64_t)trace_cap * 4));
+    DevBuf<uint32_t> d_trace;
+    HIPCHK(d_trace.alloc(trace_cap));
     // and its data accesses for the memory liveness index
     const uint32_t mem_cap = (uint32_t)std::min<uint64_t>(2 * o.ninst + 4096, 1ULL << 24);
-    MemEv *d_mem = nullptr;
-    HIPCHK(hipMalloc(&d_mem, (uint64_t)mem_cap * sizeof(MemEv)));
-    fi_outcome o2;
-    st = golden_launch(e, P, I, rec_max, d_rs, d_rp, d_rv, d_trace, trace_cap, d_rec_out, d_rec_err, rec_cap, o2,
-                       stats, d_mem, mem_cap);
-    (void)hipFree(d_rec_out);
-    (void)hipFree(d_rec_err);
-    std::vector<SnapState> rs;
-    std::vector<uint8_t> rp;
-    std::vector<uint64_t> rv;
-    std::vector<uint32_t> trace;
-    std::vector<PreInst> pre;
-    uint32_t ns = 0;
-    const uint64_t n_events = stats[15];
-    if (!st && n_events <= trace_cap) {
-        trace.resize(n_events);
-        pre.resize((e->text_hi - e->text_lo) / 2);
-        hipError_t err = hipMemcpy(trace.data(), d_trace, n_events * 4, hipMemcpyDeviceToHost);
-        if (err == hipSuccess) err = hipMemcpy(pre.data(), e->d_pre, pre.size() * sizeof(PreInst), hipMemcpyDeviceToHost);
-        for (auto &p : pre) p.flags &= (uint8_t)~(kPreLeader | kPreOddLeader);
+    DevBuf<MemEv> d_mem;
+    HIPCHK(d_mem.alloc(mem_cap));
+    unsigned long long stats[kNStats] = {};
+    fi_status st = golden_launch(e, P, I, rec_max, d_rs.get(), d_rp.get(), d_rv.get(), d_trace.get(), trace_cap,
+                                 rec_out.get(), rec_err.get(), kGoldenRecCap, g.o, stats, d_mem.get(), mem_cap);
+    rec_out.reset();
+    rec_err.reset();
+    g.I = I;
+    g.P = P;
+    g.n_snaps = stats[ST_SNAPS_CAPTURED];
+    g.n_events = stats[ST_TRACE_EVENTS];
+    g.unmapped = stats[ST_GOLDEN_UNMAPPED] != 0;
+    if (!st && g.n_events <= trace_cap) {
+        g.trace.resize(g.n_events);
+        g.pre.resize((e->text_hi - e->text_lo) / 2);
+        hipError_t err = hipMemcpy(g.trace.data(), d_trace.get(), g.n_events * 4, hipMemcpyDeviceToHost);
+        if (err == hipSuccess)
+            err = hipMemcpy(g.pre.data(), e->d_pre, g.pre.size() * sizeof(PreInst), hipMemcpyDeviceToHost);
+        for (auto &p : g.pre) p.flags &= (uint8_t)~(kPreLeader | kPreOddLeader);
         if (err != hipSuccess) st = fail(e, FI_E_HIP, "trace download: %s", hipGetErrorString(err));
     }
-    (void)hipFree(d_trace);
-    const uint64_t n_mem = stats[25];
-    std::vector<MemEv> mev;
-    if (!st && n_mem <= mem_cap) {
-        mev.resize(n_mem);
-        hipError_t err = n_mem ? hipMemcpy(mev.data(), d_mem, n_mem * sizeof(MemEv), hipMemcpyDeviceToHost) : hipSuccess;
+    d_trace.reset();
+    const uint64_t n_mem = stats[ST_MEM_EVENTS];
+    g.mem_ok = n_mem <= mem_cap;
+    if (!st && g.mem_ok) {
+        g.mev.resize(n_mem);
+        hipError_t err =
+            n_mem ? hipMemcpy(g.mev.data(), d_mem.get(), n_mem * sizeof(MemEv), hipMemcpyDeviceToHost) : hipSuccess;
         if (err != hipSuccess) st = fail(e, FI_E_HIP, "access trace download: %s", hipGetErrorString(err));
     }
-    (void)hipFree(d_mem);
+    d_mem.reset();
     if (!st) {
-        ns = (uint32_t)std::min<unsigned long long>(stats[13], rec_max);
-        rs.resize(ns);
-        rp.resize((uint64_t)ns * P * kPage);
-        rv.resize((uint64_t)ns * P);
-        hipError_t err = hipMemcpy(rs.data(), d_rs, ns * sizeof(SnapState), hipMemcpyDeviceToHost);
-        if (err == hipSuccess) err = hipMemcpy(rp.data(), d_rp, rp.size(), hipMemcpyDeviceToHost);
-        if (err == hipSuccess) err = hipMemcpy(rv.data(), d_rv, rv.size() * 8, hipMemcpyDeviceToHost);
+        const uint32_t ns = (uint32_t)std::min<unsigned long long>(g.n_snaps, rec_max);
+        g.snaps.resize(ns);
+        g.pages.resize((uint64_t)ns * P * kPage);
+        g.vpns.resize((uint64_t)ns * P);
+        hipError_t err = hipMemcpy(g.snaps.data(), d_rs.get(), ns * sizeof(SnapState), hipMemcpyDeviceToHost);
+        if (err == hipSuccess) err = hipMemcpy(g.pages.data(), d_rp.get(), g.pages.size(), hipMemcpyDeviceToHost);
+        if (err == hipSuccess) err = hipMemcpy(g.vpns.data(), d_rv.get(), g.vpns.size() * 8, hipMemcpyDeviceToHost);
         if (err != hipSuccess) st = fail(e, FI_E_HIP, "snapshot download: %s", hipGetErrorString(err));
     }
-    (void)hipFree(d_rs); (void)hipFree(d_rp); (void)hipFree(d_rv);
-    if (st) return st;
-    if (o2.ninst != o.ninst || o2.detail != o.detail || stats[13] != o.ninst / I + 1)
-        return fail(e, FI_E_GOLDEN, "golden capture pass diverged from the golden run");
+    return st;   // (the snapshot capture buffers go here: before upload_snaps)
+}
 
-    // ---- host: deduplicate frames and build one sorted page table per snapshot
-    std::map<uint64_t, uint32_t> cur;   // vpn -> frame of its latest version
-    for (uint32_t i = 0; i < e->n_start_frames; i++) cur[e->tab[i].vpn] = e->tab[i].frame;
+// Step 4: deduplicate the captured frames into e->pool and build one sorted
+// page table per snapshot (fi_golden_host.h).
+static void golden_snap_tables(fi_engine *e, const GoldenCapture &g) {
     std::vector<SnapState> snaps;
     std::vector<PageEnt> tab;
-    for (uint32_t k = 0; k < ns; k++) {
-        SnapState S = rs[k];
-        for (uint32_t i = 0; i < S.tab_n; i++) {
-            const uint64_t vpn = rv[(uint64_t)k * P + i];
-            const uint8_t *pg = rp.data() + (((uint64_t)k * P + i) << 12);
-            auto it = cur.find(vpn);
-            if (it != cur.end() && !memcmp(e->pool.data() + ((uint64_t)it->second << 12), pg, kPage)) continue;
-            const uint32_t f = (uint32_t)(e->pool.size() / kPage);
-            e->pool.insert(e->pool.end(), pg, pg + kPage);
-            cur[vpn] = f;
-            // the pre-decoded text stays valid only if the golden run never rewrites it
-            const uint64_t va = vpn << 12;
-            if (va < e->code_hi && va + kPage > e->code_lo) {   // bytes of the code range in this page
-                const uint64_t a = std::max(va, e->code_lo), b = std::min(va + kPage, e->code_hi);
-                auto org = e->pages.find(vpn);
-                if (org == e->pages.end() || memcmp(org->second.data() + (a - va), pg + (a - va), b - a))
-                    e->pre_ok = false;
-            }
-        }
-        S.tab_off = (uint32_t)tab.size();
-        S.tab_n = (uint32_t)cur.size();
-        for (auto &kv : cur) {
-            PageEnt pe{};
-            pe.vpn = kv.first;
-            pe.frame = kv.second;
-            tab.push_back(pe);
-        }
-        snaps.push_back(S);
-    }
-    // ---- register liveness at each snapshot: backward over the golden trace,
-    // live = (live - writes) | reads; an ecall reads a0..a7.  Unknown entries
-    // (trace overflow, pc outside the pre-decoded text) leave every register live.
-    bool live_ok = !trace.empty() || n_events == 0;
-    std::vector<uint32_t> rmask(trace.size()), wmask(trace.size());
-    for (size_t i = 0; live_ok && i < trace.size(); i++) {
-        const uint32_t h = trace[i] & 0x7FFFFFFFu;
-        if (h >= pre.size() || !(pre[h].flags & kPreValid)) { live_ok = false; break; }
-        const PreInst &p = pre[h];
-        uint32_t r = 0, w = 0;
-        if ((p.flags & kPreRs1) && p.rs1) r |= 1u << p.rs1;
-        if ((p.flags & kPreRs2) && p.rs2) r |= 1u << p.rs2;
-        if ((trace[i] & 0x80000000u) || p.op == OP_m5op) r |= 0x3FC00u;   // x10..x17 (an M5Op's ABI arguments)
-        else if ((p.flags & kPreRd) && p.rd) w |= 1u << p.rd;
-        rmask[i] = r;
-        wmask[i] = w;
-    }
-    {
-        uint32_t live = 0;
-        int64_t ev = (int64_t)trace.size() - 1;
-        for (int64_t k = (int64_t)snaps.size() - 1; k >= 0; k--) {
-            if (!live_ok) { snaps[k].live = 0xFFFFFFFEu; continue; }
-            for (; ev >= (int64_t)snaps[k].trace_pos; ev--) live = (live & ~wmask[ev]) | rmask[ev];
-            snaps[k].live = live & ~1u;
-        }
-    }
-    e->snaps = snaps;
-    e->tab = tab;
-    e->snap_I = I;
-    e->g_pre.clear(); e->g_trace.clear();
-    if (live_ok && !trace.empty()) { e->g_pre = pre; e->g_trace = trace; }
-    // ---- first-access index (DESIGN.md §4 "first-access forwarding"): a
-    // register flipped at numInst t is neither read nor written by the golden
-    // run before its next access, so flipping it at that access instead gives
-    // the same machine; written first (or never touched again) it is dead.
-    free_fw(e);
-    {
-        const bool ok = live_ok && !trace.empty() && o.ninst < (1ULL << 29);
-        std::vector<uint32_t> off(33, 0), ev;
-        if (ok) {
-            for (size_t i = 0; i < trace.size(); i++)
-                for (uint32_t m = (rmask[i] | wmask[i]) & ~1u; m; m &= m - 1) off[__builtin_ctz(m) + 1]++;
-            for (int r = 0; r < 32; r++) off[r + 1] += off[r];
-            ev.resize(off[32]);
-            std::vector<uint32_t> at(off.begin(), off.end() - 1);
-            uint64_t t = 0;
-            for (size_t i = 0; i < trace.size(); i++) {
-                const bool ecall = (trace[i] & 0x80000000u) != 0;
-                const uint32_t key = (uint32_t)(2 * t + (ecall ? 0 : 1));
-                for (uint32_t m = (rmask[i] | wmask[i]) & ~1u; m; m &= m - 1) {
-                    const int r = __builtin_ctz(m);
-                    ev[at[r]++] = (key << 1) | ((rmask[i] >> r) & 1u);
-                }
-                if (!ecall) t++;
-            }
-            HIPCHK(hipMalloc(&e->d_fw_off, 33 * 4));
-            HIPCHK(hipMalloc(&e->d_fw_ev, std::max<size_t>(ev.size(), 1) * 4));
-            HIPCHK(hipMemcpy(e->d_fw_off, off.data(), 33 * 4, hipMemcpyHostToDevice));
-            if (!ev.empty()) HIPCHK(hipMemcpy(e->d_fw_ev, ev.data(), ev.size() * 4, hipMemcpyHostToDevice));
-            e->fw_ok = true;
-        }
-    }
-    st = upload_snaps(e);
-    if (st) return st;
-    st = build_mem_index(e, mev, live_ok && n_mem <= mem_cap);
-    if (st) return st;
-    e->golden_unmapped = stats[62] != 0;
-    tick_prepare(e, mev, !trace.empty() && n_mem <= mem_cap);
+    e->pre_ok = dedupe_snapshot_pages(e->tab.data(), e->n_start_frames, e->pool, e->pages, e->code_lo, e->code_hi,
+                                      g.snaps, g.pages, g.vpns, g.P, snaps, tab);
+    e->snaps = std::move(snaps);
+    e->tab = std::move(tab);
+    e->snap_I = g.I;
+}
 
-    // ---- translate the golden basic blocks and build the trial kernel with
-    // them (hipRTC); the static kernel stays the fallback
+// Step 5: register liveness at each snapshot (fi_golden_host.h); keeps the
+// trace and the text it indexes when it is usable.  Returns live_ok.
+static bool golden_liveness(fi_engine *e, const GoldenCapture &g, std::vector<uint32_t> &rmask,
+                            std::vector<uint32_t> &wmask) {
+    const bool live_ok = trace_liveness(g.pre, g.trace, g.n_events, OP_m5op, rmask, wmask, e->snaps);
+    e->g_pre.clear(); e->g_trace.clear();
+    if (live_ok && !g.trace.empty()) { e->g_pre = g.pre; e->g_trace = g.trace; }
+    return live_ok;
+}
+
+// Step 6: first-access index (DESIGN.md §4 "first-access forwarding"): a
+// register flipped at numInst t is neither read nor written by the golden
+// run before its next access, so flipping it at that access instead gives
+// the same machine; written first (or never touched again) it is dead.
+static fi_status golden_first_access(fi_engine *e, const GoldenCapture &g, bool live_ok,
+                                     const std::vector<uint32_t> &rmask, const std::vector<uint32_t> &wmask) {
+    free_fw(e);
+    if (!live_ok || g.trace.empty() || e->golden.ninst >= (1ULL << 29)) return FI_OK;
+    std::vector<uint32_t> off, ev;
+    first_access_index(g.trace, rmask, wmask, off, ev);
+    HIPCHK(hipMalloc(&e->d_fw_off, 33 * 4));
+    HIPCHK(hipMalloc(&e->d_fw_ev, std::max<size_t>(ev.size(), 1) * 4));
+    HIPCHK(hipMemcpy(e->d_fw_off, off.data(), 33 * 4, hipMemcpyHostToDevice));
+    if (!ev.empty()) HIPCHK(hipMemcpy(e->d_fw_ev, ev.data(), ev.size() * 4, hipMemcpyHostToDevice));
+    e->fw_ok = true;
+    return FI_OK;
+}
+
+// Step 7: translate the golden basic blocks and build the trial kernel with
+// them (hipRTC); the static kernel stays the fallback.  Takes g.pre.
+static fi_status golden_translate(fi_engine *e, GoldenCapture &g, bool live_ok) {
     free_tx(e);
     if (e->cfg.flags & FI_CFG_NO_TRANSLATE) e->tx_status = "disabled (FI_CFG_NO_TRANSLATE)";
     else if (!e->pre_ok) e->tx_status = "golden run rewrites its text";
-    else if (!live_ok || trace.empty()) e->tx_status = "golden trace unavailable";
+    else if (!live_ok || g.trace.empty()) e->tx_status = "golden trace unavailable";
     else {
         // (snapshot pcs are not leaders: they fall all over the hot loops and
         // would cut the blocks into single instructions; a wave that starts
@@ -1408,11 +1385,11 @@ fi_status fi_golden_run(fi_engine *e, fi_golden_info *out) {
         std::vector<LoopEst> loops;
         uint32_t n_tx = 0;
         const bool ahead = !(e->cfg.flags & FI_CFG_NO_LOAD_AHEAD);   // (part of the text, which keys the code-object caches)
-        std::string body = translate_blocks(pre, e->text_lo, trace, pcs, leaders, n_tx, true, &loops, ahead);
+        std::string body = translate_blocks(g.pre, e->text_lo, g.trace, pcs, leaders, n_tx, true, &loops, ahead);
         if (n_tx > 24000) {   // the odd-pc streams make it too large: without them
             leaders.clear();
             loops.clear();
-            body = translate_blocks(pre, e->text_lo, trace, pcs, leaders, n_tx, false, &loops, ahead);
+            body = translate_blocks(g.pre, e->text_lo, g.trace, pcs, leaders, n_tx, false, &loops, ahead);
         }
         if (!loops.empty() && !(e->cfg.flags & FI_CFG_NO_LOOP_ORDER)) {
             HIPCHK(hipMalloc(&e->d_loops, loops.size() * sizeof(LoopEst)));
@@ -1435,8 +1412,8 @@ fi_status fi_golden_run(fi_engine *e, fi_golden_info *out) {
             j->arch = prop.gcnArchName;
             j->odd = jit_has_odd(body);
             j->use_cache = !(e->cfg.flags & FI_CFG_JIT_NO_CACHE);
-            for (uint32_t h : leaders) pre[h & 0x7FFFFFFFu].flags |= (h >> 31) ? kPreOddLeader : kPreLeader;
-            e->jit_pre = std::move(pre);
+            for (uint32_t h : leaders) g.pre[h & 0x7FFFFFFFu].flags |= (h >> 31) ? kPreOddLeader : kPreLeader;
+            e->jit_pre = std::move(g.pre);
             e->jit_blocks = leaders.size();
             e->jit_insts = n_tx;
             e->jit = j;
@@ -1444,9 +1421,50 @@ fi_status fi_golden_run(fi_engine *e, fi_golden_info *out) {
             e->jit_threads.emplace_back(std::thread(jit_job_run, j), j);
         }
     }
+    return FI_OK;
+}
+
+fi_status fi_golden_run(fi_engine *e, fi_golden_info *out) {
+    if (!e) return FI_E_ARG;
+    if (!e->loaded) return fail(e, FI_E_STATE, "fi_golden_run: no workload loaded");
+    HIPCHK(hipSetDevice(e->dev));
+    fi_status st = ensure_work(e, 64);
+    if (st) return st;
+    st = golden_reset(e);
+    if (st) return st;
+
+    fi_outcome o;
+    uint64_t gpages = 0;
+    double golden_ms = 0;
+    GoldenCapture g;
+    {
+        DevBuf<uint8_t> rec_out, rec_err;   // both passes record into them; pass 2 releases them
+        st = golden_pass1(e, rec_out, rec_err, o, gpages);
+        if (st) return st;
+        golden_ms = e->last_ms;
+        st = golden_pass2(e, o, gpages, rec_out, rec_err, g);
+        if (st) return st;
+    }
+    if (g.o.ninst != o.ninst || g.o.detail != o.detail || g.n_snaps != o.ninst / g.I + 1)
+        return fail(e, FI_E_GOLDEN, "golden capture pass diverged from the golden run");
+
+    golden_snap_tables(e, g);
+    std::vector<uint32_t> rmask, wmask;
+    const bool live_ok = golden_liveness(e, g, rmask, wmask);
+    st = golden_first_access(e, g, live_ok, rmask, wmask);
+    if (st) return st;
+    st = upload_snaps(e);
+    if (st) return st;
+    st = build_mem_index(e, g.mev, live_ok && g.mem_ok);
+    if (st) return st;
+    e->golden_unmapped = g.unmapped;
+    tick_prepare(e, g.mev, !g.trace.empty() && g.mem_ok);
+    st = golden_translate(e, g, live_ok);
+    if (st) return st;
+
     e->last_ms = golden_ms;
     e->golden.snapshots = e->snaps.size();
-    e->golden.snapshot_interval = I;
+    e->golden.snapshot_interval = g.I;
     e->golden.snapshot_frames = e->pool.size() / kPage;
     e->have_golden = true;
     if (e->issue_on) {   // the model follows the new golden run
@@ -1675,7 +1693,7 @@ static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *
     if (P != e->cfg.private_pages) c.ov_blocks = 0;   // the second pass has its own P' (chunk_end)
     if (c.ov_blocks) HIPCHK(hipMemsetAsync(e->d_ov_next, 0, 4, st));
     HIPCHK(hipMemsetAsync(e->d_cnt, 0, 16 * 4, st));
-    HIPCHK(hipMemsetAsync(e->d_wave_dbg, 0, k * 10 * sizeof(uint64_t), st));
+    HIPCHK(hipMemsetAsync(e->d_wave_dbg, 0, k * kWaveDbgWords * sizeof(uint64_t), st));
     const bool pack = (e->cfg.flags & FI_CFG_PACK_RUNS) != 0;
     int n_cu = 0;
     HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, e->dev));
@@ -2382,7 +2400,7 @@ fi_status fi_debug_waves(fi_engine *e, uint64_t *out, uint64_t n_waves) {
     if (!e || !out) return FI_E_ARG;
     if (n_waves > e->cap) return fail(e, FI_E_ARG, "more waves than the work buffers hold");
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(out, e->d_wave_dbg, n_waves * 10 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, e->d_wave_dbg, n_waves * kWaveDbgWords * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return FI_OK;
 }
 
@@ -2450,6 +2468,16 @@ fi_status fi_debug_translation(fi_engine *e, char *buf, uint64_t cap, uint64_t *
     }
     if (len) *len = e->tx_body.size();
     return FI_OK;
+}
+
+const char *fi_debug_stat_name(uint32_t slot) {
+    switch (slot) {
+#define FI_STAT_NAME(name, idx, what) \
+    case idx: return #name;
+        FI_STAT_SLOTS(FI_STAT_NAME)
+#undef FI_STAT_NAME
+    }
+    return nullptr;
 }
 
 fi_status fi_debug_stats(fi_engine *e, uint64_t *out64) {
@@ -2528,16 +2556,14 @@ fi_status fi_debug_dispatch_kinds(fi_engine *e, uint32_t *kinds, uint32_t cap, u
 fi_status fi_debug_decode(fi_engine *e, const uint32_t *raws, uint64_t n, void *out16) {
     if (!e || !raws || !out16) return FI_E_ARG;
     HIPCHK(hipSetDevice(e->dev));
-    uint32_t *d_raw = nullptr;
-    PreInst *d_o = nullptr;
-    HIPCHK(hipMalloc(&d_raw, n * 4));
-    HIPCHK(hipMalloc(&d_o, n * sizeof(PreInst)));
-    HIPCHK(hipMemcpy(d_raw, raws, n * 4, hipMemcpyHostToDevice));
-    HIPCHK(launch_debug_decode(d_raw, n, d_o, e->stream));
+    DevBuf<uint32_t> d_raw;
+    DevBuf<PreInst> d_o;
+    HIPCHK(d_raw.alloc(n));
+    HIPCHK(d_o.alloc(n));
+    HIPCHK(hipMemcpy(d_raw.get(), raws, n * 4, hipMemcpyHostToDevice));
+    HIPCHK(launch_debug_decode(d_raw.get(), n, d_o.get(), e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(out16, d_o, n * sizeof(PreInst), hipMemcpyDeviceToHost));
-    (void)hipFree(d_raw);
-    (void)hipFree(d_o);
+    HIPCHK(hipMemcpy(out16, d_o.get(), n * sizeof(PreInst), hipMemcpyDeviceToHost));
     return FI_OK;
 }
 
@@ -2546,17 +2572,15 @@ fi_status fi_debug_loop_outcome(fi_engine *e, const fi_debug_loop *in, uint64_t 
     if (e->snaps.empty()) return fail(e, FI_E_STATE, "fi_debug_loop_outcome: fi_golden_run first");
     if (!n) return FI_OK;
     HIPCHK(hipSetDevice(e->dev));
-    fi_debug_loop *d_in = nullptr;
-    fi_debug_loop_out *d_out = nullptr;
-    HIPCHK(hipMalloc(&d_in, n * sizeof *in));
-    HIPCHK(hipMalloc(&d_out, n * sizeof *out));
-    HIPCHK(hipMemcpy(d_in, in, n * sizeof *in, hipMemcpyHostToDevice));
+    DevBuf<fi_debug_loop> d_in;
+    DevBuf<fi_debug_loop_out> d_out;
+    HIPCHK(d_in.alloc(n));
+    HIPCHK(d_out.alloc(n));
+    HIPCHK(hipMemcpy(d_in.get(), in, n * sizeof *in, hipMemcpyHostToDevice));
     DevCtx c = base_ctx(e);
-    HIPCHK(launch_debug_loop(c, d_in, n, d_out, e->stream));
+    HIPCHK(launch_debug_loop(c, d_in.get(), n, d_out.get(), e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(out, d_out, n * sizeof *out, hipMemcpyDeviceToHost));
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
+    HIPCHK(hipMemcpy(out, d_out.get(), n * sizeof *out, hipMemcpyDeviceToHost));
     return FI_OK;
 }
 

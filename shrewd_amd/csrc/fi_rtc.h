@@ -11,7 +11,9 @@ typedef unsigned long uintptr_t;
 #ifndef INT32_MIN
 #define INT32_MIN (-2147483647 - 1)
 #endif
-#else
+#elif defined(__HIPCC__) || defined(__HIP_PLATFORM_AMD__)
 #include <hip/hip_runtime.h>
+#include <stdint.h>
+#else   // a plain host program (fi_golden_host.h's check): the structures alone
 #include <stdint.h>
 #endif

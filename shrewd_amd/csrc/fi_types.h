@@ -128,9 +128,107 @@ struct FwdCtx {
     uint64_t text_lo, text_hi;
 };
 
+// DevCtx::stats: the engine's counters and flags, X(name, slot, what it
+// holds).  The one key to the array: the enum below (ST_<name>), the names
+// fi_debug_stat_name returns and through it shrewd_amd.STAT all come from this
+// table.  The numbers are fixed: bench.py and the dumps under profiles/ read
+// slots by number.  Slots 28, 29, 31 and 63 are free.
+#define FI_STAT_SLOTS(X)                                                                                   \
+    X(FETCH_BYTES, 0, "instruction-fetch bytes")                                                           \
+    X(DATA_BYTES, 1, "data-access bytes")                                                                  \
+    X(PAGES, 2, "private (copy-on-write) pages taken")                                                     \
+    X(GOLDEN_NCYCLES, 3, "record mode: the golden run's cycles")                                           \
+    X(GOLDEN_OUT_LEN, 4, "record mode: bytes the golden run wrote to stdout")                              \
+    X(GOLDEN_ERR_LEN, 5, "record mode: bytes the golden run wrote to stderr")                              \
+    X(LOOP_ITERS, 6, "trial-loop iterations, summed over the waves")                                       \
+    X(LANE_INSTS, 7, "lane-instructions")                                                                  \
+    X(SLOW_FETCHES, 8, "slow fetches")                                                                     \
+    X(MIN_PC, 9, "min-PC reductions (solo kernels: loop trips)")                                           \
+    X(MAX_WAVE_ITERS, 10, "most loop iterations of one wave")                                              \
+    X(EARLY_CHECKS, 11, "early-exit checks (comparisons with a snapshot)")                                 \
+    X(EARLY_EXITS, 12, "early exits")                                                                      \
+    X(SNAPS_CAPTURED, 13, "record mode: snapshots captured")                                               \
+    X(START_INST_SUM, 14, "sum of the waves' start numInst (the golden prefix skipped)")                   \
+    X(TRACE_EVENTS, 15, "record mode: golden trace events")                                                \
+    X(TX_INSTS, 16, "instructions run in translated code")                                                 \
+    X(TX_ENTRIES, 17, "entries into translated code")                                                      \
+    X(SLOWEST_WAVE_TX, 18, "slowest wave: iters << 32 | tx permille << 20 | tx entries")                   \
+    X(SLOWEST_WAVE_SLOW, 19, "slowest wave: iters << 32 | slow fetches")                                   \
+    X(WAVE0_MEMTIME, 20, "wave 0: s_memtime delta over the dispatch")                                      \
+    X(WAVE0_REALTIME, 21, "wave 0: s_memrealtime delta over the dispatch")                                 \
+    X(GOLDEN_EXTRA_STATE, 22, "record mode: the golden run holds state outside the snapshots (FP, LR/SC, VM)") \
+    X(DEVICE_INSTS, 23, "instructions executed on the device")                                             \
+    X(SIMT_LANE_INSTS, 24, "lane-instructions of the diverged-lanes step loop")                            \
+    X(MEM_EVENTS, 25, "record mode: golden data-access events")                                            \
+    X(MEM_DEAD, 26, "memory faults ended at injection (dead word)")                                        \
+    X(REG_DEAD, 27, "register faults dead at injection")                                                   \
+    X(REDO_TRIALS, 30, "trials re-run with more private pages (FI_ESC_RESOURCE, fi_engine.cpp run_chunk)") \
+    X(PROF_PHASE0, 32, "FI_PROF build: cycles up to PSTAMP(0)")                                            \
+    X(PROF_PHASE1, 33, "FI_PROF build: cycles up to PSTAMP(1)")                                            \
+    X(PROF_PHASE2, 34, "FI_PROF build: cycles up to PSTAMP(2)")                                            \
+    X(PROF_PHASE3, 35, "FI_PROF build: cycles up to PSTAMP(3)")                                            \
+    X(PROF_PHASE4, 36, "FI_PROF build: cycles up to PSTAMP(4)")                                            \
+    X(PROF_PHASE5, 37, "FI_PROF build: cycles up to PSTAMP(5)")                                            \
+    X(PROF_PHASE6, 38, "FI_PROF build: cycles up to PSTAMP(6)")                                            \
+    X(PROF_PHASE7, 39, "FI_PROF build: cycles up to PSTAMP(7)")                                            \
+    X(K64_FETCH_BYTES, 40, "64-lane kernel: instruction-fetch bytes")                                      \
+    X(K64_DATA_BYTES, 41, "64-lane kernel: data-access bytes")                                             \
+    X(K64_PAGES, 42, "64-lane kernel: private pages taken")                                                \
+    X(K64_DEVICE_INSTS, 43, "64-lane kernel: instructions executed")                                       \
+    X(SOLO_FETCH_BYTES, 44, "solo kernel: instruction-fetch bytes")                                        \
+    X(SOLO_DATA_BYTES, 45, "solo kernel: data-access bytes")                                               \
+    X(SOLO_PAGES, 46, "solo kernel: private pages taken")                                                  \
+    X(SOLO_DEVICE_INSTS, 47, "solo kernel: instructions executed")                                         \
+    X(SOLO_ODD_FETCH_BYTES, 48, "solo-odd kernel: instruction-fetch bytes")                                \
+    X(SOLO_ODD_DATA_BYTES, 49, "solo-odd kernel: data-access bytes")                                       \
+    X(SOLO_ODD_PAGES, 50, "solo-odd kernel: private pages taken")                                          \
+    X(SOLO_ODD_DEVICE_INSTS, 51, "solo-odd kernel: instructions executed")                                 \
+    X(CLK_UNTIL, 52, "record mode: 1 + numInst of the golden run's last curTick read")                     \
+    X(FAST_RUNS, 53, "solo_fast_run calls")                                                                \
+    X(FAST_INSTS, 54, "instructions the solo_fast_run calls ran")                                          \
+    X(FAST_BACKS, 55, "solo_fast_run hand-backs")                                                          \
+    X(LOOP_HANGS, 56, "hangs proved by the clean body's counted-loop test")                                \
+    X(LOOP_PGFAULTS, 57, "page-fault crashes proved in run-off loops")                                     \
+    X(LOOP_UNDECIDED, 58, "loop proofs undecided")                                                         \
+    X(LP_COMMIT, 59, "hangs proved by the interpreter's loop probe (lp_commit)")                           \
+    X(LP_FAIL, 60, "loop probes that failed and backed off (lp_fail)")                                     \
+    X(OV_BLOCKS, 61, "overflow page blocks taken from the pool (priv_room_ool)")                           \
+    X(GOLDEN_UNMAPPED, 62, "record mode: the golden run unmapped memory (munmap, brk shrink)")
+
+constexpr int kNStats = 64;          // DevCtx::stats entries
+enum Stat : int {
+#define FI_STAT_ENUM(name, idx, what) ST_##name = idx,
+    FI_STAT_SLOTS(FI_STAT_ENUM)
+#undef FI_STAT_ENUM
+};
+// The FI_PROF accumulators are ST_PROF_PHASE0 + k; a kernel's own traffic
+// counters are stat_kernel(k, off): k = 0 the 64-lane kernel, 1 solo,
+// 2 solo-odd; off = kStK*.
+constexpr int kStKernelStride = 4;
+constexpr int kStKFetch = 0, kStKData = 1, kStKPages = 2, kStKInsts = 3;
+constexpr int stat_kernel(int k, int off) { return ST_K64_FETCH_BYTES + kStKernelStride * k + off; }
+static_assert(stat_kernel(1, kStKFetch) == ST_SOLO_FETCH_BYTES && stat_kernel(2, kStKInsts) == ST_SOLO_ODD_DEVICE_INSTS &&
+                  stat_kernel(0, kStKData) == ST_K64_DATA_BYTES && stat_kernel(0, kStKPages) == ST_K64_PAGES,
+              "the per-kernel group is base + 4 * kernel + offset");
+static_assert(ST_PROF_PHASE7 == ST_PROF_PHASE0 + 7, "FI_PROF phases are consecutive");
+
+// One record of DevCtx::wave_dbg: kWaveDbgWords u64 per wave.
+enum WaveDbg : int {
+    WD_CYCLES = 0,        // s_memtime cycles of the wave
+    WD_ITERS,             // loop iterations
+    WD_TX_INSTS,          // translated instructions
+    WD_SLOW_MINPC,        // slow fetches | min-PC reductions << 32 (solo: loop trips)
+    WD_RT_START,          // s_memrealtime (100 MHz) at the wave's start
+    WD_RT_END,            //   and at its end
+    WD_TRIAL,             // lane 0's trial (index into the sites; ~0 = none)
+    WD_TRIAL_INSTS,       // lane 0's instructions in this dispatch
+    WD_TX_ENTRIES,        // translated-code entries
+    WD_PAGE_LOOKUPS,      // lane 0's full page-table lookups
+    kWaveDbgWords
+};
+
 // Everything one launch of the trial kernel needs.  Passed by value as the
 // kernel argument (lives in the kernarg segment -> scalar loads).
-constexpr int kNStats = 64;          // DevCtx::stats entries
 
 struct DevCtx {
     // golden text, pre-decoded (pre_ok = 0 if the golden run rewrote its text)
@@ -212,9 +310,7 @@ struct DevCtx {
     const uint32_t *perm;            // launch slot -> index into sites/out (sorted by site.inst)
     fi_outcome *out;
     uint64_t n;                      // trials in this launch
-    uint64_t *wave_dbg;              // per wave: {s_memtime cycles, loop iterations, translated insts, slow fetches,
-                                     //            s_memrealtime at start, at end, lane 0's trial, its instructions,
-                                     //            translated entries, lane 0's full page lookups}
+    uint64_t *wave_dbg;              // per wave: one record of kWaveDbgWords u64 (WaveDbg)
     // SE memory map: process-start brk and "stack" VMA; per-slot VM state
     uint64_t brk0, svma_lo, svma_hi;
     VmState *vm;                     // [n_slots]
@@ -249,26 +345,7 @@ struct DevCtx {
     const uint64_t *mw_addr;         // [mw_n] sorted 8-byte-aligned addresses the golden run accesses
     const uint32_t *mw_off;          // [mw_n + 1] each word's events in mw_ev
     const uint64_t *mw_ev;           // per word in time order: numInst << 16 | bytes read << 8 | bytes written
-    unsigned long long *stats;     // [0] fetch B [1] data B [2] pages [3..5] golden ncycles/out/err
-                                     // [6] loop iterations [7] lane-insts [8] slow fetches [9] min-PC [10] max iter/wave
-                                     // [11] early-exit checks [12] early exits [13] snapshots captured [14] start-inst sum
-                                     // [15] golden trace events [16] translated insts [17] translated entries
-                                     // [18] slowest wave: iters<<32 | tx permille<<20 | entries [19] iters<<32 | slow
-                                     // [20] wave-0 s_memtime delta [21] s_memrealtime delta
-                                     // [22] golden run holds state outside the snapshots (FP, LR/SC, VM)
-                                     // [23] instructions executed on the device
-                                     // [24] lane-instructions of the diverged-lanes step loop
-                                     // [25] golden data-access events [26] memory faults ended at injection
-                                     // [27] register faults dead at injection [30] trials re-run with more private
-                                     // pages (FI_ESC_RESOURCE, fi_engine.cpp run_chunk)
-                                     // [52] record mode: 1 + numInst of the golden run's last curTick read
-                                     // [62] record mode: the golden run unmapped memory (munmap, brk shrink)
-                                     // [53] solo_fast_run calls [54] instructions they ran [55] hand-backs
-                                     // [56] hangs proved by the clean body's counted-loop test
-                                     // [57] page-fault crashes proved in run-off loops [58] loop proofs undecided
-                                     // [32..39] FI_PROF phase cycles
-                                     // [40 + 4k + {0,1,2,3}] fetch B, data B, pages, device insts of kernel k
-                                     // (0 the 64-lane kernel, 1 solo, 2 solo-odd)
+    unsigned long long *stats;       // [kNStats] counters and flags, one per slot of FI_STAT_SLOTS above
     // output capture (fi_run_sites_capture; cap_bytes 0 = off): each trial of the chunk
     // owns one row of cap_stride bytes in cap_out / cap_err, preset to the golden streams
     // (fi_capture_init_kernel); write() stores its bytes over them and the lane that ends a trial its

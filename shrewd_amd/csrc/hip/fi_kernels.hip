@@ -374,7 +374,7 @@ __global__ void fi_redo_collect_kernel(const fi_outcome *out, uint64_t n, uint32
     const fi_outcome o = out[i];
     if (o.cls == FI_ESCAPE && o.sub == FI_ESC_RESOURCE && o.exit_code == 0) {
         idx[atomicAdd(cnt, 1u)] = (uint32_t)i;
-        atomicAdd(&stats[30], 1ull);
+        atomicAdd(&stats[ST_REDO_TRIALS], 1ull);
     }
 }
 __global__ void fi_redo_gather_kernel(const fi_site *sites, const uint32_t *idx, uint64_t n, fi_site *rsites,
@@ -441,10 +441,10 @@ __global__ void __launch_bounds__(256) fi_capture_finish_kernel(uint8_t *rows, u
 
 __global__ void fi_hist_stats_kernel(const unsigned long long *stats, fi_histogram *h) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
-        h->fetch_bytes += stats[0];
-        h->data_bytes += stats[1];
-        h->cow_pages += stats[2];
-        h->device_insts += stats[23];
+        h->fetch_bytes += stats[ST_FETCH_BYTES];
+        h->data_bytes += stats[ST_DATA_BYTES];
+        h->cow_pages += stats[ST_PAGES];
+        h->device_insts += stats[ST_DEVICE_INSTS];
     }
 }
 

@@ -292,7 +292,7 @@ __device__ __noinline__ bool priv_room_ool(KCtx *c, uint64_t slot, uint32_t i) {
         const uint32_t b = atomicAdd(c->ov_next, 1u);
         if (b >= c->ov_blocks) return false;
         c->ov_of[slot] = b;
-        atomicAdd(&c->stats[61], 1ull);   // (blocks taken: diagnostics)
+        atomicAdd(&c->stats[ST_OV_BLOCKS], 1ull);   // (blocks taken: diagnostics)
     }
     return true;
 }
@@ -396,7 +396,7 @@ __device__ VmState *vm_of(KCtx *c, LaneMem &m, uint64_t slot) {
             v->vma[0][0] = c->svma_lo; v->vma[0][1] = c->svma_hi;                 // argsInit's "stack" VMA
         }
         m.vm = true;
-        if (c->record) c->stats[22] = 1;   // the golden VM state is not in the snapshots
+        if (c->record) c->stats[ST_GOLDEN_EXTRA_STATE] = 1;   // the golden VM state is not in the snapshots
     }
     return v;
 }
@@ -469,7 +469,7 @@ __device__ bool vm_add(VmState *v, uint64_t lo, uint64_t hi) {
 // stack page gets one).  0 ok, 1 no private page left, 2 the VMA list is full
 // (resource escapes; exit code kEscTable for the latter, vm_esc).
 __device__ int vm_unmap(KCtx *c, const WaveMem &w, LaneMem &m, uint64_t slot, VmState *v, uint64_t lo, uint64_t hi) {
-    if (c->record) c->stats[62] = 1;   // frames freed: the tick model's frame order no longer holds
+    if (c->record) c->stats[ST_GOLDEN_UNMAPPED] = 1;   // frames freed: the tick model's frame order no longer holds
     const uint32_t n = v->nvma;
     for (uint32_t i = 0; i < n; i++) {
         const uint64_t a = v->vma[i][0], b = v->vma[i][1];
@@ -981,7 +981,7 @@ __device__ __forceinline__ void rec_mem(KCtx *c, uint64_t a, uint64_t n, uint64_
 #ifndef FI_TX
     while (n && kind) {
         const uint64_t k = n < (1u << 29) ? n : (1u << 29);
-        const unsigned long long i = atomicAdd(&c->stats[25], 1ull);
+        const unsigned long long i = atomicAdd(&c->stats[ST_MEM_EVENTS], 1ull);
         if (i < c->rec_mem_cap) {
             MemEv ev;
             ev.addr = a; ev.t = (uint32_t)t; ev.len_kind = (uint32_t)k | (kind << 30);
@@ -1268,7 +1268,7 @@ __device__ __noinline__ bool do_syscall(KCtx *c, WaveMem w, Lane &L, LaneMem &m,
         if (!a1) { finish(L, FI_CRASH, FI_CRASH_SE_PANIC, 134, pc32); return false; }
         if (!proxy_readable(c, w, m, slot, a1, 16)) { finish(L, FI_CRASH, FI_CRASH_PROXY, 1, pc32); return false; }
         const uint64_t ns = (c->tick0 + (L.ncyc - 1) * c->clk_period) / 1000;
-        if (c->record) c->stats[52] = L.ninst + 1;   // the golden future reads curTick up to here
+        if (c->record) c->stats[ST_CLK_UNTIL] = L.ninst + 1;   // the golden future reads curTick up to here
         const uint64_t sec = ns / 1000000000ULL + 1000000000ULL, nsec = ns % 1000000000ULL;
         char b[16];
         for (int k = 0; k < 8; k++) { b[k] = (char)(sec >> (8 * k)); b[8 + k] = (char)(nsec >> (8 * k)); }
@@ -1662,7 +1662,7 @@ __device__ __forceinline__ bool tx_probe(const LaneMem &m, uint64_t ea, uint32_t
 
 // ------------------------------------------------------------------ trial kernel
 // Diagnostic build only (-DFI_PROF): s_memtime stamps at the phase boundaries
-// of the fast loop, summed per wave into stats[24..27] (never in the shipped
+// of the fast loop, summed per wave into stats[ST_PROF_PHASE0 + k] (never in the shipped
 // library; a stamp waits for outstanding scalar/LDS loads, so it also shows
 // which phase absorbs those waits).
 #ifdef FI_PROF
@@ -2195,7 +2195,7 @@ __device__ __noinline__ bool lp_prove(const lds_lp *P, const uint64_t *xe, const
 __device__ __noinline__ void lp_fail(lds_lp *P, KCtx *c) {
     P->on = 0; P->cnt = 0;
     P->at = P->at < (1u << 30) ? 2 * P->at : P->at;
-    atomicAdd(&c->stats[60], 1ull);
+    atomicAdd(&c->stats[ST_LP_FAIL], 1ull);
 }
 __device__ __noinline__ void lp_window(lds_lp *P, KCtx *c, const lds_u64 *R, uint64_t slot, uint64_t pc, bool fp) {
     if (++P->tries > 4) { lp_fail(P, c); return; }
@@ -2234,7 +2234,7 @@ __device__ __noinline__ uint32_t lp_commit(lds_lp *P, KCtx *c, const lds_u64 *R,
     if (pc != P->pc0) return 0;
     if (lp_prove(P, (const uint64_t *)R, c->fregs + slot, c->n_slots, fp)) {
         P->on = 0;
-        atomicAdd(&c->stats[59], 1ull);
+        atomicAdd(&c->stats[ST_LP_COMMIT], 1ull);
         return 1;
     }
     lp_fail(P, c);
@@ -3539,7 +3539,7 @@ __device__ __noinline__ void solo_pre_run(KCtx *CX, lds_u64 *R, lds_mem *mp, lds
     }
     uint64_t spc = uni64(io->spc);
     uint32_t steps = 0, xticks = 0, fbytes = 0, dbytes = 0;
-    uint32_t n_fast = 0, n_fast_steps = 0, n_fast_back = 0;   // diagnostics: stats[53..55]
+    uint32_t n_fast = 0, n_fast_steps = 0, n_fast_back = 0;   // diagnostics: ST_FAST_*
 #ifdef FI_PROF   // phases: fetch (+ decode of rewritten code), operands, execute, commit
     uint64_t pacc[4] = {0, 0, 0, 0}, plast = __builtin_amdgcn_s_memtime();
 #define PST(k)                                                  \
@@ -3793,9 +3793,9 @@ __device__ __noinline__ void solo_pre_run(KCtx *CX, lds_u64 *R, lds_mem *mp, lds
     }
 leave:
     if (n_fast) {
-        atomicAdd(&CX->stats[53], (unsigned long long)n_fast);
-        atomicAdd(&CX->stats[54], (unsigned long long)n_fast_steps);
-        atomicAdd(&CX->stats[55], (unsigned long long)n_fast_back);
+        atomicAdd(&CX->stats[ST_FAST_RUNS], (unsigned long long)n_fast);
+        atomicAdd(&CX->stats[ST_FAST_INSTS], (unsigned long long)n_fast_steps);
+        atomicAdd(&CX->stats[ST_FAST_BACKS], (unsigned long long)n_fast_back);
     }
     io->spc = spc; io->watch = watch;
     io->steps = steps; io->xticks = xticks; io->fbytes = fbytes; io->dbytes = dbytes;
@@ -3963,7 +3963,7 @@ __device__ __forceinline__ void trial_body() {
         for (int r = 0; r < 32; r++) CX->fregs[(uint64_t)r * CX->n_slots + slot] = CX->fp0[r];
         L.fp = true;
         L.fflags = (uint8_t)(CX->fcsr0 & 0x1F); L.frm = (uint8_t)((CX->fcsr0 >> 5) & 7);
-        if (CX->record) CX->stats[22] = 1;   // FP state outside the snapshots (host disables snapshot starts)
+        if (CX->record) CX->stats[ST_GOLDEN_EXTRA_STATE] = 1;   // FP state outside the snapshots (host disables snapshot starts)
     }
     if (resume && live) {
         L.pc = SV->pc; L.ninst = SV->ninst; L.ncyc = SV->ncyc; L.out_pos = SV->out_pos; L.err_pos = SV->err_pos;
@@ -3984,7 +3984,7 @@ __device__ __forceinline__ void trial_body() {
         L.injected = 1;
         finish(L, FI_MASKED, (int)CX->gsub, (int)CX->gexit, CX->gdetail);
         L.res.ninst = CX->gninst;
-        if (kSoloOnce) atomicAdd(&CX->stats[27], 1ull);
+        if (kSoloOnce) atomicAdd(&CX->stats[ST_REG_DEAD], 1ull);
     }
     bool suspended = false;
     const uint64_t start_inst = (live && !resume) ? L.ninst : 0;
@@ -4149,13 +4149,13 @@ __device__ __forceinline__ void trial_body() {
                     if (CX->mem_live) {   // ... so the trial is the golden run
                         finish(L, FI_MASKED, (int)CX->gsub, (int)CX->gexit, CX->gdetail);
                         L.res.ninst = CX->gninst;
-                        if (kSoloOnce) atomicAdd(&CX->stats[26], 1ull);
+                        if (kSoloOnce) atomicAdd(&CX->stats[ST_MEM_DEAD], 1ull);
                     }
                 } else if (CX->mem_live && mem_dead(CX, s.addr, s.mask, L.ninst)) {
                     L.injected = 1;
                     finish(L, FI_MASKED, (int)CX->gsub, (int)CX->gexit, CX->gdetail);
                     L.res.ninst = CX->gninst;
-                    if (kSoloOnce) atomicAdd(&CX->stats[26], 1ull);
+                    if (kSoloOnce) atomicAdd(&CX->stats[ST_MEM_DEAD], 1ull);
                 } else if (!(p & 1)) {
                     m.req_vpn = s.addr >> 12; m.req_src = page_of(p);   // copy-on-write first, flip next iteration
                 } else {
@@ -4487,15 +4487,15 @@ __device__ __forceinline__ void trial_body() {
                             proved_skip = left;
                             L.ninst += left;
                             finish(L, FI_HANG, 1, 0, 0u);
-                            atomicAdd(&CX->stats[56], 1ull);
+                            atomicAdd(&CX->stats[ST_LOOP_HANGS], 1ull);
                         } else if (r == 2) {   // a proved page fault kf instructions on
                             proved_skip = kf;
                             L.ninst += kf;
                             finish(L, FI_CRASH, FI_CRASH_PAGE_FAULT, 134, (uint32_t)fva);
-                            atomicAdd(&CX->stats[57], 1ull);
+                            atomicAdd(&CX->stats[ST_LOOP_PGFAULTS], 1ull);
                         } else {   // undecided: the trial runs on, without asking again
                             no_proof = true;
-                            atomicAdd(&CX->stats[58], 1ull);
+                            atomicAdd(&CX->stats[ST_LOOP_UNDECIDED], 1ull);
                         }
                         continue;
                     }
@@ -5207,12 +5207,12 @@ __device__ __forceinline__ void trial_body() {
             case OP_lr_w: case OP_lr_d:
                 msz = d.op == OP_lr_w ? 4 : 8; mext = msz == 4 ? 32 : 0; llsc = 1;
                 xticks = ((d.raw >> 25) & 1) + ((d.raw >> 26) & 1);
-                if (CX->record) CX->stats[22] = 1;   // golden LR/SC state is not in the snapshots
+                if (CX->record) CX->stats[ST_GOLDEN_EXTRA_STATE] = 1;   // golden LR/SC state is not in the snapshots
                 break;
             case OP_sc_w: case OP_sc_d:
                 msz = d.op == OP_sc_w ? 4 : 8; llsc = 2;
                 xticks = ((d.raw >> 25) & 1) + ((d.raw >> 26) & 1);
-                if (CX->record) CX->stats[22] = 1;
+                if (CX->record) CX->stats[ST_GOLDEN_EXTRA_STATE] = 1;
                 break;
             // ---- privileged SYSTEM / hypervisor load-store from PRV_U, cache-block
             // ops, M5 pseudo-ops, scalar crypto (oracle/rv64se.c refine_misc, execute)
@@ -5226,7 +5226,7 @@ __device__ __forceinline__ void trial_body() {
                 case 0x07:
                     if (CX->clk_esc) { f = F_TKCLOCK; break; }
                     v = (CX->tick0 + (L.ncyc + ticks - 1) * CX->clk_period) / 1000;
-                    if (CX->record) CX->stats[52] = L.ninst + 1;
+                    if (CX->record) CX->stats[ST_CLK_UNTIL] = L.ninst + 1;
                     break;
                 case 0x23:   // m5sum(a0..a5)
                     xdet = L.watch >= 10 && L.watch <= 15;
@@ -5368,7 +5368,7 @@ __device__ __forceinline__ void trial_body() {
                 if (!L.fp) {
                     for (int r = 0; r < 32; r++) CX->fregs[(uint64_t)r * CX->n_slots + slot] = 0;
                     L.fp = true;
-                    if (CX->record) CX->stats[22] = 1;   // the golden run uses FP state (host disables snapshots)
+                    if (CX->record) CX->stats[ST_GOLDEN_EXTRA_STATE] = 1;   // the golden run uses FP state (host disables snapshots)
                 }
                 if (fbox) CX->fregs[(uint64_t)d.rd * CX->n_slots + slot] = fval;
                 if (fpst & 0x100u) L.fflags |= (uint8_t)(fpst & 0x1F);       // FFLAGS_EXE: accumulate
@@ -5377,7 +5377,7 @@ __device__ __forceinline__ void trial_body() {
             L.ncyc += xticks;
             if (nvcfg != ~0u) {
                 m.vcfg = nvcfg;
-                if (CX->record && nvcfg) CX->stats[22] = 1;   // golden vector state is not in the snapshots
+                if (CX->record && nvcfg) CX->stats[ST_GOLDEN_EXTRA_STATE] = 1;   // golden vector state is not in the snapshots
             }
             bool rdet = false;
             if (L.injected == 3) {   // result fault (oracle/rv64se.c:result_fault)
@@ -5501,28 +5501,28 @@ __device__ __forceinline__ void trial_body() {
     // of it is held in registers across the loop)
     if (live && !suspended) capture_lens(opq(kc), sidx, L.res.ninst, L.ninst, L.out_pos, L.err_pos);
     if (CX->record && live) {
-        CX->stats[3] = L.ncyc;
-        CX->stats[4] = L.out_pos;
-        CX->stats[5] = L.err_pos;
-        CX->stats[13] = snaps_taken;
-        CX->stats[15] = tpos;
+        CX->stats[ST_GOLDEN_NCYCLES] = L.ncyc;
+        CX->stats[ST_GOLDEN_OUT_LEN] = L.out_pos;
+        CX->stats[ST_GOLDEN_ERR_LEN] = L.err_pos;
+        CX->stats[ST_SNAPS_CAPTURED] = snaps_taken;
+        CX->stats[ST_TRACE_EVENTS] = tpos;
     }
 #ifdef FI_PROF
     if (lane == 0 && kSoloOnce)
-        for (int k = 0; k < 8; k++) atomicAdd(&CX->stats[32 + k], (unsigned long long)pacc[k]);
+        for (int k = 0; k < 8; k++) atomicAdd(&CX->stats[ST_PROF_PHASE0 + k], (unsigned long long)pacc[k]);
 #endif
     if (lane == 0 && CX->wave_dbg) {
-        uint64_t *wd = CX->wave_dbg + 10 * ((uint64_t)blockIdx.x + rlo);   // (solo-odd: after the solo entries)
-        wd[0] = __builtin_amdgcn_s_memtime() - t_start;
-        wd[1] = n_iter;
-        wd[2] = n_tx;
-        wd[3] = n_slow | ((uint64_t)n_min << 32);         // slow fetches | min-PC reductions (solo: loop trips)
-        wd[4] = rt_start;                                // s_memrealtime (100 MHz) at the wave's start / end
-        wd[5] = __builtin_amdgcn_s_memrealtime();
-        wd[6] = live ? (uint64_t)sidx : ~0ULL;           // lane 0's trial (index into the sites)
-        wd[7] = live ? L.ninst - launch_inst - proved_skip : 0;   // lane 0's instructions in this dispatch
-        wd[8] = n_txin;                                  // translated-code entries
-        wd[9] = m.nmiss;                                 // lane 0's full page-table lookups
+        uint64_t *wd = CX->wave_dbg + kWaveDbgWords * ((uint64_t)blockIdx.x + rlo);   // (solo-odd: after the solo entries)
+        wd[WD_CYCLES] = __builtin_amdgcn_s_memtime() - t_start;
+        wd[WD_ITERS] = n_iter;
+        wd[WD_TX_INSTS] = n_tx;
+        wd[WD_SLOW_MINPC] = n_slow | ((uint64_t)n_min << 32);
+        wd[WD_RT_START] = rt_start;
+        wd[WD_RT_END] = __builtin_amdgcn_s_memrealtime();
+        wd[WD_TRIAL] = live ? (uint64_t)sidx : ~0ULL;
+        wd[WD_TRIAL_INSTS] = live ? L.ninst - launch_inst - proved_skip : 0;
+        wd[WD_TX_ENTRIES] = n_txin;
+        wd[WD_PAGE_LOOKUPS] = m.nmiss;
     }
     // the dispatch's busy span: waves that ran a trial (a surplus wave of a
     // resume grid returned above; one lane's vector atomics)
@@ -5531,41 +5531,43 @@ __device__ __forceinline__ void trial_body() {
         atomicMax(&CX->span[1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
     }
     if (blockIdx.x == 0 && lane == 0) {
-        CX->stats[20] = __builtin_amdgcn_s_memtime() - t_start;
-        CX->stats[21] = __builtin_amdgcn_s_memrealtime() - rt_start;
+        CX->stats[ST_WAVE0_MEMTIME] = __builtin_amdgcn_s_memtime() - t_start;
+        CX->stats[ST_WAVE0_REALTIME] = __builtin_amdgcn_s_memrealtime() - rt_start;
     }
     if (CX->record) pages_made = m.n_priv;   // golden: every private entry (pages, tombstones)
     const uint64_t fb = wsum64<kNL>(L.fetch_b), db = wsum64<kNL>(L.data_b), pm = wsum64<kNL>(pages_made);
     const uint64_t si = wsum64<kNL>(start_inst);
     const uint64_t xi = wsum64<kNL>(live ? L.ninst - launch_inst - proved_skip : 0);
     if (lane == 0 && kSoloOnce) {
-        atomicAdd(&CX->stats[23], (unsigned long long)xi);
-        atomicAdd(&CX->stats[0], (unsigned long long)fb);
-        atomicAdd(&CX->stats[1], (unsigned long long)db);
-        atomicAdd(&CX->stats[2], (unsigned long long)pm);
+        atomicAdd(&CX->stats[ST_DEVICE_INSTS], (unsigned long long)xi);
+        atomicAdd(&CX->stats[ST_FETCH_BYTES], (unsigned long long)fb);
+        atomicAdd(&CX->stats[ST_DATA_BYTES], (unsigned long long)db);
+        atomicAdd(&CX->stats[ST_PAGES], (unsigned long long)pm);
         {   // the same per kernel: 0 64-lane, 1 solo, 2 solo-odd (the bench's per-kernel roofline)
             constexpr uint32_t kk = kNL > 1 ? 0u : (kOdd ? 2u : 1u);
-            atomicAdd(&CX->stats[40 + 4 * kk], (unsigned long long)fb);
-            atomicAdd(&CX->stats[41 + 4 * kk], (unsigned long long)db);
-            atomicAdd(&CX->stats[42 + 4 * kk], (unsigned long long)pm);
-            atomicAdd(&CX->stats[43 + 4 * kk], (unsigned long long)xi);
+            atomicAdd(&CX->stats[stat_kernel(kk, kStKFetch)], (unsigned long long)fb);
+            atomicAdd(&CX->stats[stat_kernel(kk, kStKData)], (unsigned long long)db);
+            atomicAdd(&CX->stats[stat_kernel(kk, kStKPages)], (unsigned long long)pm);
+            atomicAdd(&CX->stats[stat_kernel(kk, kStKInsts)], (unsigned long long)xi);
         }
-        atomicAdd(&CX->stats[6], (unsigned long long)n_iter);
-        atomicAdd(&CX->stats[7], (unsigned long long)n_exec);
-        atomicAdd(&CX->stats[8], (unsigned long long)n_slow);
-        atomicAdd(&CX->stats[9], (unsigned long long)n_min);
-        atomicMax(&CX->stats[10], (unsigned long long)n_iter);
-        atomicAdd(&CX->stats[11], (unsigned long long)n_chk);
-        atomicAdd(&CX->stats[12], (unsigned long long)n_early);
-        atomicAdd(&CX->stats[14], (unsigned long long)si);
-        atomicAdd(&CX->stats[16], (unsigned long long)n_tx);
-        atomicAdd(&CX->stats[17], (unsigned long long)n_txin);
-        atomicAdd(&CX->stats[24], (unsigned long long)n_simt);
+        atomicAdd(&CX->stats[ST_LOOP_ITERS], (unsigned long long)n_iter);
+        atomicAdd(&CX->stats[ST_LANE_INSTS], (unsigned long long)n_exec);
+        atomicAdd(&CX->stats[ST_SLOW_FETCHES], (unsigned long long)n_slow);
+        atomicAdd(&CX->stats[ST_MIN_PC], (unsigned long long)n_min);
+        atomicMax(&CX->stats[ST_MAX_WAVE_ITERS], (unsigned long long)n_iter);
+        atomicAdd(&CX->stats[ST_EARLY_CHECKS], (unsigned long long)n_chk);
+        atomicAdd(&CX->stats[ST_EARLY_EXITS], (unsigned long long)n_early);
+        atomicAdd(&CX->stats[ST_START_INST_SUM], (unsigned long long)si);
+        atomicAdd(&CX->stats[ST_TX_INSTS], (unsigned long long)n_tx);
+        atomicAdd(&CX->stats[ST_TX_ENTRIES], (unsigned long long)n_txin);
+        atomicAdd(&CX->stats[ST_SIMT_LANE_INSTS], (unsigned long long)n_simt);
         // the slowest wave: iterations, translated permille, entries (packed)
-        atomicMax(&CX->stats[18], ((unsigned long long)n_iter << 32) |
-                                      ((unsigned long long)(n_iter ? (uint64_t)n_tx * 1000 / n_iter : 0) << 20) |
-                                      (n_txin < (1u << 20) ? n_txin : (1u << 20) - 1));
-        atomicMax(&CX->stats[19], ((unsigned long long)n_iter << 32) | (n_slow < 0xFFFFFFFFu ? n_slow : 0xFFFFFFFFu));
+        atomicMax(&CX->stats[ST_SLOWEST_WAVE_TX],
+                  ((unsigned long long)n_iter << 32) |
+                      ((unsigned long long)(n_iter ? (uint64_t)n_tx * 1000 / n_iter : 0) << 20) |
+                      (n_txin < (1u << 20) ? n_txin : (1u << 20) - 1));
+        atomicMax(&CX->stats[ST_SLOWEST_WAVE_SLOW],
+                  ((unsigned long long)n_iter << 32) | (n_slow < 0xFFFFFFFFu ? n_slow : 0xFFFFFFFFu));
 #undef n_slow
 #undef n_min
 #undef n_exec

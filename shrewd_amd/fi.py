@@ -10,6 +10,7 @@ MI355X is visible the engine refuses to start (FI_E_NODEVICE).
 from __future__ import annotations
 
 import ctypes as C
+import enum
 import os
 from typing import Iterable, Sequence
 
@@ -270,6 +271,21 @@ def issue_model_run(ops: np.ndarray, params: IssueParams | None = None):
 
 
 _lib = None
+N_STATS = 64          # entries of Engine.debug_stats() (fi_types.h kNStats); their names: STAT, below
+
+
+class WAVE(enum.IntEnum):
+    """Words of one record of Engine.debug_waves() (include/fi_debug.h fi_debug_waves)."""
+    CYCLES = 0
+    ITERS = 1
+    TX_INSTS = 2
+    SLOW_MINPC = 3
+    RT_START = 4
+    RT_END = 5
+    TRIAL = 6
+    TRIAL_INSTS = 7
+    TX_ENTRIES = 8
+    PAGE_LOOKUPS = 9
 
 
 def library_path() -> str:
@@ -352,8 +368,22 @@ def lib():
         L.fi_run_tick_trials_device.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp]
         L.fi_translate_status.restype = C.c_char_p
         L.fi_translate_status.argtypes = [vp]
+        L.fi_debug_stat_name.restype = C.c_char_p
+        L.fi_debug_stat_name.argtypes = [C.c_uint32]
+        global STAT
+        STAT = enum.IntEnum("STAT", {L.fi_debug_stat_name(i).decode(): i for i in range(N_STATS)
+                                     if L.fi_debug_stat_name(i)})
         _lib = L
     return _lib
+
+
+def __getattr__(name):
+    """STAT: the slots of Engine.debug_stats() by name (STAT.TX_INSTS, ...), an
+    IntEnum made from the library's own table (fi_debug_stat_name) when it loads."""
+    if name == "STAT":
+        lib()
+        return STAT
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _cstrs(items: Sequence[str] | None):
@@ -626,7 +656,7 @@ class Engine:
         return self.L.fi_translate_status(self.h).decode()
 
     def debug_waves(self, n_waves: int) -> np.ndarray:
-        out = np.zeros((n_waves, 10), np.uint64)
+        out = np.zeros((n_waves, len(WAVE)), np.uint64)
         self._chk(self.L.fi_debug_waves(self.h, out.ctypes.data, n_waves), "fi_debug_waves")
         return out
 
@@ -678,7 +708,7 @@ class Engine:
         return self.L.fi_last_kernel_ms(self.h)
 
     def debug_stats(self) -> np.ndarray:
-        out = np.zeros(64, np.uint64)
+        out = np.zeros(N_STATS, np.uint64)
         self._chk(self.L.fi_debug_stats(self.h, out.ctypes.data), "fi_debug_stats")
         return out
 

@@ -231,6 +231,7 @@ def test_chunks_and_second_pass(engines):
     """Launch size changes no stream; neither does the second pass of the
     trials that ran out of private pages (P = 1, no overflow pool: every chunk
     has some), which writes into the rows its first pass began."""
+    from shrewd_amd import STAT
     from shrewd_amd.fi import CFG_NO_OVERFLOW
     for name in ("outs", "crc32"):
         one = engines(name)
@@ -246,7 +247,7 @@ def test_chunks_and_second_pass(engines):
             for f in ("counts", "crash_sub", "escape_sub", "trials", "guest_insts"):
                 assert np.array_equal(got[1][f], hist[f]), (name, what, f)
             same_streams(got[2], want, f"{name} {what}")
-        assert int(redo.debug_stats()[30]) > 0, f"{name}: no resource escape to redo"
+        assert int(redo.debug_stats()[STAT.REDO_TRIALS]) > 0, f"{name}: no resource escape to redo"
 
 
 def test_arguments(engines):

@@ -262,6 +262,7 @@ def test_first_access_forwarding(engine_factory, oracle_mod, name):
     """Register sites are injected at the golden run's next access of the
     register (dead ones end at injection): outcomes equal the oracle's and
     the unforwarded engine's."""
+    from shrewd_amd import STAT
     e = engine_factory(name)
     f = engine_factory(name, flags=512)
     o = oracle_for(oracle_mod, name)
@@ -269,9 +270,9 @@ def test_first_access_forwarding(engine_factory, oracle_mod, name):
         x.set_campaign(0xF0A0, REGS, 1)
     sites = e.sample(0, 3000)
     dev, _ = e.run_sites(sites)
-    dead = int(e.debug_stats()[27])
+    dead = int(e.debug_stats()[STAT.REG_DEAD])
     ref, _ = f.run_sites(sites)
-    assert int(f.debug_stats()[27]) == 0 and dead > 0
+    assert int(f.debug_stats()[STAT.REG_DEAD]) == 0 and dead > 0
     compare(dev, ref, sites)
     compare(dev, o.run_trials(sites), sites)
 
@@ -288,13 +289,14 @@ def test_translation_skipped_without_hot_code(engine_factory):
 def test_translated_path_active(engine_factory, name):
     """The load-time translated kernel (fi_trial_kernel_tx) is built and runs:
     a hipRTC failure would otherwise fall back to the static kernel silently."""
+    from shrewd_amd import STAT
     e = engine_factory(name)
     assert e.translate_status() == "", e.translate_status()
     assert e.golden.translated_blocks > 0 and e.golden.translated_insts > 0
     e.set_campaign(0x7A11, REGS | PC, 1)
     e.run_trials(0, 2000)
     st = e.debug_stats()
-    assert int(st[16]) > 0 and int(st[17]) > 0   # translated instructions, block entries
+    assert int(st[STAT.TX_INSTS]) > 0 and int(st[STAT.TX_ENTRIES]) > 0   # translated instructions, block entries
 
 
 def test_dead_memory_faults_end_at_injection(engine_factory, oracle_mod):
@@ -302,12 +304,13 @@ def test_dead_memory_faults_end_at_injection(engine_factory, oracle_mod):
     them ends at injection as the golden run (the golden run's access index,
     fi_trial.hip:mem_dead); the outcomes still equal the oracle's full runs,
     and the shortcut is really taken."""
+    from shrewd_amd import STAT
     e = engine_factory("crc32")
     o = oracle_for(oracle_mod, "crc32")
     e.set_campaign(0x5EED0D0D, MEM, 2)
     sites = e.sample(0, 4000)
     dev, _ = e.run_sites(sites)
-    assert int(e.debug_stats()[26]) > 1000
+    assert int(e.debug_stats()[STAT.MEM_DEAD]) > 1000
     compare(dev, o.run_trials(sites), sites)
 
 
@@ -363,6 +366,7 @@ def test_counted_loop_hang_proofs(engine_factory, oracle_mod):
     proves those hangs when it enters the loop (fi_translate.cpp): the records
     equal a run without the proofs (FI_CFG_NO_HANG_PROOF: every hang runs to
     the cap) and the oracle's, with fewer instructions executed."""
+    from shrewd_amd import STAT
     from shrewd_amd.fi import CFG_NO_HANG_PROOF
     n = 20000
     on = engine_factory("crc32", max_trials_per_launch=n)
@@ -371,9 +375,9 @@ def test_counted_loop_hang_proofs(engine_factory, oracle_mod):
         e.set_campaign(0x5EED0002, REGS | PC, 1)
         e.set_protect(0)
     a, ha = on.run_trials(0, n)
-    proved, crashed = int(on.debug_stats()[56]), int(on.debug_stats()[57])
+    proved, crashed = int(on.debug_stats()[STAT.LOOP_HANGS]), int(on.debug_stats()[STAT.LOOP_PGFAULTS])
     b, hb = off.run_trials(0, n)
-    assert int(off.debug_stats()[56]) == 0 and int(off.debug_stats()[57]) == 0
+    assert int(off.debug_stats()[STAT.LOOP_HANGS]) == 0 and int(off.debug_stats()[STAT.LOOP_PGFAULTS]) == 0
     assert np.array_equal(a, b)
     hang = np.nonzero(a["cls"] == 3)[0]
     assert len(hang) > 20 and proved > 0 and proved <= len(hang)
@@ -404,7 +408,8 @@ def test_dynamic_loop_proofs(engine_factory, oracle_mod, name):
     its loop and proved to repeat forever.  Every such trial is a hang whose
     record equals the oracle's (which runs it to the cap) and the engine's
     own without proofs (FI_CFG_NO_HANG_PROOF), and the proofs fired
-    (stats[59]) with far fewer instructions executed."""
+    (STAT.LP_COMMIT) with far fewer instructions executed."""
+    from shrewd_amd import STAT
     from shrewd_amd.fi import CFG_NO_HANG_PROOF
     ids = DYN_LOOP_TRIALS[name]
     on = engine_factory(name, flags=128, max_trials_per_launch=4096)            # FI_CFG_SOLO_ALL
@@ -414,9 +419,9 @@ def test_dynamic_loop_proofs(engine_factory, oracle_mod, name):
         e.set_protect(0)
     sites = on.sample(0, max(ids) + 1)[ids]
     a, ha = on.run_sites(sites)
-    proved = int(on.debug_stats()[59])
+    proved = int(on.debug_stats()[STAT.LP_COMMIT])
     b, hb = off.run_sites(sites)
-    assert int(off.debug_stats()[59]) == 0
+    assert int(off.debug_stats()[STAT.LP_COMMIT]) == 0
     assert np.array_equal(a, b)
     assert (a["cls"] == 3).all() and (a["detail"] == 0).all()
     assert proved >= len(ids) - 1
@@ -438,9 +443,10 @@ def test_runoff_loop_proofs(oracle_mod):
     """Run-off loops (fi_translate.cpp, fi_trial.hip loop_outcome): faults on
     the scan pointer / end of the runoff program's three scan loops.  Trials
     that walk off a .bss buffer or below the text end as page-fault crashes
-    proved at the loop's entry (stats[57]); those that walk into heap pages
-    the fault handler would map stay undecided (stats[58]) and run on.  Every
+    proved at the loop's entry (STAT.LOOP_PGFAULTS); those that walk into heap pages
+    the fault handler would map stay undecided (STAT.LOOP_UNDECIDED) and run on.  Every
     record equals the oracle's, with the proofs on and off."""
+    from shrewd_amd import STAT
     from shrewd_amd import Engine
     from shrewd_amd.fi import CFG_NO_HANG_PROOF
     import test_isa_vectors as kat
@@ -458,7 +464,7 @@ def test_runoff_loop_proofs(oracle_mod):
         assert e.translate_status() == ""
         compare(dev, ref, sites)
         st = e.debug_stats()
-        got.append((int(st[57]), int(st[58]), int(h["device_insts"])))
+        got.append((int(st[STAT.LOOP_PGFAULTS]), int(st[STAT.LOOP_UNDECIDED]), int(h["device_insts"])))
         e.close()
     (crash_on, und_on, ins_on), (crash_off, und_off, ins_off) = got
     assert crash_on > 10 and und_on > 0 and crash_off == 0 and und_off == 0
@@ -468,11 +474,12 @@ def test_runoff_loop_proofs(oracle_mod):
 def test_storeoff_loop_proofs(oracle_mod):
     """Run-off loops that store at their counter (round 6: fi_translate.cpp
     kind 2, fi_trial.hip loop_outcome): store walks off a .bss buffer end as
-    page-fault crashes proved at the loop's entry (stats[57]); walks that
+    page-fault crashes proved at the loop's entry (STAT.LOOP_PGFAULTS); walks that
     could reach the code range or go into heap pages the fault handler maps
-    stay undecided (stats[58]) and run on.  Every record equals the oracle's
+    stay undecided (STAT.LOOP_UNDECIDED) and run on.  Every record equals the oracle's
     (reference semantics: mem_state.cc:387-447, sim/faults.cc:95-105), with
     the proofs on and off."""
+    from shrewd_amd import STAT
     from shrewd_amd import Engine
     from shrewd_amd.fi import CFG_NO_HANG_PROOF
     import test_isa_vectors as kat
@@ -493,7 +500,7 @@ def test_storeoff_loop_proofs(oracle_mod):
             assert {0, 2, 3, 4} <= kinds, kinds
         compare(dev, ref, sites)
         st = e.debug_stats()
-        got.append((int(st[57]), int(st[58]), int(h["device_insts"])))
+        got.append((int(st[STAT.LOOP_PGFAULTS]), int(st[STAT.LOOP_UNDECIDED]), int(h["device_insts"])))
         e.close()
     (crash_on, und_on, ins_on), (crash_off, und_off, ins_off) = got
     assert crash_on > 10 and und_on > 0 and crash_off == 0 and und_off == 0
@@ -505,16 +512,17 @@ def test_region_kat_proofs(oracle_mod):
     and eleven near-miss twins the translator must refuse, under faults on
     each loop's counter, bound, table bases and ra, plus hand-placed sites
     (region_explicit_sites).  Every record equals the oracle's, with the
-    proofs on and off.  With them on, hangs are proved (stats[56]) with fewer
+    proofs on and off.  With them on, hangs are proved (STAT.LOOP_HANGS) with fewer
     instructions run, and the sites that move V0's store table into the text,
     onto an unmapped page, or to the end of the data page with its last 64
     bytes on the unmapped page after it (a check of the table's first page
     alone would call that one a hang; the oracle has it page-fault ten passes
-    on) while lengthening the loop stay undecided (stats[58]: loop_outcome
+    on) while lengthening the loop stay undecided (STAT.LOOP_UNDECIDED: loop_outcome
     kinds 1 / 5) and run on.  The counts below are
     the oracle's for seed 13 and the 3000 random sites (valid-loop hangs 119, V0
     bound flips of bit 12 and up 37, all hangs; V3's 34, none a hang; V6
     crashes 119): a site set that exercised nothing cannot pass."""
+    from shrewd_amd import STAT
     from shrewd_amd import Engine
     from shrewd_amd.fi import CFG_NO_HANG_PROOF
     import test_isa_vectors as kat
@@ -548,7 +556,8 @@ def test_region_kat_proofs(oracle_mod):
         dev, h = e.run_sites(sites)
         compare(dev, ref, sites)
         st = e.debug_stats()
-        got.append((int(st[56]), int(st[57]), int(st[58]), int(h["device_insts"])))
+        got.append((int(st[STAT.LOOP_HANGS]), int(st[STAT.LOOP_PGFAULTS]), int(st[STAT.LOOP_UNDECIDED]),
+                    int(h["device_insts"])))
         e.close()
     print("region KAT (hangs proved, crashes proved, undecided, device insts): on", got[0], "off", got[1])
     (hang_on, _, und_on, ins_on), (hang_off, crash_off, und_off, ins_off) = got
@@ -563,8 +572,9 @@ def test_region_loop_proofs(engine_factory, oracle_mod):
     """intmix's loop bound s3 flipped high: the main loop (a call and table
     stores per pass) runs to the hang cap.  The region proof (fi_translate.cpp,
     fi_trial.hip loop_outcome: bounded accesses, kinds 1 / 5) ends those
-    trials as hangs at their next dispatch entry into the loop (stats[56]);
+    trials as hangs at their next dispatch entry into the loop (STAT.LOOP_HANGS);
     every record equals the oracle's, with the proofs on and off."""
+    from shrewd_amd import STAT
     from oracle.pyoracle import SITE_DT
     from shrewd_amd.fi import CFG_NO_HANG_PROOF
     o = oracle_for(oracle_mod, "intmix")
@@ -582,7 +592,7 @@ def test_region_loop_proofs(engine_factory, oracle_mod):
         e = engine_factory("intmix", flags=flags)
         dev, h = e.run_sites(s)
         compare(dev, ref, s)
-        got.append((int(e.debug_stats()[56]), int(h["device_insts"])))
+        got.append((int(e.debug_stats()[STAT.LOOP_HANGS]), int(h["device_insts"])))
     (hang_on, ins_on), (hang_off, ins_off) = got
     assert (ref["cls"] == 3).sum() > 50
     assert hang_on > 20 and hang_off == 0 and ins_on < ins_off // 2, got
@@ -605,6 +615,7 @@ def test_chunking_invariance(engine_factory):
     overflow pool) runs after the next chunk's first,
     from its own sites buffer -- the outcomes, the histogram and its totals
     equal a one-launch run's, on the host path and the device path."""
+    from shrewd_amd import STAT
     small = engine_factory("qsort", max_trials_per_launch=1000)
     big = engine_factory("qsort")
     for e in (small, big):
@@ -620,7 +631,7 @@ def test_chunking_invariance(engine_factory):
     for e in redo:
         e.set_campaign(77, REGS | PC | MEM, 2)
         o, h = e.run_trials(0, 3000)
-        assert int(e.debug_stats()[30]) > 0, "no resource escape to redo"
+        assert int(e.debug_stats()[STAT.REDO_TRIALS]) > 0, "no resource escape to redo"
         outs.append((o, h))
     assert np.array_equal(outs[0][0], outs[1][0])
     for f in ("counts", "crash_sub", "escape_sub", "trials", "guest_insts"):
@@ -803,6 +814,7 @@ def test_known_answer_programs_solo_interpreter(oracle_mod, prog, path):
     simt: the same with diverged lanes in the SIMT step loop (SIMT);
     no-fault trials print the models and end masked, faulted trials match the
     oracle."""
+    from shrewd_amd import STAT
     from shrewd_amd import Engine
     from shrewd_amd.fi import (CFG_NO_EARLY_EXIT, CFG_NO_SNAPSHOT_START, CFG_NO_SOLO, CFG_NO_TRANSLATE, CFG_SIMT,
                                CFG_SOLO_ALL)
@@ -829,9 +841,9 @@ def test_known_answer_programs_solo_interpreter(oracle_mod, prog, path):
     compare(dev, o.run_trials(sites, protect_mask=0), sites)
     st = e.debug_stats()
     if path == "solo":
-        assert int(st[54]) > 0, "the assembly inner loop did not run"
+        assert int(st[STAT.FAST_INSTS]) > 0, "the assembly inner loop did not run"
     if path == "simt":
-        assert int(st[24]) > 0, "the SIMT step loop did not run"
+        assert int(st[STAT.SIMT_LANE_INSTS]) > 0, "the SIMT step loop did not run"
     e.close()
 
 
@@ -901,6 +913,7 @@ def test_clock_read_blocks_tick_blind_early_exit(oracle_mod):
     (fi_trial.hip, DevCtx::clk_until): every such trial is SDC, as on the
     oracle, with early exit on (the golden run touches no FP/VM/LR-SC state,
     so snapshots and early exit stay enabled) and off."""
+    from shrewd_amd import STAT
     from shrewd_amd import Engine
     import test_isa_vectors as kat
     elf = kat.clk_program_elf()
@@ -915,7 +928,7 @@ def test_clock_read_blocks_tick_blind_early_exit(oracle_mod):
         e.golden_run()
         dev, _ = e.run_sites(sites)
         if flags == 0:
-            assert int(e.debug_stats()[11]) > 0, "early-exit comparisons did not run"
+            assert int(e.debug_stats()[STAT.EARLY_CHECKS]) > 0, "early-exit comparisons did not run"
         compare(dev, ref, sites)
         e.close()
 
@@ -1022,6 +1035,7 @@ def test_resource_redo(engine_factory, oracle_mod, name):
     again with more pages before the histogram: with one private page per
     trial the outcomes equal the default engine's and the oracle's either
     way, while the same engine with neither escapes."""
+    from shrewd_amd import STAT
     from shrewd_amd.fi import CFG_NO_OVERFLOW, CFG_NO_REDO
     n = 3000
     tight = engine_factory(name, private_pages=1, max_trials_per_launch=n)                    # overflow + redo
@@ -1036,14 +1050,14 @@ def test_resource_redo(engine_factory, oracle_mod, name):
     esc = (b["cls"] == 5) & (b["sub"] == 5)
     assert esc.sum() > 0
     r, hr = redo.run_sites(sites)
-    assert int(redo.debug_stats()[30]) == int(esc.sum()) and int(redo.debug_stats()[61]) == 0
+    assert int(redo.debug_stats()[STAT.REDO_TRIALS]) == int(esc.sum()) and int(redo.debug_stats()[STAT.OV_BLOCKS]) == 0
     v, hv = ovf.run_sites(sites)
-    blocks = int(ovf.debug_stats()[61])
+    blocks = int(ovf.debug_stats()[STAT.OV_BLOCKS])
     assert blocks > 0
     # the pool (64 blocks) runs dry at P = 1: the rest still escape without the redo pass
     assert int(((v["cls"] == 5) & (v["sub"] == 5)).sum()) == int(esc.sum()) - blocks
     a, ha = tight.run_sites(sites)
-    assert int(tight.debug_stats()[30]) == int(esc.sum()) - int(tight.debug_stats()[61])
+    assert int(tight.debug_stats()[STAT.REDO_TRIALS]) == int(esc.sum()) - int(tight.debug_stats()[STAT.OV_BLOCKS])
     for x, h in ((a, ha), (r, hr)):
         assert not ((x["cls"] == 5) & (x["sub"] == 5)).any()
         assert int(h["escape_sub"][5]) == 0 and int(h["trials"]) == n
@@ -1085,6 +1099,7 @@ def test_odd_stream_loop_proofs(engine_factory, oracle_mod):
     loop probe is due, and the probe proves the hang (qsort 80709 / 32646:
     a store loop whose values converge).  Records equal the engine's own
     without proofs and the oracle's (which runs them to the cap)."""
+    from shrewd_amd import STAT
     from shrewd_amd.fi import CFG_NO_HANG_PROOF
     ids = [80709, 32646, 37937, 68608]
     on = engine_factory("qsort")
@@ -1094,7 +1109,7 @@ def test_odd_stream_loop_proofs(engine_factory, oracle_mod):
         e.set_protect(0)
     sites = on.sample(0, max(ids) + 1)[ids]
     a, _ = on.run_sites(sites)
-    assert int(on.debug_stats()[59]) >= 2
+    assert int(on.debug_stats()[STAT.LP_COMMIT]) >= 2
     b, _ = off.run_sites(sites)
     assert np.array_equal(a, b)
     assert (a["cls"][:2] == 3).all()
@@ -1121,3 +1136,18 @@ def test_rewritten_code_loops_bit_exact(engine_factory, oracle_mod, name, seed, 
     sites = e.sample(0, max(ids) + 1)[ids]
     dev, _ = e.run_sites(sites)
     compare(dev, o.run_trials(sites, protect_mask=0), sites)
+
+
+def test_every_written_stat_slot_is_named(engine_factory):
+    """The smoke shape (crc32, 512 trials, default configuration): every
+    non-zero entry of debug_stats() is a slot the table names (fi_types.h
+    FI_STAT_SLOTS) -- a kernel that writes a slot the table does not know
+    shows here."""
+    from shrewd_amd import STAT
+    e = engine_factory("crc32")
+    e.set_campaign(0x5EED0001, REGS | PC | MEM, 1)
+    e.run_sites(e.sample(0, 512))
+    st = e.debug_stats()
+    named = {int(s) for s in STAT}
+    assert len(st) == 64 and int(st[STAT.DEVICE_INSTS]) > 0
+    assert [i for i in np.nonzero(st)[0].tolist() if i not in named] == []

@@ -10,7 +10,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402,F401
-from shrewd_amd import Engine  # noqa: E402
+from shrewd_amd import STAT, WAVE, Engine  # noqa: E402
 
 REGS_PC = ((1 << 32) - 2) | (1 << 32)
 ap = argparse.ArgumentParser()
@@ -28,11 +28,12 @@ e.load_elf(open(f"workloads/{name}.elf", "rb").read(), [name])
 g = e.golden_run()
 gms = e.last_kernel_ms()
 st = e.debug_stats()
-clk = int(st[20]) / max(1, int(st[21])) * 100.0
+clk = int(st[STAT.WAVE0_MEMTIME]) / max(1, int(st[STAT.WAVE0_REALTIME])) * 100.0
 print(json.dumps({"golden_ninst": g.ninst, "golden_ms": gms, "golden_ns_per_inst": gms * 1e6 / max(1, g.ninst),
-                  "snapshots": g.snapshots, "interval": g.snapshot_interval, "frames": g.snapshot_frames, "capture_pass_clock_mhz": round(clk, 1),
-                  "cycles_per_inst_capture_pass": int(st[20]) / max(1, g.ninst),
-                  "prof_cycles_per_inst": [round(int(st[24 + k]) / max(1, g.ninst), 1) for k in range(4)],
+                  "snapshots": g.snapshots, "interval": g.snapshot_interval, "frames": g.snapshot_frames,
+                  "capture_pass_clock_mhz": round(clk, 1),
+                  "cycles_per_inst_capture_pass": int(st[STAT.WAVE0_MEMTIME]) / max(1, g.ninst),
+                  "prof_cycles_per_inst": [round(int(st[STAT.PROF_PHASE0 + k]) / max(1, g.ninst), 1) for k in range(4)],
                   "tx_blocks": g.translated_blocks, "tx_insts": g.translated_insts, "tx_us": g.translate_us,
                   "tx_status": e.translate_status()[:3000]}),
       flush=True)
@@ -50,25 +51,36 @@ for n in a.trials:
         st = e.debug_stats()
         ms = e.last_kernel_ms()
         waves = (n + 63) // 64
+        iters, slow = max(1, int(st[STAT.LOOP_ITERS])), max(1, int(st[STAT.SLOW_FETCHES]))
         print(json.dumps({"n": n, "kind": label, "kernel_ms": round(ms, 3), "trials_per_s": n / ms * 1e3,
-                          "iters_per_wave": int(st[6]) / waves, "max_iter_wave": int(st[10]),
-                          "lane_insts": int(st[7]), "lanes_per_iter": round(int(st[7]) / max(1, int(st[6])), 2),
-                          "slow": int(st[8]), "minpc": int(st[9]), "checks": int(st[11]), "early": int(st[12]),
-                          "skipped_prefix": int(st[14]), "cow_pages": int(st[2]),
-                          "ns_per_iter_slowest_wave": round(ms * 1e6 / max(1, int(st[10])), 1),
-                          "clock_mhz": round(int(st[20]) / max(1, int(st[21])) * 100.0, 1),
-                          "wave0_cycles": int(st[20]), "survivors": e.debug_epochs()[:4],
-                          "tx_insts": int(st[16]), "tx_entries": int(st[17]),
-                          "slowest": {"iters": int(st[18]) >> 32, "tx_permille": (int(st[18]) >> 20) & 0xFFF,
-                                      "tx_entries": int(st[18]) & 0xFFFFF, "slow": int(st[19]) & 0xFFFFFFFF},
-                          "prof_cycles_per_iter": [round(int(st[24 + k]) / max(1, int(st[6])), 1) for k in range(4)],
-                          "prof_slow_cycles_per_slow": [round(int(st[24 + k]) / max(1, int(st[8])), 1) for k in range(4, 8)],
+                          "iters_per_wave": int(st[STAT.LOOP_ITERS]) / waves,
+                          "max_iter_wave": int(st[STAT.MAX_WAVE_ITERS]),
+                          "lane_insts": int(st[STAT.LANE_INSTS]),
+                          "lanes_per_iter": round(int(st[STAT.LANE_INSTS]) / max(1, int(st[STAT.LOOP_ITERS])), 2),
+                          "slow": int(st[STAT.SLOW_FETCHES]), "minpc": int(st[STAT.MIN_PC]),
+                          "checks": int(st[STAT.EARLY_CHECKS]), "early": int(st[STAT.EARLY_EXITS]),
+                          "skipped_prefix": int(st[STAT.START_INST_SUM]), "cow_pages": int(st[STAT.PAGES]),
+                          "ns_per_iter_slowest_wave": round(ms * 1e6 / max(1, int(st[STAT.MAX_WAVE_ITERS])), 1),
+                          "clock_mhz": round(int(st[STAT.WAVE0_MEMTIME]) / max(1, int(st[STAT.WAVE0_REALTIME])) * 100.0,
+                                             1),
+                          "wave0_cycles": int(st[STAT.WAVE0_MEMTIME]), "survivors": e.debug_epochs()[:4],
+                          "tx_insts": int(st[STAT.TX_INSTS]), "tx_entries": int(st[STAT.TX_ENTRIES]),
+                          "slowest": {"iters": int(st[STAT.SLOWEST_WAVE_TX]) >> 32,
+                                      "tx_permille": (int(st[STAT.SLOWEST_WAVE_TX]) >> 20) & 0xFFF,
+                                      "tx_entries": int(st[STAT.SLOWEST_WAVE_TX]) & 0xFFFFF,
+                                      "slow": int(st[STAT.SLOWEST_WAVE_SLOW]) & 0xFFFFFFFF},
+                          # (-DFI_PROF builds only, else zeros: stamps 0-3 per iteration, 4-7 per slow fetch)
+                          "prof_cycles_per_iter": [round(int(st[STAT.PROF_PHASE0 + k]) / iters, 1) for k in range(4)],
+                          "prof_slow_cycles_per_slow": [round(int(st[STAT.PROF_PHASE0 + k]) / slow, 1)
+                                                        for k in range(4, 8)],
                           "classes": np.bincount(out["cls"], minlength=6).tolist()}), flush=True)
         wv = e.debug_waves(waves).astype(np.int64)
-        top = np.argsort(-wv[:, 0])[:4]
-        print(json.dumps({"longest_waves": [{"wave": int(w), "ms": round(wv[w, 0] / 2.4e6, 2), "iters": int(wv[w, 1]),
-                                             "tx": int(wv[w, 2]), "slow": int(wv[w, 3]),
-                                             "ns_per_iter": round(wv[w, 0] / 2.4 / max(1, wv[w, 1]), 1)}
+        top = np.argsort(-wv[:, WAVE.CYCLES])[:4]
+        print(json.dumps({"longest_waves": [{"wave": int(w), "ms": round(wv[w, WAVE.CYCLES] / 2.4e6, 2),
+                                             "iters": int(wv[w, WAVE.ITERS]), "tx": int(wv[w, WAVE.TX_INSTS]),
+                                             "slow": int(wv[w, WAVE.SLOW_MINPC]),
+                                             "ns_per_iter": round(wv[w, WAVE.CYCLES] / 2.4 /
+                                                                  max(1, wv[w, WAVE.ITERS]), 1)}
                                             for w in top]}), flush=True)
         if label == "faults" and n == a.trials[-1]:
             np.save("gpurun_out/waves.npy", wv)
@@ -88,6 +100,7 @@ if a.converged:
         st = e2.debug_stats()
         print(json.dumps({"converged_wave_from_start": label, "kernel_ms": round(ms, 3),
                           "ns_per_inst": round(ms * 1e6 / g2.ninst, 1),
-                          "cycles_per_inst": round(int(st[20]) / g2.ninst, 1), "tx_insts": int(st[16]),
-                          "tx_entries": int(st[17]), "status": e2.translate_status()[:200]}), flush=True)
+                          "cycles_per_inst": round(int(st[STAT.WAVE0_MEMTIME]) / g2.ninst, 1),
+                          "tx_insts": int(st[STAT.TX_INSTS]),
+                          "tx_entries": int(st[STAT.TX_ENTRIES]), "status": e2.translate_status()[:200]}), flush=True)
         e2.close()

@@ -1,7 +1,7 @@
 """Why does one 1M-trial launch run slower per trial than 100k-trial launches?
 Runs the same N seeded trials once per launch size and reports, per size:
 wall time, per-dispatch kernel time by kind (0 64-lane, 1 solo, 2 solo-odd),
-epoch survivor counts, the redo count (stats[30]) and the solo dispatch's
+epoch survivor counts, the redo count (STAT.REDO_TRIALS) and the solo dispatch's
 slowest waves (start / end, instructions, outcome) of the LAST chunk.
 
 python tools/gpu/launch_size.py [WORKLOAD] [N] [SEED] [SIZES...] -> JSON lines"""
@@ -13,7 +13,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
-from shrewd_amd import Engine  # noqa: E402
+from shrewd_amd import STAT, WAVE, Engine  # noqa: E402
 
 REGS_PC = ((1 << 32) - 2) | (1 << 32)
 name = sys.argv[1] if len(sys.argv) > 1 else "qsort"
@@ -41,30 +41,32 @@ for size in SIZES:
     st = e.debug_stats()
     ep = e.debug_epochs()
     k_last = N - size * ((N - 1) // size)
-    w = e.debug_waves(k_last).reshape(k_last, 10).astype(np.int64)
-    live = (w[:, 6] >= 0) & (w[:, 6] < k_last) & (w[:, 5] > 0) & (w[:, 7] > 0)
+    w = e.debug_waves(k_last).reshape(k_last, len(WAVE)).astype(np.int64)
+    live = (w[:, WAVE.TRIAL] >= 0) & (w[:, WAVE.TRIAL] < k_last) & (w[:, WAVE.RT_END] > 0) & (w[:, WAVE.TRIAL_INSTS] > 0)
     w = w[live]
     rec = {"workload": name, "trials": N, "per_launch": size, "private_pages": PP, "wall_s": round(wall, 4),
            "trials_per_s": round(N / wall), "device_insts": int(h["device_insts"]),
            "dispatch_ms_by_kind": {k: [round(sum(v), 2), len(v)] for k, v in by.items()},
-           "epochs_last_chunk": ep[:4], "redo_last_chunk": int(st[30]), "stats_0_24": st[:64].tolist(),
+           "epochs_last_chunk": ep[:4], "redo_last_chunk": int(st[STAT.REDO_TRIALS]), "stats_0_24": st[:64].tolist(),
            "same_as_first": None if ref is None else int((out != ref).sum())}
     if len(w):
-        t0w = w[:, 4].min()
-        start, end = (w[:, 4] - t0w) / 100.0, (w[:, 5] - t0w) / 100.0
+        t0w = w[:, WAVE.RT_START].min()
+        start, end = (w[:, WAVE.RT_START] - t0w) / 100.0, (w[:, WAVE.RT_END] - t0w) / 100.0
         rec["solo_waves"] = int(len(w))
         rec["solo_span_us"] = round(float(end.max()), 1)
-        rec["solo_insts"] = int(w[:, 7].sum())
+        rec["solo_insts"] = int(w[:, WAVE.TRIAL_INSTS].sum())
         rec["end_q_us"] = {q: round(float(np.quantile(end, q)), 1) for q in (0.5, 0.9, 0.99, 0.999, 1.0)}
         rec["active_at_us"] = {t: int(((start <= t) & (end > t)).sum())
                                for t in (100, 1000, 5000, 20000, 50000, 100000, 200000, 400000)}
         order = np.argsort(-(end - start))[:int(os.environ.get("LS_TOP", "8"))]
-        rec["slowest"] = [{"trial": int(w[i, 6]) + N - k_last, "cls": int(out["cls"][int(w[i, 6]) + N - k_last]),
+        rec["slowest"] = [{"trial": int(w[i, WAVE.TRIAL]) + N - k_last,
+                           "cls": int(out["cls"][int(w[i, WAVE.TRIAL]) + N - k_last]),
                            "start_us": round(float(start[i]), 1), "end_us": round(float(end[i]), 1),
-                           "insts": int(w[i, 7]), "iters": int(w[i, 1]), "tx_insts": int(w[i, 2]),
-                           "slow": int(w[i, 3]) & 0xFFFFFFFF, "trips": int(w[i, 3]) >> 32,
-                           "tx_entries": int(w[i, 8]), "nmiss": int(w[i, 9]),
-                           "ns_per_inst": round(1e3 * float(end[i] - start[i]) / max(1, int(w[i, 7])), 1)}
+                           "insts": int(w[i, WAVE.TRIAL_INSTS]), "iters": int(w[i, WAVE.ITERS]),
+                           "tx_insts": int(w[i, WAVE.TX_INSTS]),
+                           "slow": int(w[i, WAVE.SLOW_MINPC]) & 0xFFFFFFFF, "trips": int(w[i, WAVE.SLOW_MINPC]) >> 32,
+                           "tx_entries": int(w[i, WAVE.TX_ENTRIES]), "nmiss": int(w[i, WAVE.PAGE_LOOKUPS]),
+                           "ns_per_inst": round(1e3 * float(end[i] - start[i]) / max(1, int(w[i, WAVE.TRIAL_INSTS])), 1)}
                           for i in order]
     esc = np.nonzero(out["cls"] == 5)[0]
     rec["escapes"] = [{"trial": int(i), "sub": int(out["sub"][i]), "detail": hex(int(out["detail"][i])),

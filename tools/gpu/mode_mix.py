@@ -13,7 +13,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
-from shrewd_amd import Engine  # noqa: E402
+from shrewd_amd import WAVE, Engine  # noqa: E402
 
 REGS_PC = ((1 << 32) - 2) | (1 << 32)
 name = sys.argv[1] if len(sys.argv) > 1 else "crc32"
@@ -33,16 +33,17 @@ for rep in range(3):
 rec["dispatch_ms"] = {str(k): round(m, 3) for m, k in zip(ms, kinds)}
 ep = e.debug_epochs()
 ns = int(ep[0])
-w = e.debug_waves(ns).reshape(ns, 10).astype(np.int64)
-w = w[(w[:, 5] > 0) & (w[:, 6] >= 0)]
-tx, insts = w[:, 2], w[:, 7]
+w = e.debug_waves(ns).reshape(ns, len(WAVE)).astype(np.int64)
+w = w[(w[:, WAVE.RT_END] > 0) & (w[:, WAVE.TRIAL] >= 0)]
+tx, insts = w[:, WAVE.TX_INSTS], w[:, WAVE.TRIAL_INSTS]
 other = np.maximum(insts - tx, 0)
-cyc = w[:, 0]
+cyc = w[:, WAVE.CYCLES]
 rec.update({"solo_waves": int(len(w)), "insts": int(insts.sum()), "tx_insts": int(tx.sum()),
-            "other_insts": int(other.sum()), "iters": int(w[:, 1].sum()), "tx_entries": int(w[:, 8].sum()),
-            "trips": int((w[:, 3] >> 32).sum()), "slow": int((w[:, 3] & 0xFFFFFFFF).sum()),
-            "nmiss": int(w[:, 9].sum()), "wave_cycles": int(cyc.sum())})
-A = np.stack([tx, other, w[:, 8], w[:, 9], np.ones(len(w))], 1).astype(np.float64)
+            "other_insts": int(other.sum()), "iters": int(w[:, WAVE.ITERS].sum()),
+            "tx_entries": int(w[:, WAVE.TX_ENTRIES].sum()),
+            "trips": int((w[:, WAVE.SLOW_MINPC] >> 32).sum()), "slow": int((w[:, WAVE.SLOW_MINPC] & 0xFFFFFFFF).sum()),
+            "nmiss": int(w[:, WAVE.PAGE_LOOKUPS].sum()), "wave_cycles": int(cyc.sum())})
+A = np.stack([tx, other, w[:, WAVE.TX_ENTRIES], w[:, WAVE.PAGE_LOOKUPS], np.ones(len(w))], 1).astype(np.float64)
 coef = np.linalg.lstsq(A, cyc.astype(np.float64), rcond=None)[0]
 rec["fit_cycles_per"] = {"tx_inst": round(coef[0], 2), "other_inst": round(coef[1], 2),
                          "tx_entry": round(coef[2], 1), "miss": round(coef[3], 1), "wave": round(coef[4], 1)}

@@ -9,7 +9,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
-from shrewd_amd import Engine  # noqa: E402
+from shrewd_amd import STAT, Engine  # noqa: E402
 
 REGS_PC = ((1 << 32) - 2) | (1 << 32)
 name, seed, ids = sys.argv[1], int(sys.argv[2], 0), [int(x) for x in sys.argv[3:]]
@@ -28,9 +28,11 @@ for rep in range(2):
         rec = {"trial": i, "rep": rep, "site": [int(s["inst"][0]), hex(int(s["mask"][0])), int(s["target"][0])],
                "cls": int(out["cls"][0]), "sub": int(out["sub"][0]), "ninst": int(out["ninst"][0]),
                "dispatch_ms": [round(float(x), 3) for x in dms], "kinds": [int(k) for k in kinds],
-               "device_insts": int(st[23]), "tx_insts": int(st[16]), "tx_entries": int(st[17]),
-               "fast_calls": int(st[53]), "fast_insts": int(st[54]), "fast_handbacks": int(st[55]),
-               "loop_iters": int(st[6]), "slow_fetches": int(st[8])}
+               "device_insts": int(st[STAT.DEVICE_INSTS]), "tx_insts": int(st[STAT.TX_INSTS]),
+               "tx_entries": int(st[STAT.TX_ENTRIES]),
+               "fast_calls": int(st[STAT.FAST_RUNS]), "fast_insts": int(st[STAT.FAST_INSTS]),
+               "fast_handbacks": int(st[STAT.FAST_BACKS]),
+               "loop_iters": int(st[STAT.LOOP_ITERS]), "slow_fetches": int(st[STAT.SLOW_FETCHES])}
         tot = sum(dms)
-        rec["ns_per_inst"] = round(tot * 1e6 / max(1, int(st[23])), 1)
+        rec["ns_per_inst"] = round(tot * 1e6 / max(1, int(st[STAT.DEVICE_INSTS])), 1)
         print(json.dumps(rec), flush=True)

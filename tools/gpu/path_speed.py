@@ -7,7 +7,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
-from shrewd_amd import Engine  # noqa: E402
+from shrewd_amd import STAT, Engine  # noqa: E402
 
 REGS_PC = ((1 << 32) - 2) | (1 << 32)
 name, seed, ids = sys.argv[1], int(sys.argv[2], 0), [int(x) for x in sys.argv[3:]]
@@ -25,6 +25,7 @@ for label, flags in (("solo_tx", 128), ("solo_interp", 128 | 4), ("wave_tx", 64)
         ms = e.last_kernel_ms()
         st = e.debug_stats()
         print(json.dumps({"path": label, "trial": i, "cls": int(o["cls"][0]), "ninst": int(o["ninst"][0]),
-                          "ns_per_inst": round(ms * 1e6 / max(1, int(o["ninst"][0])), 1), "slow": int(st[8]),
-                          "tx": int(st[16])}), flush=True)
+                          "ns_per_inst": round(ms * 1e6 / max(1, int(o["ninst"][0])), 1),
+                          "slow": int(st[STAT.SLOW_FETCHES]),
+                          "tx": int(st[STAT.TX_INSTS])}), flush=True)
     e.close()

@@ -9,7 +9,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
-from shrewd_amd import Engine  # noqa: E402
+from shrewd_amd import STAT, Engine  # noqa: E402
 from shrewd_amd.fi import CFG_NO_TRANSLATE  # noqa: E402
 
 REGS_PC = ((1 << 32) - 2) | (1 << 32)
@@ -24,7 +24,8 @@ for i in ids:
     out, _ = e.run_sites(s)
     ms = e.last_kernel_ms()
     st = e.debug_stats().astype(np.int64)
-    it = max(1, int(st[6]))
+    it = max(1, int(st[STAT.LOOP_ITERS]))
     print(json.dumps({"trial": i, "cls": int(out["cls"][0]), "kernel_ms": round(ms, 3), "iters": it,
-                      "slow": int(st[8]), "ns_per_iter": round(ms * 1e6 / it, 1),
-                      "cycles_per_iter_by_stamp": [round(int(st[32 + k]) / it, 1) for k in range(8)]}), flush=True)
+                      "slow": int(st[STAT.SLOW_FETCHES]), "ns_per_iter": round(ms * 1e6 / it, 1),
+                      "cycles_per_iter_by_stamp": [round(int(st[STAT.PROF_PHASE0 + k]) / it, 1) for k in range(8)]}),
+          flush=True)

@@ -8,7 +8,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
-from shrewd_amd import Engine  # noqa: E402
+from shrewd_amd import STAT, Engine  # noqa: E402
 
 REGS_PC = ((1 << 32) - 2) | (1 << 32)
 CFGS = [("default", 0, 0), ("simt", 256, 0), ("simt_no_solo", 256 | 64, 0), ("simt_no_solo_3ep", 256 | 64, 3),
@@ -37,6 +37,7 @@ for job in jobs:
         print(json.dumps({"w": name, "cfg": label, "kernel_ms": round(e.last_kernel_ms(), 2),
                           "dispatch_ms": [round(x, 2) for x in e.debug_dispatch_ms()],
                           "survivors": e.debug_epochs()[:4], "device_insts": int(h["device_insts"]),
-                          "simt_insts": int(st[24]), "tx_insts": int(st[16]), "slow": int(st[8]),
+                          "simt_insts": int(st[STAT.SIMT_LANE_INSTS]), "tx_insts": int(st[STAT.TX_INSTS]),
+                          "slow": int(st[STAT.SLOW_FETCHES]),
                           "identical_to_default": same}), flush=True)
         e.close()

@@ -13,7 +13,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
-from shrewd_amd import Engine  # noqa: E402
+from shrewd_amd import STAT, Engine  # noqa: E402
 
 S = {"regs_pc": ((1 << 32) - 2) | (1 << 32), "mem": 1 << 33, "result": 1 << 34}
 name, seed, structs = sys.argv[1], int(sys.argv[2], 0), S[sys.argv[3]]
@@ -33,11 +33,14 @@ for i in ids:
     xi = int(h["device_insts"])
     rec = {"trial": i, "site": {k: int(s[0][k]) for k in ("inst", "target", "mask")}, "cls": int(out["cls"][0]),
            "ninst_end": int(out["ninst"][0]), "executed": xi, "kernel_ms": round(ms, 3),
-           "ns_per_inst": round(ms * 1e6 / max(xi, 1), 1), "translated": int(st[16]), "tx_entries": int(st[17]),
-           "slow_fetches": int(st[8]), "iters": int(st[6]), "trips": int(st[9]),
-           "fast_calls": int(st[53]), "fast_insts": int(st[54]), "fast_backs": int(st[55]),
-           "proofs_56_63": [int(x) for x in st[56:64]]}
+           "ns_per_inst": round(ms * 1e6 / max(xi, 1), 1), "translated": int(st[STAT.TX_INSTS]),
+           "tx_entries": int(st[STAT.TX_ENTRIES]),
+           "slow_fetches": int(st[STAT.SLOW_FETCHES]), "iters": int(st[STAT.LOOP_ITERS]), "trips": int(st[STAT.MIN_PC]),
+           "fast_calls": int(st[STAT.FAST_RUNS]), "fast_insts": int(st[STAT.FAST_INSTS]),
+           "fast_backs": int(st[STAT.FAST_BACKS]),
+           "proofs_56_63": [int(x) for x in st[STAT.LOOP_HANGS:]]}
     if os.environ.get("SHREWD_FI_LIB"):
-        rec["cycles_per_iter_by_stamp"] = [round(int(st[32 + k]) / max(1, int(st[6])), 1) for k in range(8)]
-        rec["stats_32_40"] = [int(x) for x in st[32:40]]
+        rec["cycles_per_iter_by_stamp"] = [round(int(st[STAT.PROF_PHASE0 + k]) / max(1, int(st[STAT.LOOP_ITERS])), 1)
+                                           for k in range(8)]
+        rec["stats_32_40"] = [int(x) for x in st[STAT.PROF_PHASE0:STAT.PROF_PHASE7 + 1]]
     print(json.dumps(rec), flush=True)

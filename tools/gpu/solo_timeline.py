@@ -11,7 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
-from shrewd_amd import Engine  # noqa: E402
+from shrewd_amd import WAVE, Engine  # noqa: E402
 
 REGS_PC = ((1 << 32) - 2) | (1 << 32)
 name = sys.argv[1] if len(sys.argv) > 1 else "crc32"
@@ -26,12 +26,12 @@ sites = e.sample(0, n)
 e.run_sites(sites)
 e.kernel_timer_reset()
 out, h = e.run_sites(sites)
-w = e.debug_waves(n).reshape(n, 10).astype(np.int64)
-live = (w[:, 6] >= 0) & (w[:, 6] < n) & (w[:, 5] > 0)
+w = e.debug_waves(n).reshape(n, len(WAVE)).astype(np.int64)
+live = (w[:, WAVE.TRIAL] >= 0) & (w[:, WAVE.TRIAL] < n) & (w[:, WAVE.RT_END] > 0)
 w = w[live]
-t0 = w[:, 4].min()
-start, end = (w[:, 4] - t0) / 100.0, (w[:, 5] - t0) / 100.0        # us
-ins = w[:, 7]
+t0 = w[:, WAVE.RT_START].min()
+start, end = (w[:, WAVE.RT_START] - t0) / 100.0, (w[:, WAVE.RT_END] - t0) / 100.0        # us
+ins = w[:, WAVE.TRIAL_INSTS]
 span = end.max()
 busy = ins > 0
 rec = {"workload": name, "trials": n, "dispatch_ms": e.debug_dispatch_ms(), "solo_waves_with_work": int(busy.sum()),
@@ -42,7 +42,7 @@ rec = {"workload": name, "trials": n, "dispatch_ms": e.debug_dispatch_ms(), "sol
 print(json.dumps(rec), flush=True)
 # the solo order's key (fi_surv_keys_kernel): instructions committed when the
 # solo dispatch began (a proved hang's record says the cap: skip those)
-tids = w[:, 6]
+tids = w[:, WAVE.TRIAL]
 n0 = out["ninst"][tids].astype(np.int64) - ins
 ok = busy & (out["cls"][tids] != 3)
 late = ok & (start > 1000.0)
@@ -61,12 +61,13 @@ for c, t, k in zip(out["cls"][tids[busy]], sites["target"][tids[busy]], ins[busy
 print(json.dumps({"insts_by_cls_target": dict(sorted(grp.items(), key=lambda kv: -kv[1][1])[:24])}), flush=True)
 order = np.argsort(-end)[:top]
 for i in order:
-    tid = int(w[i, 6])
+    tid = int(w[i, WAVE.TRIAL])
     print(json.dumps({"trial": tid, "cls": int(out["cls"][tid]), "target": int(sites["target"][tid]),
                       "bit": int(np.log2(float(sites["mask"][tid]))) if int(sites["mask"][tid]) else -1,
                       "start_us": round(float(start[i]), 1), "end_us": round(float(end[i]), 1),
-                      "insts": int(ins[i]), "ninst0": int(n0[i]), "ns_per_inst": round(1e3 * float(end[i] - start[i]) / max(1, int(ins[i])), 1),
-                      "tx_entries": int(w[i, 8]), "tx_insts": int(w[i, 2])}), flush=True)
+                      "insts": int(ins[i]), "ninst0": int(n0[i]),
+                      "ns_per_inst": round(1e3 * float(end[i] - start[i]) / max(1, int(ins[i])), 1),
+                      "tx_entries": int(w[i, WAVE.TX_ENTRIES]), "tx_insts": int(w[i, WAVE.TX_INSTS])}), flush=True)
 # every solo trial, for offline scheduling studies (SOLO_TL_DUMP=path.npz)
 if os.environ.get("SOLO_TL_DUMP"):
     np.savez(os.environ["SOLO_TL_DUMP"], tid=tids, start_us=start, end_us=end, insts=ins, n0=n0,

@@ -11,7 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
-from shrewd_amd import Engine  # noqa: E402
+from shrewd_amd import STAT, Engine  # noqa: E402
 
 REGS_PC = ((1 << 32) - 2) | (1 << 32)
 name, seed, ids = sys.argv[1], int(sys.argv[2], 0), [int(x) for x in sys.argv[3:]]
@@ -29,6 +29,8 @@ for i in ids + [ids]:
     ran = int(out["ninst"].max()) - int(s["inst"].min())
     print(json.dumps({"trial": i if isinstance(i, int) else "all", "cls": out["cls"].tolist()[:8],
                       "ninst_after_inject": ran, "kernel_ms": round(ms, 3),
-                      "ns_per_inst": round(ms * 1e6 / max(1, ran), 1), "iters": int(st[6]), "slow": int(st[8]),
-                      "minpc": int(st[9]), "tx_insts": int(st[16]), "tx_entries": int(st[17]),
-                      "checks": int(st[11])}), flush=True)
+                      "ns_per_inst": round(ms * 1e6 / max(1, ran), 1), "iters": int(st[STAT.LOOP_ITERS]),
+                      "slow": int(st[STAT.SLOW_FETCHES]),
+                      "minpc": int(st[STAT.MIN_PC]), "tx_insts": int(st[STAT.TX_INSTS]),
+                      "tx_entries": int(st[STAT.TX_ENTRIES]),
+                      "checks": int(st[STAT.EARLY_CHECKS])}), flush=True)

@@ -11,7 +11,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
-from shrewd_amd import Engine  # noqa: E402
+from shrewd_amd import STAT, Engine  # noqa: E402
 
 REGS_PC = ((1 << 32) - 2) | (1 << 32)
 name = sys.argv[1] if len(sys.argv) > 1 else "crc32"
@@ -29,9 +29,11 @@ for rep in range(2):
 print(json.dumps({"workload": name, "golden_ninst": int(g.ninst), "dispatch_ms": e.debug_dispatch_ms(),
                   "survivors": e.debug_epochs()[:4], "kernel_ms": e.last_kernel_ms(),
                   "classes": np.bincount(out["cls"], minlength=6).tolist(),
-                  "device_insts": int(h["device_insts"]), "tx_insts": int(st[16]), "slow_fetches": int(st[8]),
-                  "slowest_wave": {"iters": int(st[18]) >> 32, "tx_permille": (int(st[18]) >> 20) & 0xFFF,
-                                   "entries": int(st[18]) & 0xFFFFF}}), flush=True)
+                  "device_insts": int(h["device_insts"]), "tx_insts": int(st[STAT.TX_INSTS]),
+                  "slow_fetches": int(st[STAT.SLOW_FETCHES]),
+                  "slowest_wave": {"iters": int(st[STAT.SLOWEST_WAVE_TX]) >> 32,
+                                   "tx_permille": (int(st[STAT.SLOWEST_WAVE_TX]) >> 20) & 0xFFF,
+                                   "entries": int(st[STAT.SLOWEST_WAVE_TX]) & 0xFFFFF}}), flush=True)
 # work after injection (instructions a serial run executes past the inject point)
 early = (out["cls"] == 0) & (out["ninst"] == g.ninst)
 work = out["ninst"].astype(np.int64) - sites["inst"].astype(np.int64)
@@ -51,6 +53,8 @@ for i in picked:
     ran = int(o["ninst"][0]) - int(s["inst"][0])
     print(json.dumps({"trial": i, "target": int(s["target"][0]), "bit": int(np.log2(float(s["mask"][0]))),
                       "cls": int(o["cls"][0]), "sub": int(o["sub"][0]), "ran": ran, "ms": round(ms, 3),
-                      "ns_per_inst": round(ms * 1e6 / max(1, ran), 1), "iters": int(st[6]), "slow": int(st[8]),
-                      "tx_insts": int(st[16]), "tx_entries": int(st[17]), "dispatch_ms": e.debug_dispatch_ms()}),
+                      "ns_per_inst": round(ms * 1e6 / max(1, ran), 1), "iters": int(st[STAT.LOOP_ITERS]),
+                      "slow": int(st[STAT.SLOW_FETCHES]),
+                      "tx_insts": int(st[STAT.TX_INSTS]), "tx_entries": int(st[STAT.TX_ENTRIES]),
+                      "dispatch_ms": e.debug_dispatch_ms()}),
           flush=True)
