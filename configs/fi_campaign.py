@@ -50,6 +50,9 @@ def parse(argv=None):
     ap.add_argument("--tick-contract", default="numinst", choices=["numinst", "literal"],
                     help="--cpu-type timing: literal runs the sites where the timing CPU is not a numInst flip "
                          "instead of reporting them as escape/timing")
+    ap.add_argument("--exact", action="store_true",
+                    help="cover the whole fault space instead of --trials samples: one trial per first-access "
+                         "class, weighted (registers, pc, result; --cpu-type atomic; the ctypes path)")
     ap.add_argument("--num-gpus", type=int, default=1)
     ap.add_argument("--max-insts-factor", type=float, default=2.0)
     ap.add_argument("--private-pages", type=int, default=16)
@@ -62,6 +65,8 @@ def _split(s):
 
 
 def run_gem5(a):
+    if a.exact:
+        sys.exit("--exact: the FaultCampaign SimObject has no exact mode yet; run this script with python")
     import m5
     from m5.objects import FaultCampaign, Root
     camp = FaultCampaign(workload=a.workload, cmd=_split(a.cmd) or [a.workload], env=_split(a.env),
@@ -105,11 +110,16 @@ def run_ctypes(a):
                       input=a.input, executable=a.executable or None, cpu_type=a.cpu_type,
                       tick_map=a.tick_map, tick_contract=a.tick_contract)
     t0 = time.perf_counter()
-    c.run(first_trial=a.first_trial)
+    if a.exact:
+        c.run_exact()
+    else:
+        c.run(first_trial=a.first_trial)
     dt = time.perf_counter() - t0
     if rank == 0:
-        s = c.summary()
+        s = c.summary()   # (--exact: "trials" and the classes count sites, the whole space)
         s.update(seconds=dt, trials_per_s=s["trials"] / dt, num_gpus=world)
+        if a.exact:
+            s["vulnerability"] = c.vulnerability()
         print(json.dumps(s), flush=True)
     if world > 1:
         import torch.distributed as dist

@@ -610,6 +610,75 @@ fi_status fi_run_trials(fi_engine *e, uint64_t first_trial, uint64_t n, fi_outco
 /* Explicit sites (parity tests, replay of a gem5-side site list). */
 fi_status fi_run_sites(fi_engine *e, const fi_site *sites, uint64_t n, fi_outcome *out, fi_histogram *hist);
 
+/* ---- Exact campaigns: the whole fault space by def-use pruning.
+ *
+ * The space of a campaign (fi_set_campaign, fi_set_bits) is every site
+ * (t, structure, b): t in [0, golden ninst), a selected structure, an eligible
+ * bit position b -- set in the fi_set_bits mask and <= 64 - burst; the site's
+ * mask is ((1 << burst) - 1) << b.  fi_run_exact covers it with one trial per
+ * equivalence class, counted with the class's size:
+ *  - Register r (1..31).  Its entries ev[off[r] .. off[r + 1]) of the golden
+ *    run's first-access index -- entry = (2 * numInst + !ecall) << 1 | reads,
+ *    numInst counting the instructions committed before the event -- in order,
+ *    u'_i = min(ev_i >> 2, ninst - 1), prev'_i = u'_{i-1} (-1 for the first).
+ *    Entry i heads a class iff its reads bit is set and u'_i > prev'_i; the
+ *    class covers t in (prev'_i, u'_i], its weight is u'_i - prev'_i and its
+ *    representative site is inst = u'_i: a flip anywhere in the interval is
+ *    the flip at the access (first-access forwarding).  The clip to ninst - 1
+ *    matters: the exit ecall reads a0..a7 at numInst == ninst, and sites exist
+ *    only for t < ninst.  Every other t of the register is dead -- the next
+ *    access writes it, or there is none -- and counts as the golden run
+ *    (masked, the golden numInst) without a trial: dead_r = ninst - the sum of
+ *    the weights.
+ *  - The pc (FI_T_PC) and an instruction's result (FI_T_RESULT): one class of
+ *    weight 1 per t, no dead sites.
+ *  - Memory words (FI_T_MEM) have no classes here: a campaign that selects
+ *    them is refused with FI_E_ARG.
+ * Exact trial id k counts through the selected structures in ascending
+ * number, within a structure through its classes in time order, within a
+ * class through the eligible positions ascending: k = class index x nbits +
+ * bit slot, the class index running on across the structures.  fi_site.trial
+ * carries the low 32 bits of k.
+ *
+ * Needs a golden run with a first-access index (golden ninst < 2^29, a
+ * complete golden trace: else FI_E_STATE) and the atomic CPU model.
+ * FI_CFG_NO_FORWARD does not turn the index off: the representatives then run
+ * unforwarded, with the same outcomes.  fi_set_protect,
+ * fi_set_protect_opclasses and fi_set_issue_model apply as in fi_run_sites (a
+ * dead register fault stays masked under a protected register: the watch
+ * fires only on a read). */
+typedef struct {
+    uint64_t space;          /* sites covered: ninst x eligible bits x selected structures */
+    uint64_t trials;         /* exact trials (classes x eligible bits) */
+    uint64_t dead_sites;     /* sites counted as the golden run without a trial */
+    uint32_t nbits, pad;     /* eligible bit positions */
+    uint64_t classes[FI_N_STRUCT];   /* per structure (0: not selected) */
+} fi_exact_info;
+typedef struct { uint32_t inst, weight; } fi_exact_class;
+
+/* Pure host function (no device, no engine): register reg's classes of the
+ * index (off33: 33 offsets, ev: the entries) of a golden run of ninst
+ * instructions, in time order.  Copies up to cap classes to out (may be NULL);
+ * *n = their number, *dead = dead_r (either may be NULL). */
+fi_status fi_exact_classes(const uint32_t *off33, const uint32_t *ev, uint64_t ninst, uint32_t reg,
+                           fi_exact_class *out, uint64_t cap, uint64_t *n, uint64_t *dead);
+/* The space and the trial count under the current fi_set_campaign / fi_set_bits settings. */
+fi_status fi_exact_get_info(fi_engine *e, fi_exact_info *out);
+/* The sites of exact trials [first, first + n) and the number of sites each stands for. */
+fi_status fi_exact_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site *sites, uint32_t *weights);
+/* Run exact trials [first, first + n), first + n <= fi_exact_info.trials.  out
+ * (n entries, trial order) may be NULL.  hist is accumulated into with
+ * weights: a trial counts weight times in counts, crash_sub, escape_sub and
+ * trials and adds weight x its numInst to guest_insts.  The dead sites are
+ * added by the call with first == 0 (also when n == 0) and by no other, so
+ * disjoint ranges that cover [0, trials) sum to the whole space, where
+ * counts.sum() == hist.trials == fi_exact_info.space.  guest_insts is a
+ * 64-bit sum and wraps modulo 2^64 (not below about 2^25 golden
+ * instructions).  The traffic diagnostics (fetch_bytes, data_bytes,
+ * cow_pages, device_insts) stay unweighted: they describe what the device
+ * ran. */
+fi_status fi_run_exact(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist);
+
 /* Output capture.  A trial's stdout (stderr) stream is every byte its run
  * writes to fd 1 (fd 2) from process start (or the checkpoint restore point)
  * to its end: what the serial gem5 run of that site leaves in its output

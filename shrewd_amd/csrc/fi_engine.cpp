@@ -28,6 +28,7 @@
 #include "fi_capture.h"
 #include "fi_checkpoint.h"
 #include "fi_debug.h"
+#include "fi_exact.h"
 #include "fi_golden_host.h"
 #include "fi_site_draw.h"
 #include "fi_tick.h"
@@ -59,6 +60,11 @@ hipError_t launch_debug_loop(const DevCtx &c, const fi_debug_loop *in, uint64_t 
 hipError_t launch_hist(const fi_site *sites, const fi_outcome *out, uint64_t n, fi_histogram *h,
                        const unsigned long long *stats, hipStream_t st);
 hipError_t launch_hist_stats(const unsigned long long *stats, fi_histogram *h, hipStream_t st);
+hipError_t launch_exact_sites(const ExactPlan &p, uint64_t first, uint64_t n, const uint64_t *classes, fi_site *sites,
+                              uint64_t *keys, uint32_t *perm, uint32_t *weight, hipStream_t st);
+hipError_t launch_exact_hist(const fi_site *sites, const fi_outcome *out, const uint32_t *weight, uint64_t n,
+                             fi_histogram *h, hipStream_t st);
+hipError_t launch_exact_dead(const ExactDead &d, fi_histogram *h, hipStream_t st);
 hipError_t sort_pairs_bytes(uint64_t n, size_t &bytes);
 hipError_t launch_pack_runs(const uint64_t *keys, const uint32_t *cnt, uint64_t cap, uint32_t *wrange,
                             uint32_t *n_waves, hipStream_t st);
@@ -200,6 +206,14 @@ struct fi_engine {
     // accesses in order, entry = (2 * numInst + !ecall) << 1 | reads
     uint32_t *d_fw_off = nullptr, *d_fw_ev = nullptr;
     bool fw_ok = false;
+    // exact campaigns (fi_exact.h): the host copy of the index and, built from it at
+    // the first exact call after a golden run, every register's classes (register r's packed words
+    // at ex_off[r] .. ex_off[r + 1]) and dead-site count
+    std::vector<uint32_t> fw_off, fw_ev;
+    bool ex_ok = false;
+    uint32_t ex_off[33] = {};
+    uint64_t ex_dead[32] = {};
+    uint64_t *d_ex_classes = nullptr;
     uint64_t *d_eff = nullptr;       // [cap] effective inject time per trial (kFwDead: dead at injection)
     uint32_t *d_mw_off = nullptr;
     bool pre_ok = true;
@@ -274,6 +288,7 @@ struct fi_engine {
     // work buffers, sized for `cap` trials per launch
     uint64_t cap = 0;
     fi_site *d_sites = nullptr, *d_sites_alt = nullptr;   // the chunk being run / the one being finished
+    uint32_t *d_weight[2] = {nullptr, nullptr};           // an exact chunk's weights, alternating like the sites
     uint64_t *d_keys = nullptr, *d_keys2 = nullptr;
     uint32_t *d_perm = nullptr, *d_perm2 = nullptr;
     void *d_tmp = nullptr;
@@ -465,7 +480,7 @@ fi_status fi_create(const fi_config *cfg, fi_engine **out) {
         // (one block of P' - P pages per 2048 slots)
         size_t free_b = 0, total_b = 0;
         const uint64_t P = e->cfg.private_pages, P2 = redo_pages(P);
-        const uint64_t slot_b = 3 * sizeof(fi_site) + 3 * sizeof(fi_outcome) + 8 * 8 + 8 * 4 + kWaveDbgWords * 8 +
+        const uint64_t slot_b = 3 * sizeof(fi_site) + 3 * sizeof(fi_outcome) + 8 * 8 + 10 * 4 + kWaveDbgWords * 8 +
                                 sizeof(LaneSave) + sizeof(VmState) + 33 * 8 + kDmapWords * 4 + 4 + 64;
         const uint64_t per = P * (kPage + 8) + slot_b + (P2 > P ? (P2 - P) * (kPage + 8) / 2048 + 1 : 0);
         uint64_t cap = 65536;
@@ -487,7 +502,7 @@ static void free_capture(fi_engine *e) {
 
 static void free_work(fi_engine *e) {
     free_capture(e);
-    dfree(e->d_sites); dfree(e->d_sites_alt); dfree(e->d_out_alt); dfree(e->d_keys); dfree(e->d_keys2); dfree(e->d_perm); dfree(e->d_perm2);
+    dfree(e->d_sites); dfree(e->d_sites_alt); dfree(e->d_weight[0]); dfree(e->d_weight[1]); dfree(e->d_out_alt); dfree(e->d_keys); dfree(e->d_keys2); dfree(e->d_perm); dfree(e->d_perm2);
     dfree(e->d_tmp); dfree(e->d_out); dfree(e->d_hist); dfree(e->d_stats); dfree(e->d_wave_dbg); dfree(e->d_fregs);
     dfree(e->d_inpos);
     dfree(e->d_save); dfree(e->d_surv[0]); dfree(e->d_surv[1]); dfree(e->d_cnt);
@@ -511,8 +526,9 @@ static void free_tick_table(fi_engine *e) {
     dfree(e->d_tk_done); dfree(e->d_tk_rec);
 }
 static void free_fw(fi_engine *e) {
-    dfree(e->d_fw_off); dfree(e->d_fw_ev); dfree(e->d_loops);
-    e->fw_ok = false;
+    dfree(e->d_fw_off); dfree(e->d_fw_ev); dfree(e->d_loops); dfree(e->d_ex_classes);
+    e->fw_ok = e->ex_ok = false;
+    e->fw_off.clear(); e->fw_ev.clear();
     e->n_loops = 0;
 }
 static void free_tx(fi_engine *e) {
@@ -948,6 +964,8 @@ static fi_status ensure_work(fi_engine *e, uint64_t n) {
     const uint64_t c = n;
     HIPCHK(hipMalloc(&e->d_sites, c * sizeof(fi_site)));
     HIPCHK(hipMalloc(&e->d_sites_alt, c * sizeof(fi_site)));
+    HIPCHK(hipMalloc(&e->d_weight[0], c * 4));
+    HIPCHK(hipMalloc(&e->d_weight[1], c * 4));
     HIPCHK(hipMalloc(&e->d_keys, c * 8));
     HIPCHK(hipMalloc(&e->d_keys2, c * 8));
     HIPCHK(hipMalloc(&e->d_perm, c * 4));
@@ -1365,6 +1383,8 @@ static fi_status golden_first_access(fi_engine *e, const GoldenCapture &g, bool 
     HIPCHK(hipMalloc(&e->d_fw_ev, std::max<size_t>(ev.size(), 1) * 4));
     HIPCHK(hipMemcpy(e->d_fw_off, off.data(), 33 * 4, hipMemcpyHostToDevice));
     if (!ev.empty()) HIPCHK(hipMemcpy(e->d_fw_ev, ev.data(), ev.size() * 4, hipMemcpyHostToDevice));
+    e->fw_off = std::move(off);
+    e->fw_ev = std::move(ev);
     e->fw_ok = true;
     return FI_OK;
 }
@@ -1812,6 +1832,7 @@ struct Chunk {
     const fi_site *tsites = nullptr;
     const uint8_t *disp = nullptr;
     const fi_outcome *res = nullptr;
+    const uint32_t *weight = nullptr; // an exact chunk: the sites each trial stands for (the weighted histogram)
     uint32_t slot = 0;                // redo list / count / event pair
     uint64_t off = 0;                 // a capture call: the chunk's first trial (row of the caller's arrays)
     bool capture = false;             //   and its output goes to the capture buffers of `slot`
@@ -1859,7 +1880,8 @@ static fi_status chunk_end(fi_engine *e, const Chunk &ch, fi_histogram *d_hist, 
     }
     // (a redo trial is never a parked one: those end masked, not as resource escapes)
     if (ch.disp) HIPCHK(launch_tick_fix(ch.disp, ch.res, ch.k, ch.out, st));
-    HIPCHK(launch_hist(ch.tsites ? ch.tsites : ch.sites, ch.out, ch.k, d_hist, nullptr, st));
+    if (ch.weight) HIPCHK(launch_exact_hist(ch.sites, ch.out, ch.weight, ch.k, d_hist, st));
+    else HIPCHK(launch_hist(ch.tsites ? ch.tsites : ch.sites, ch.out, ch.k, d_hist, nullptr, st));
     if (ch.host_out) {
         if (!e->h_stage[ch.slot]) HIPCHK(hipHostMalloc(&e->h_stage[ch.slot], e->cap * sizeof(fi_outcome)));
         HIPCHK(hipMemcpyAsync(e->h_stage[ch.slot], ch.out, ch.k * sizeof(fi_outcome), hipMemcpyDeviceToHost, st));
@@ -1917,12 +1939,14 @@ static TickMapCtx tick_map_ctx(fi_engine *e, uint64_t first, const fi_tick_site 
 // Where a run's sites come from: given (host arrays of n entries), or sampled
 // on the device as trials first, first + 1, ...  A tick run's sites are tick
 // sites: mapped by the caller (sites) or, in the sampler's place, on the
-// device (ticks / sampled).
+// device (ticks / sampled).  exact: trials first, first + 1, ... of that plan,
+// enumerated on the device in the sampler's place (fi_run_exact).
 struct SiteSource {
     const fi_site *sites = nullptr;
     const fi_tick_site *ticks = nullptr;
     bool sampled = false;
     bool tick = false;
+    const ExactPlan *exact = nullptr;
 };
 
 // Trials [first, first + n) or the given sites (src), in chunks of at most
@@ -1959,6 +1983,10 @@ static fi_status run_chunks(fi_engine *e, uint64_t first, const SiteSource &src,
             }
             HIPCHK(launch_tick_map(tick_map_ctx(e, first + done, in), ch.k, ch.sites, e->d_keys, e->d_perm,
                                    e->d_tk_sites[ch.slot], e->d_tk_disp[ch.slot], e->d_tk_res[ch.slot], st));
+        } else if (src.exact) {
+            ch.weight = e->d_weight[ch.slot];
+            HIPCHK(launch_exact_sites(*src.exact, first + done, ch.k, e->d_ex_classes, ch.sites, e->d_keys, e->d_perm,
+                                      e->d_weight[ch.slot], st));
         } else {
             HIPCHK(launch_sample(sample_ctx(e, first + done), ch.k, ch.sites, e->d_keys, e->d_perm, st));
         }
@@ -2035,6 +2063,128 @@ fi_status fi_run_sites(fi_engine *e, const fi_site *sites, uint64_t n, fi_outcom
     if (!sites && n) return FI_E_ARG;
     // (no sites: an empty sampled run)
     return run_common(e, 0, SiteSource{sites, nullptr, !sites, false}, n, out, hist);
+}
+
+// ---- Exact campaigns (the classes and the trial ids: fi_exact.h)
+fi_status fi_exact_classes(const uint32_t *off33, const uint32_t *ev, uint64_t ninst, uint32_t reg,
+                           fi_exact_class *out, uint64_t cap, uint64_t *n, uint64_t *dead) {
+    if (!off33 || (!ev && off33[32]) || reg < 1 || reg > 31 || ninst >= (1ULL << kExactInstBits)) return FI_E_ARG;
+    std::vector<uint64_t> w(out ? (size_t)std::min<uint64_t>(cap, off33[reg + 1] - off33[reg]) : 0);
+    uint64_t d = 0;
+    const uint64_t cnt = exact_reg_classes(off33, ev, ninst, reg, w.data(), w.size(), &d);
+    for (size_t i = 0; i < w.size() && i < cnt; i++) {
+        out[i].inst = (uint32_t)exact_word_inst(w[i]);
+        out[i].weight = exact_word_weight(w[i]);
+    }
+    if (n) *n = cnt;
+    if (dead) *dead = d;
+    return FI_OK;
+}
+
+// Every register's classes, once per golden run: packed, uploaded beside d_fw_ev.
+static fi_status exact_build(fi_engine *e) {
+    if (e->ex_ok) return FI_OK;
+    std::vector<uint64_t> words;
+    for (uint32_t r = 1; r < 32; r++) {
+        e->ex_off[r] = (uint32_t)words.size();
+        const uint64_t cnt = exact_reg_classes(e->fw_off.data(), e->fw_ev.data(), e->golden.ninst, r, nullptr, 0,
+                                               &e->ex_dead[r]);
+        words.resize(words.size() + cnt);
+        exact_reg_classes(e->fw_off.data(), e->fw_ev.data(), e->golden.ninst, r, words.data() + e->ex_off[r], cnt,
+                          nullptr);
+    }
+    e->ex_off[0] = 0;
+    e->ex_off[32] = (uint32_t)words.size();
+    dfree(e->d_ex_classes);
+    HIPCHK(hipMalloc(&e->d_ex_classes, std::max<size_t>(words.size(), 1) * 8));
+    if (!words.empty()) HIPCHK(hipMemcpy(e->d_ex_classes, words.data(), words.size() * 8, hipMemcpyHostToDevice));
+    e->ex_ok = true;
+    return FI_OK;
+}
+
+// The checks every exact entry point shares, then the campaign's plan, its
+// dead sites and (info, may be NULL) its sizes.
+static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, ExactDead &dd, fi_exact_info *info) {
+    if (!e) return FI_E_ARG;
+    if (!e->have_golden) return fail(e, FI_E_STATE, "%s: golden run required", who);
+    if (!e->structures) return fail(e, FI_E_STATE, "%s: fi_set_campaign first", who);
+    if (e->structures & (1ULL << FI_T_MEM))
+        return fail(e, FI_E_ARG, "%s: memory words (structure %d) have no exact classes; select registers, "
+                    "the pc and instruction results", who, FI_T_MEM);
+    if (e->cpu_model != FI_CPU_ATOMIC)
+        return fail(e, FI_E_STATE, "%s: exact campaigns enumerate numInst sites (the CPU model is TimingSimpleCPU)", who);
+    if (!e->fw_ok)
+        return fail(e, FI_E_STATE, "%s: the golden run has no first-access index (a golden trace that is incomplete "
+                    "or 2^29 instructions or more)", who);
+    HIPCHK(hipSetDevice(e->dev));
+    fi_status s = exact_build(e);
+    if (s) return s;
+    dd = ExactDead{};
+    fi_exact_info x{};
+    const uint64_t ninst = e->golden.ninst;
+    p = exact_plan(e->structures, e->ex_off, ninst, e->bits, e->burst, x.classes);
+    for (uint32_t t = 1; t < FI_N_STRUCT; t++) {
+        if (!((e->structures >> t) & 1)) continue;
+        x.space += ninst * p.nbits;
+        if (t < 32) {
+            dd.dead[t] = (uint32_t)e->ex_dead[t];
+            x.dead_sites += e->ex_dead[t] * p.nbits;
+        }
+    }
+    x.trials = p.trials;
+    x.nbits = p.nbits;
+    dd.bits = p.bits; dd.total = x.dead_sites; dd.golden_ninst = ninst;
+    if (p.trials >= kExactMaxTrials) return fail(e, FI_E_ARG, "%s: 2^40 exact trials or more", who);
+    if (info) *info = x;
+    return FI_OK;
+}
+
+fi_status fi_exact_get_info(fi_engine *e, fi_exact_info *out) {
+    if (!e || !out) return FI_E_ARG;
+    ExactPlan p;
+    ExactDead dd;
+    return exact_prepare(e, "fi_exact_get_info", p, dd, out);
+}
+
+fi_status fi_exact_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site *sites, uint32_t *weights) {
+    if (!e || (n && !sites)) return FI_E_ARG;
+    ExactPlan p;
+    ExactDead dd;
+    fi_status s = exact_prepare(e, "fi_exact_sites", p, dd, nullptr);
+    if (s) return s;
+    if (first > p.trials || n > p.trials - first)
+        return fail(e, FI_E_ARG, "fi_exact_sites: trials [%llu, %llu) outside the campaign's %llu", (unsigned long long)first,
+                    (unsigned long long)(first + n), (unsigned long long)p.trials);
+    s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch));
+    if (s) return s;
+    for (uint64_t done = 0; done < n;) {
+        const uint64_t k = std::min<uint64_t>(n - done, e->cap);
+        HIPCHK(launch_exact_sites(p, first + done, k, e->d_ex_classes, e->d_sites, e->d_keys, e->d_perm, e->d_weight[0],
+                                  e->stream));
+        HIPCHK(hipMemcpyAsync(sites + done, e->d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        if (weights) HIPCHK(hipMemcpyAsync(weights + done, e->d_weight[0], k * 4, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        done += k;
+    }
+    return FI_OK;
+}
+
+fi_status fi_run_exact(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist) {
+    ExactPlan p;
+    ExactDead dd;
+    fi_status s = exact_prepare(e, "fi_run_exact", p, dd, nullptr);
+    if (s) return s;
+    if (first > p.trials || n > p.trials - first)
+        return fail(e, FI_E_ARG, "fi_run_exact: trials [%llu, %llu) outside the campaign's %llu", (unsigned long long)first,
+                    (unsigned long long)(first + n), (unsigned long long)p.trials);
+    s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch));
+    if (s) return s;
+    HIPCHK(hipMemsetAsync(e->d_hist, 0, sizeof(fi_histogram), e->stream));
+    if (first == 0) HIPCHK(launch_exact_dead(dd, e->d_hist, e->stream));   // the sites that need no trial
+    SiteSource src;
+    src.exact = &p;
+    s = run_chunks(e, first, src, n, nullptr, out, e->d_hist, e->stream);
+    return s ? s : run_finish(e, hist);
 }
 
 // Output capture (the sizing and the staging copy: fi_capture.h).

@@ -4,6 +4,7 @@
 //   fi_tick_map_kernel  tick-domain sites: the same draw over ticks, mapped to numInst sites
 //   fi_predecode_kernel decodes every halfword of the golden text once
 //   fi_hist_kernel      outcome histogram (structure x first-bit x class)
+//   fi_exact_*_kernel   exact campaigns: sites by first-access class, the weighted histogram, the dead sites
 //   hipcub radix sort   trials by inject time, so a wave's 64 lanes share the
 //                       golden prefix and start at the same snapshot
 //
@@ -14,6 +15,7 @@
 #include "fi_types.h"
 #include "fi_site_draw.h"
 #include "fi_tick_map.h"
+#include "fi_exact.h"
 #include "fi_device.h"
 #include "rv64_isa.h"
 #include "fi_softfp.h"
@@ -254,6 +256,99 @@ __global__ void __launch_bounds__(256) fi_hist_kernel(const fi_site *sites, cons
     if (lane == 0 && nt) {
         atomicAdd((unsigned long long *)&h->trials, (unsigned long long)nt);
         atomicAdd((unsigned long long *)&h->guest_insts, (unsigned long long)ni);
+    }
+}
+
+// ------------------------------------------------------------------ exact campaigns
+// The sampler's stand-in: thread i takes exact trial first + i (fi_exact.h
+// exact_site: the structure's row, the class word -- shared by the nbits
+// consecutive lanes of a class -- or the synthesised pc / result class, the
+// slot's bit position).  weight[i] = the sites the trial stands for.
+__global__ void __launch_bounds__(256) fi_exact_sites_kernel(ExactPlan p, uint64_t first, uint64_t n,
+                                                             const uint64_t *classes, fi_site *sites, uint64_t *keys,
+                                                             uint32_t *perm, uint32_t *weight) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ExactSite x = exact_site(p, classes, first + i);
+    fi_site s;
+    s.inst = x.inst; s.mask = x.mask; s.addr = 0; s.target = x.target; s.trial = (uint32_t)(first + i);
+    sites[i] = s;
+    keys[i] = s.inst;
+    perm[i] = (uint32_t)i;
+    weight[i] = x.weight;
+}
+
+// fi_hist_kernel with weights: trial i counts weight[i] times in counts,
+// crash_sub, escape_sub and trials, and adds weight[i] x its numInst to
+// guest_insts.  An exact chunk's trials fall into the 64 x FI_N_CLASS bins of
+// one structure (a few where the chunk crosses into the next), so the bins
+// are privatised: the workgroup keeps the table of its first trial's
+// structure in LDS (3 KiB: occupancy stays at the 8 waves/SIMD the registers
+// allow), lanes of that structure add there, lanes of another one -- a block
+// that straddles a segment boundary -- add to global memory directly, and the
+// block flushes its non-zero bins with one global atomic each.  Sub-codes and
+// totals are summed in the wave first.  Integer adds only: the result does
+// not depend on arrival order.
+__global__ void __launch_bounds__(256) fi_exact_hist_kernel(const fi_site *sites, const fi_outcome *out,
+                                                            const uint32_t *weight, uint64_t n, fi_histogram *h) {
+    __shared__ unsigned long long bins[64 * FI_N_CLASS];
+    for (uint32_t b = threadIdx.x; b < 64 * FI_N_CLASS; b += blockDim.x) bins[b] = 0;
+    // (the grid covers n: the block's first trial exists; every lane reads the same word)
+    uint32_t t0 = sites[(uint64_t)blockIdx.x * blockDim.x].target;
+    t0 = t0 < FI_N_STRUCT ? t0 : 0;
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t cls = FI_N_CLASS, sub = 0;
+    uint64_t w = 0, wi = 0;
+    if (i < n) {
+        const fi_site s = sites[i];
+        const fi_outcome o = out[i];
+        const uint32_t t = s.target < FI_N_STRUCT ? s.target : 0;
+        const uint32_t bit = s.mask ? (uint32_t)__builtin_ctzll(s.mask) : 0;
+        cls = o.cls < FI_N_CLASS ? o.cls : FI_ESCAPE;
+        sub = o.sub;
+        w = weight[i];
+        wi = w * o.ninst;
+        if (t == t0) atomicAdd(&bins[bit * FI_N_CLASS + cls], (unsigned long long)w);
+        else atomicAdd((unsigned long long *)&h->counts[t][bit][cls], (unsigned long long)w);
+    }
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t crash = __ballot(cls == FI_CRASH), esc = __ballot(cls == FI_ESCAPE);
+    if (crash) {
+        for (uint32_t k = 0; k < 16; k++) {
+            if (!(crash & __ballot((sub & 15) == k))) continue;   // (wave-uniform)
+            const uint64_t c = wave_sum64(cls == FI_CRASH && (sub & 15) == k ? w : 0);
+            if (c && lane == 0) atomicAdd((unsigned long long *)&h->crash_sub[k], (unsigned long long)c);
+        }
+    }
+    if (esc) {
+        for (uint32_t k = 0; k < 8; k++) {
+            if (!(esc & __ballot((sub & 7) == k))) continue;
+            const uint64_t c = wave_sum64(cls == FI_ESCAPE && (sub & 7) == k ? w : 0);
+            if (c && lane == 0) atomicAdd((unsigned long long *)&h->escape_sub[k], (unsigned long long)c);
+        }
+    }
+    const uint64_t nt = wave_sum64(w), ni = wave_sum64(wi);
+    if (lane == 0 && nt) {
+        atomicAdd((unsigned long long *)&h->trials, (unsigned long long)nt);
+        atomicAdd((unsigned long long *)&h->guest_insts, (unsigned long long)ni);
+    }
+    __syncthreads();
+    unsigned long long *g = (unsigned long long *)&h->counts[t0][0][0];
+    for (uint32_t b = threadIdx.x; b < 64 * FI_N_CLASS; b += blockDim.x)
+        if (bins[b]) atomicAdd(&g[b], bins[b]);
+}
+
+// The dead sites of an exact campaign (no trial: the golden run, masked):
+// block r, thread b adds register r's dead count to counts[r][b][FI_MASKED]
+// for every selected r and eligible b; the totals by one thread.
+__global__ void __launch_bounds__(64) fi_exact_dead_kernel(ExactDead d, fi_histogram *h) {
+    const uint32_t r = blockIdx.x, b = threadIdx.x;
+    const uint32_t c = d.dead[r];
+    if (c && ((d.bits >> b) & 1)) atomicAdd((unsigned long long *)&h->counts[r][b][FI_MASKED], (unsigned long long)c);
+    if (r == 0 && b == 0 && d.total) {
+        atomicAdd((unsigned long long *)&h->trials, (unsigned long long)d.total);
+        atomicAdd((unsigned long long *)&h->guest_insts, (unsigned long long)(d.total * d.golden_ninst));
     }
 }
 
@@ -498,6 +593,21 @@ hipError_t launch_hist(const fi_site *sites, const fi_outcome *out, uint64_t n, 
                        const unsigned long long *stats, hipStream_t st) {
     hipLaunchKernelGGL(fi_hist_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, sites, out, n, h);
     if (stats) hipLaunchKernelGGL(fi_hist_stats_kernel, dim3(1), dim3(64), 0, st, stats, h);
+    return hipGetLastError();
+}
+hipError_t launch_exact_sites(const ExactPlan &p, uint64_t first, uint64_t n, const uint64_t *classes, fi_site *sites,
+                              uint64_t *keys, uint32_t *perm, uint32_t *weight, hipStream_t st) {
+    hipLaunchKernelGGL(fi_exact_sites_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, p, first, n, classes, sites, keys,
+                       perm, weight);
+    return hipGetLastError();
+}
+hipError_t launch_exact_hist(const fi_site *sites, const fi_outcome *out, const uint32_t *weight, uint64_t n,
+                             fi_histogram *h, hipStream_t st) {
+    hipLaunchKernelGGL(fi_exact_hist_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, sites, out, weight, n, h);
+    return hipGetLastError();
+}
+hipError_t launch_exact_dead(const ExactDead &d, fi_histogram *h, hipStream_t st) {
+    hipLaunchKernelGGL(fi_exact_dead_kernel, dim3(32), dim3(64), 0, st, d, h);
     return hipGetLastError();
 }
 hipError_t launch_hist_stats(const unsigned long long *stats, fi_histogram *h, hipStream_t st) {

@@ -43,6 +43,7 @@ HIST_DT = np.dtype([("counts", "<u8", (N_STRUCT, 64, 6)), ("crash_sub", "<u8", (
                     ("trials", "<u8"), ("guest_insts", "<u8"), ("fetch_bytes", "<u8"), ("data_bytes", "<u8"),
                     ("cow_pages", "<u8"), ("device_insts", "<u8")])
 STREAM_LEN_DT = np.dtype([("out_len", "<u8"), ("err_len", "<u8")])
+EXACT_CLASS_DT = np.dtype([("inst", "<u4"), ("weight", "<u4")])   # fi_exact_class
 
 
 class Capture:
@@ -152,6 +153,16 @@ class GoldenInfo(C.Structure):
                 ("translated_insts", C.c_uint64), ("translate_us", C.c_uint64)]
 
 
+class ExactInfo(C.Structure):
+    """fi_exact_info: the sizes of an exact campaign (Engine.exact_info)."""
+    _fields_ = [("space", C.c_uint64), ("trials", C.c_uint64), ("dead_sites", C.c_uint64), ("nbits", C.c_uint32),
+                ("pad", C.c_uint32), ("classes", C.c_uint64 * N_STRUCT)]
+
+    def as_dict(self) -> dict:
+        return {"space": int(self.space), "trials": int(self.trials), "dead_sites": int(self.dead_sites),
+                "nbits": int(self.nbits), "classes": {s: int(c) for s, c in enumerate(self.classes) if c}}
+
+
 class IssueParams(C.Structure):
     """fi_issue_params: the O3 issue model of SHREWD's FU contention."""
     _fields_ = [("issue_width", C.c_uint32), ("dispatch_width", C.c_uint32), ("commit_width", C.c_uint32),
@@ -236,6 +247,24 @@ def timing_model_run(ops: np.ndarray, params: TimingParams | None = None):
     if rc != FI_OK:
         raise EngineError(f"fi_timing_model_run: {rc}")
     return out, st
+
+
+def exact_classes(off, ev, ninst: int, reg: int):
+    """fi_exact_classes (pure host code): register reg's first-access classes
+    of the index (off: 33 offsets, ev: entries (2 * numInst + !ecall) << 1 |
+    reads) of a golden run of ninst instructions
+    -> (EXACT_CLASS_DT[n] in time order, dead sites of the register)."""
+    off = np.ascontiguousarray(off, np.uint32)
+    ev = np.ascontiguousarray(ev, np.uint32)
+    if len(off) != 33 or int(off[32]) > len(ev):
+        raise ValueError("exact_classes: off has 33 entries and off[32] <= len(ev)")
+    n, dead = C.c_uint64(), C.c_uint64()
+    out = np.zeros(int(off[reg + 1]) - int(off[reg]) if 1 <= reg <= 31 else 0, EXACT_CLASS_DT)
+    rc = lib().fi_exact_classes(off.ctypes.data, ev.ctypes.data, ninst, reg, out.ctypes.data, len(out),
+                                C.byref(n), C.byref(dead))
+    if rc != FI_OK:
+        raise EngineError(f"fi_exact_classes: {rc}")
+    return out[:n.value].copy(), int(dead.value)
 
 
 ISSUE_PLAIN, ISSUE_LOAD, ISSUE_STORE, ISSUE_SERIAL = 0, 1, 2, 3
@@ -324,6 +353,11 @@ def lib():
         L.fi_sample_sites.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
         L.fi_run_trials.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
         L.fi_run_sites.argtypes = [vp, vp, C.c_uint64, vp, vp]
+        L.fi_exact_classes.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64, C.POINTER(C.c_uint64),
+                                       C.POINTER(C.c_uint64)]
+        L.fi_exact_get_info.argtypes = [vp, C.POINTER(ExactInfo)]
+        L.fi_exact_sites.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
+        L.fi_run_exact.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
         L.fi_run_sites_capture.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp]
         L.fi_run_trials_device.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp]
         L.fi_sync.argtypes = [vp]
@@ -625,6 +659,30 @@ class Engine:
         hist = np.zeros(1, HIST_DT)
         self._chk(self.L.fi_run_sites(self.h, sites.ctypes.data, len(sites), out.ctypes.data, hist.ctypes.data),
                   "fi_run_sites")
+        return out, hist[0]
+
+    # ---- exact campaigns: one trial per first-access class (include/fi_engine.h)
+    def exact_info(self) -> ExactInfo:
+        """fi_exact_get_info: the space, the trial count, the dead sites and
+        the classes per structure under set_campaign / set_bits."""
+        x = ExactInfo()
+        self._chk(self.L.fi_exact_get_info(self.h, C.byref(x)), "fi_exact_get_info")
+        return x
+
+    def exact_sites(self, first: int, n: int):
+        """-> (sites of exact trials [first, first + n), the sites each stands for)"""
+        sites = np.zeros(n, SITE_DT)
+        w = np.zeros(n, np.uint32)
+        self._chk(self.L.fi_exact_sites(self.h, first, n, sites.ctypes.data, w.ctypes.data), "fi_exact_sites")
+        return sites, w
+
+    def run_exact(self, first: int, n: int, want_outcomes: bool = True):
+        """fi_run_exact: exact trials [first, first + n) -> (outcomes, weighted
+        histogram); the range that starts at 0 also counts the dead sites."""
+        out = np.zeros(n, OUTCOME_DT) if want_outcomes else None
+        hist = np.zeros(1, HIST_DT)
+        self._chk(self.L.fi_run_exact(self.h, first, n, out.ctypes.data if out is not None else None,
+                                      hist.ctypes.data), "fi_run_exact")
         return out, hist[0]
 
     def run_sites_capture(self, sites: np.ndarray, cap_bytes: int = 4096, stderr: bool = True):
@@ -956,6 +1014,40 @@ class FaultCampaign:
         if self.output:
             np.save(self.output if world == 1 else f"{self.output}.rank{rank}", self.outcomes)
         return self.outcomes
+
+    def run_exact(self):
+        """The campaign's whole fault space instead of `trials` samples: one
+        trial per first-access class, weighted by the class's size
+        (Engine.run_exact; registers, the pc and instruction results, the
+        atomic CPU model).  Shards the exact trial ids like run(); only rank
+        0's range starts at 0 and counts the dead sites, and the histogram is
+        all-reduced the same way.  summary() and vulnerability() read it."""
+        n = int(self.engine.exact_info().trials)
+        rank, world = 0, 1
+        if self.num_gpus > 1:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                rank, world = dist.get_rank(), dist.get_world_size()
+        lo, cnt = shard_range(n, world, rank)
+        self.first = lo
+        self.outcomes, self._hist = self.engine.run_exact(lo, cnt)
+        if world > 1:
+            import torch
+            import torch.distributed as dist
+            dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else None
+            self._hist = allreduce_histogram(self._hist, dev)
+        if self.output:
+            np.save(self.output if world == 1 else f"{self.output}.rank{rank}", self.outcomes)
+        return self.outcomes
+
+    def vulnerability(self) -> dict:
+        """Per selected structure, the six outcome-class shares of its sites
+        after run_exact(): counts[s].sum(bits) / (ninst x eligible bits)."""
+        x = self.engine.exact_info()
+        per = int(self.golden.ninst) * int(x.nbits)
+        h = self._hist["counts"]
+        return {s: {CLASS_NAMES[c]: int(h[s, :, c].sum()) / per for c in range(6)}
+                for s in range(1, N_STRUCT) if (structures_mask(self.structures) >> s) & 1}
 
     def outputs(self, trials, max_bytes: int = 4096) -> dict:
         """What the given trials printed: {trial: (outcome, stdout, stderr)},
