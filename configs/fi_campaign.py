@@ -53,11 +53,16 @@ def parse(argv=None):
     ap.add_argument("--exact", action="store_true",
                     help="cover the whole fault space instead of --trials samples: one trial per first-access "
                          "class, weighted (registers, pc, result; --cpu-type atomic; the ctypes path)")
+    ap.add_argument("--exact-memory", action="store_true",
+                    help="--exact, and also cover the memory words (structure mem) by byte-liveness class "
+                         "(the ctypes path)")
     ap.add_argument("--num-gpus", type=int, default=1)
     ap.add_argument("--max-insts-factor", type=float, default=2.0)
     ap.add_argument("--private-pages", type=int, default=16)
     ap.add_argument("--output", default="")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    a.exact = a.exact or a.exact_memory
+    return a
 
 
 def _split(s):
@@ -108,7 +113,7 @@ def run_ctypes(a):
                       shadow_fu_model=a.shadow_fu_model, priority_to_shadow=a.priority_to_shadow, checkpoint=a.checkpoint,
                       issue_params={"issue_width": a.issue_width, "load_latency": a.load_latency},
                       input=a.input, executable=a.executable or None, cpu_type=a.cpu_type,
-                      tick_map=a.tick_map, tick_contract=a.tick_contract)
+                      tick_map=a.tick_map, tick_contract=a.tick_contract, exact_memory=a.exact_memory)
     t0 = time.perf_counter()
     if a.exact:
         c.run_exact()

@@ -632,8 +632,8 @@ fi_status fi_run_sites(fi_engine *e, const fi_site *sites, uint64_t n, fi_outcom
  *    the weights.
  *  - The pc (FI_T_PC) and an instruction's result (FI_T_RESULT): one class of
  *    weight 1 per t, no dead sites.
- *  - Memory words (FI_T_MEM) have no classes here: a campaign that selects
- *    them is refused with FI_E_ARG.
+ *  - Memory words (FI_T_MEM) are opt-in (fi_set_exact_memory below); without
+ *    it a campaign that selects them is refused with FI_E_ARG.
  * Exact trial id k counts through the selected structures in ascending
  * number, within a structure through its classes in time order, within a
  * class through the eligible positions ascending: k = class index x nbits +
@@ -678,6 +678,70 @@ fi_status fi_exact_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site *site
  * cow_pages, device_insts) stay unweighted: they describe what the device
  * ran. */
 fi_status fi_run_exact(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist);
+
+/* ---- Exact campaigns over memory words, by byte-liveness class.
+ *
+ * fi_set_exact_memory(e, 1): an exact campaign that selects FI_T_MEM includes
+ * it (default 0: refused as above; a campaign that does not select FI_T_MEM is
+ * the same campaign either way, id for id).
+ *  - The space: every 8-byte word of the memory-fault candidate pages (those
+ *    fi_run_trials draws from, 512 words each) x t x eligible position.  Words
+ *    that overlap the text are left out (fetches are not in the memory index,
+ *    so they have no classes); fi_exact_mem_info.text_words counts them.
+ *  - A position b flips the bytes F(b) = { b / 8 .. (b + burst - 1) / 8 }.
+ *    Eligible positions with equal F form a byte set; byte sets are ordered by
+ *    their lowest position.
+ *  - A word's events of the golden run's memory index (fi_golden_mem_index:
+ *    numInst << 16 | bytes read << 8 | bytes written, in time order), walked
+ *    backwards: live_after(last) = 0, live_before(i) = rd_i | (live_after(i) &
+ *    ~wr_i), live_after(i - 1) = live_before(i).
+ *  - For a word and a byte set F, the events with (rd | wr) & F != 0 in order:
+ *    u'_i = min(ev_i >> 16, ninst - 1), prev'_i = u'_{i-1} (-1 for the first).
+ *    Entry i heads an interval over t in (prev'_i, u'_i] iff u'_i > prev'_i.
+ *    If F & live_before(i) != 0 the interval is a class: one trial per position
+ *    of the byte set at inst = u'_i, addr = the word, weight u'_i - prev'_i.
+ *    Otherwise its sites are dead, as are those after the last such event and
+ *    every site of a word the index does not list; a dead site counts as the
+ *    golden run without a trial.
+ * Trial ids: memory comes after the pc and before the result; inside it byte
+ * sets in their order, within one the words by ascending address, within a
+ * word its classes in time order, within a class the set's positions
+ * ascending.  fi_exact_info.classes[FI_T_MEM], space (+ words x ninst x
+ * nbits), trials and dead_sites include memory.
+ *
+ * Turning it on needs a golden run under the atomic CPU model whose memory
+ * index is complete and which unmapped nothing (munmap, a shrinking brk): the
+ * candidate pages are mapped at process start, so every word then stays mapped
+ * from a site's t to its next access, which is what moving the site there
+ * rests on.  Else FI_E_STATE, and the message says which.  FI_CFG_NO_FORWARD
+ * and FI_CFG_NO_EARLY_EXIT do not turn it off. */
+fi_status fi_set_exact_memory(fi_engine *e, int on);
+typedef struct {
+    uint64_t words;          /* words in the space */
+    uint64_t text_words;     /* candidate-page words left out: they overlap the text */
+    uint64_t index_words;    /* words the golden run's memory index lists */
+    uint32_t byte_sets, pad;
+    double build_ms;         /* host time of the one-time class build on the device */
+    struct {
+        uint32_t bytes, pad;     /* F, a bit per byte */
+        uint64_t positions;      /* the set's eligible positions */
+        uint64_t classes;
+        uint64_t dead_sites;     /* dead (word, t) pairs x the set's positions */
+    } set[64];
+} fi_exact_mem_info;
+/* Under the current fi_set_campaign / fi_set_bits settings; needs fi_set_exact_memory on. */
+fi_status fi_exact_mem_get_info(fi_engine *e, fi_exact_mem_info *out);
+/* Pure host function: the classes of one word's events ev[0 .. n_ev) and one
+ * byte set (byte_mask, 1..0xFF) in a golden run of ninst instructions, in time
+ * order; out, cap, n as fi_exact_classes, *dead = ninst - the weights' sum. */
+fi_status fi_exact_mem_classes(const uint64_t *ev, uint64_t n_ev, uint64_t ninst, uint32_t byte_mask,
+                               fi_exact_class *out, uint64_t cap, uint64_t *n, uint64_t *dead);
+/* The golden run's memory index copied back: the listed words' addresses
+ * (ascending), off (words + 1 offsets into ev) and the events; each array may
+ * be NULL, at most its cap entries are written.  counts[0] = words, counts[1]
+ * = events.  FI_E_STATE without a golden run or with an incomplete index. */
+fi_status fi_golden_mem_index(fi_engine *e, uint64_t *addr, uint64_t addr_cap, uint32_t *off, uint64_t off_cap,
+                              uint64_t *ev, uint64_t ev_cap, uint64_t counts[2]);
 
 /* Output capture.  A trial's stdout (stderr) stream is every byte its run
  * writes to fd 1 (fd 2) from process start (or the checkpoint restore point)

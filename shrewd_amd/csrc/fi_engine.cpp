@@ -65,6 +65,12 @@ hipError_t launch_exact_sites(const ExactPlan &p, uint64_t first, uint64_t n, co
 hipError_t launch_exact_hist(const fi_site *sites, const fi_outcome *out, const uint32_t *weight, uint64_t n,
                              fi_histogram *h, hipStream_t st);
 hipError_t launch_exact_dead(const ExactDead &d, fi_histogram *h, hipStream_t st);
+hipError_t launch_exact_mem_live(const ExactMemCtx &c, uint8_t *live, hipStream_t st);
+hipError_t launch_exact_mem_walk(const ExactMemCtx &c, const ExactMemRow *rows, uint32_t n_rows, const uint8_t *live,
+                                 uint64_t *cnt, unsigned long long *wsum, ExactMemClass *cls, uint32_t emit,
+                                 hipStream_t st);
+hipError_t scan_u64_bytes(uint64_t n, size_t &bytes);
+hipError_t scan_u64(void *tmp, size_t bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t st);
 hipError_t sort_pairs_bytes(uint64_t n, size_t &bytes);
 hipError_t launch_pack_runs(const uint64_t *keys, const uint32_t *cnt, uint64_t cap, uint32_t *wrange,
                             uint32_t *n_waves, hipStream_t st);
@@ -214,6 +220,21 @@ struct fi_engine {
     uint32_t ex_off[33] = {};
     uint64_t ex_dead[32] = {};
     uint64_t *d_ex_classes = nullptr;
+    // memory words (fi_set_exact_memory): the classes of the golden run's memory index under one
+    // (bits, burst), built on the device at the first exact call that needs them (exact_mem_build)
+    bool exact_mem = false;
+    uint64_t mw_nev = 0;             // the index's events
+    struct ExMem {
+        bool ok = false;
+        uint64_t bits = 0;
+        uint32_t burst = 0, n_rows = 0;
+        ExactMemRow rows[kExactMaxMemRows] = {};
+        uint64_t classes[kExactMaxMemRows] = {}, dead[kExactMaxMemRows] = {};   // per byte set; dead: (word, t) pairs
+        uint64_t words = 0, text_words = 0, n_classes = 0;
+        double build_ms = 0;
+        ExactMemRow *d_rows = nullptr;
+        ExactMemClass *d_cls = nullptr;
+    } xm;
     uint64_t *d_eff = nullptr;       // [cap] effective inject time per trial (kFwDead: dead at injection)
     uint32_t *d_mw_off = nullptr;
     bool pre_ok = true;
@@ -519,7 +540,10 @@ static void free_work(fi_engine *e) {
 static void free_snaps(fi_engine *e) { dfree(e->d_snaps); dfree(e->d_tab); dfree(e->d_pool); }
 static void free_mem_index(fi_engine *e) {
     dfree(e->d_mw_addr); dfree(e->d_mw_off); dfree(e->d_mw_ev);
+    dfree(e->xm.d_rows); dfree(e->xm.d_cls);
+    e->xm.ok = false;
     e->mw_n = 0;
+    e->mw_nev = 0;
     e->mem_live = false;
 }
 static void free_tick_table(fi_engine *e) {
@@ -1174,6 +1198,7 @@ static fi_status build_mem_index(fi_engine *e, const std::vector<MemEv> &mev, bo
     HIPCHK(hipMemcpy(e->d_mw_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
     if (!evs.empty()) HIPCHK(hipMemcpy(e->d_mw_ev, evs.data(), evs.size() * 8, hipMemcpyHostToDevice));
     e->mw_n = (uint32_t)addr.size();
+    e->mw_nev = evs.size();
     e->mem_live = true;
     return FI_OK;
 }
@@ -2102,15 +2127,111 @@ static fi_status exact_build(fi_engine *e) {
     return FI_OK;
 }
 
+// Why exact campaigns cannot cover memory words here, or NULL.  The classes
+// rest on what forwarding a memory site rests on (run_pass): a complete access
+// index and a word that stays mapped from the site's t to its next access.  The
+// candidate pages are mapped at process start and leave only through
+// vm_unmap, so "the golden run unmapped nothing" stands for the second --
+// golden_fp, which run_pass uses, would also refuse every golden run that
+// merely writes FP or LR/SC state, which changes nothing about its memory.
+static const char *exact_mem_refusal(const fi_engine *e) {
+    if (e->cpu_model != FI_CPU_ATOMIC) return "the CPU model is TimingSimpleCPU (exact campaigns enumerate numInst sites)";
+    if (!e->mem_live) return "the golden run's memory index is incomplete (the access trace overflowed, or an "
+                             "instruction came from outside the pre-decoded text)";
+    if (e->golden_unmapped) return "the golden run unmapped memory (munmap, a shrinking brk): a word need not stay "
+                                   "mapped up to its next access";
+    return nullptr;
+}
+
+// The memory classes under the campaign's (bits, burst), once per golden run
+// and pair: liveness, count, scan, emit (fi_kernels.hip), then the rows.
+static fi_status exact_mem_build(fi_engine *e) {
+    fi_engine::ExMem &m = e->xm;
+    const uint64_t bits = e->bits & burst_positions(e->burst);
+    if (m.ok && m.bits == bits && m.burst == e->burst) return FI_OK;
+    m.ok = false;
+    dfree(m.d_rows); dfree(m.d_cls);
+    m.n_rows = exact_mem_sets(bits, e->burst, m.rows);
+    m.text_words = exact_mem_text_words(e->mem_pages.data(), e->mem_pages.size(), e->text_lo, e->text_hi);
+    m.words = e->mem_pages.size() * 512 - m.text_words;
+    m.n_classes = 0;
+    const uint64_t ninst = e->golden.ninst, pairs = m.words * ninst;
+    if (m.words && pairs / m.words != ninst) return fail(e, FI_E_ARG, "exact memory: words x ninst overflows");
+    std::vector<uint64_t> offs(m.n_rows + 1, 0), wsum(kExactMaxMemRows, 0);
+    const uint64_t n_cnt = (uint64_t)m.n_rows * e->mw_n + 1;
+    auto t0 = std::chrono::steady_clock::now();
+    if (e->mw_n && m.n_rows) {
+        if (n_cnt >= (1ULL << 31)) return fail(e, FI_E_ARG, "exact memory: 2^31 (byte set, word) pairs or more");
+        ExactMemCtx c{};
+        c.mw_addr = e->d_mw_addr; c.mw_ev = e->d_mw_ev; c.mw_off = e->d_mw_off; c.mw_n = e->mw_n;
+        c.pages = e->d_mem_pages; c.n_pages = e->mem_pages.size();
+        c.text_lo = e->text_lo; c.text_hi = e->text_hi; c.ninst = ninst;
+        uint8_t *d_live = nullptr, *d_tmp = nullptr;
+        uint64_t *d_cnt = nullptr, *d_offs = nullptr, *d_wsum = nullptr;
+        size_t tmp_bytes = 0;
+        hipError_t err = scan_u64_bytes(n_cnt, tmp_bytes);
+        if (err == hipSuccess) err = hipMalloc(&d_live, std::max<uint64_t>(e->mw_nev, 1));
+        if (err == hipSuccess) err = hipMalloc(&d_tmp, std::max<size_t>(tmp_bytes, 1));
+        if (err == hipSuccess) err = hipMalloc(&d_cnt, n_cnt * 8);
+        if (err == hipSuccess) err = hipMalloc(&d_offs, n_cnt * 8);
+        if (err == hipSuccess) err = hipMalloc(&d_wsum, kExactMaxMemRows * 8);
+        if (err == hipSuccess) err = hipMalloc(&m.d_rows, kExactMaxMemRows * sizeof(ExactMemRow));
+        hipStream_t st = e->stream;
+        if (err == hipSuccess) err = hipMemsetAsync(d_cnt + (n_cnt - 1), 0, 8, st);
+        if (err == hipSuccess) err = hipMemsetAsync(d_wsum, 0, kExactMaxMemRows * 8, st);
+        if (err == hipSuccess) err = hipMemcpyAsync(m.d_rows, m.rows, m.n_rows * sizeof(ExactMemRow), hipMemcpyHostToDevice, st);
+        if (err == hipSuccess) err = launch_exact_mem_live(c, d_live, st);
+        if (err == hipSuccess) err = launch_exact_mem_walk(c, m.d_rows, m.n_rows, d_live, d_cnt,
+                                                           (unsigned long long *)d_wsum, nullptr, 0, st);
+        if (err == hipSuccess) err = scan_u64(d_tmp, tmp_bytes, d_cnt, d_offs, n_cnt, st);
+        // the offsets at the rows' starts and the total: every mw_n-th entry
+        if (err == hipSuccess) err = hipStreamSynchronize(st);
+        if (err == hipSuccess) err = hipMemcpy2D(offs.data(), 8, d_offs, (size_t)e->mw_n * 8, 8, m.n_rows + 1,
+                                                 hipMemcpyDeviceToHost);
+        if (err == hipSuccess) err = hipMemcpy(wsum.data(), d_wsum, kExactMaxMemRows * 8, hipMemcpyDeviceToHost);
+        const uint64_t total = offs[m.n_rows];
+        if (err == hipSuccess && total < (1ULL << 32)) {
+            err = hipMalloc(&m.d_cls, std::max<uint64_t>(total, 1) * sizeof(ExactMemClass));
+            if (err == hipSuccess && total)
+                err = launch_exact_mem_walk(c, m.d_rows, m.n_rows, d_live, d_offs, nullptr, m.d_cls, 1, st);
+            if (err == hipSuccess) err = hipStreamSynchronize(st);
+        }
+        (void)hipFree(d_live); (void)hipFree(d_tmp); (void)hipFree(d_cnt); (void)hipFree(d_offs); (void)hipFree(d_wsum);
+        if (err != hipSuccess) return fail(e, FI_E_HIP, "exact memory classes: %s", hipGetErrorString(err));
+        if (total >= (1ULL << 32)) return fail(e, FI_E_ARG, "exact memory: 2^32 classes or more");
+    } else {
+        HIPCHK(hipMalloc(&m.d_rows, kExactMaxMemRows * sizeof(ExactMemRow)));
+        HIPCHK(hipMalloc(&m.d_cls, sizeof(ExactMemClass)));
+    }
+    for (uint32_t g = 0; g < m.n_rows; g++) {
+        m.classes[g] = offs[g + 1] - offs[g];
+        m.dead[g] = pairs - wsum[g];
+        m.n_classes += m.classes[g];
+    }
+    // the rows' first trials and class offsets, as every plan will have them
+    ExactPlan scratch{};
+    exact_plan_mem(scratch, m.rows, m.n_rows, m.classes, nullptr, nullptr, nullptr);
+    HIPCHK(hipMemcpy(m.d_rows, m.rows, sizeof m.rows, hipMemcpyHostToDevice));
+    m.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    m.bits = bits; m.burst = e->burst;
+    m.ok = true;
+    return FI_OK;
+}
+
 // The checks every exact entry point shares, then the campaign's plan, its
 // dead sites and (info, may be NULL) its sizes.
 static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, ExactDead &dd, fi_exact_info *info) {
     if (!e) return FI_E_ARG;
     if (!e->have_golden) return fail(e, FI_E_STATE, "%s: golden run required", who);
     if (!e->structures) return fail(e, FI_E_STATE, "%s: fi_set_campaign first", who);
-    if (e->structures & (1ULL << FI_T_MEM))
-        return fail(e, FI_E_ARG, "%s: memory words (structure %d) have no exact classes; select registers, "
-                    "the pc and instruction results", who, FI_T_MEM);
+    const bool mem = (e->structures >> FI_T_MEM) & 1;
+    if (mem && !e->exact_mem)
+        return fail(e, FI_E_ARG, "%s: memory words (structure %d) have no exact classes unless fi_set_exact_memory "
+                    "is on; select registers, the pc and instruction results", who, FI_T_MEM);
+    if (mem) {
+        const char *why = exact_mem_refusal(e);
+        if (why) return fail(e, FI_E_STATE, "%s: exact memory: %s", who, why);
+    }
     if (e->cpu_model != FI_CPU_ATOMIC)
         return fail(e, FI_E_STATE, "%s: exact campaigns enumerate numInst sites (the CPU model is TimingSimpleCPU)", who);
     if (!e->fw_ok)
@@ -2118,6 +2239,7 @@ static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, Exac
                     "or 2^29 instructions or more)", who);
     HIPCHK(hipSetDevice(e->dev));
     fi_status s = exact_build(e);
+    if (!s && mem) s = exact_mem_build(e);
     if (s) return s;
     dd = ExactDead{};
     fi_exact_info x{};
@@ -2125,11 +2247,25 @@ static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, Exac
     p = exact_plan(e->structures, e->ex_off, ninst, e->bits, e->burst, x.classes);
     for (uint32_t t = 1; t < FI_N_STRUCT; t++) {
         if (!((e->structures >> t) & 1)) continue;
+        if (t == FI_T_MEM) continue;
         x.space += ninst * p.nbits;
         if (t < 32) {
             dd.dead[t] = (uint32_t)e->ex_dead[t];
             x.dead_sites += e->ex_dead[t] * p.nbits;
         }
+    }
+    if (mem) {
+        fi_engine::ExMem &m = e->xm;
+        exact_plan_mem(p, m.rows, m.n_rows, m.classes, m.d_rows, m.d_cls, e->d_mw_addr);
+        x.classes[FI_T_MEM] = m.n_classes;
+        x.space += m.words * ninst * p.nbits;
+        for (uint32_t g = 0; g < m.n_rows; g++) {
+            x.dead_sites += m.dead[g] * m.rows[g].npos;
+            for (uint64_t b = m.rows[g].pos; b; b &= b - 1) dd.mem_dead[__builtin_ctzll(b)] = m.dead[g];
+        }
+        uint64_t nc = m.n_classes;
+        for (uint32_t t = 1; t < FI_N_STRUCT; t++) nc += t == FI_T_MEM ? 0 : x.classes[t];
+        if (nc >= (1ULL << 32)) return fail(e, FI_E_ARG, "%s: 2^32 exact classes or more", who);
     }
     x.trials = p.trials;
     x.nbits = p.nbits;
@@ -2144,6 +2280,73 @@ fi_status fi_exact_get_info(fi_engine *e, fi_exact_info *out) {
     ExactPlan p;
     ExactDead dd;
     return exact_prepare(e, "fi_exact_get_info", p, dd, out);
+}
+
+fi_status fi_set_exact_memory(fi_engine *e, int on) {
+    if (!e) return FI_E_ARG;
+    if (on) {
+        if (!e->have_golden) return fail(e, FI_E_STATE, "fi_set_exact_memory: golden run required");
+        const char *why = exact_mem_refusal(e);
+        if (why) return fail(e, FI_E_STATE, "fi_set_exact_memory: %s", why);
+    }
+    e->exact_mem = on != 0;
+    return FI_OK;
+}
+
+fi_status fi_exact_mem_get_info(fi_engine *e, fi_exact_mem_info *out) {
+    if (!e || !out) return FI_E_ARG;
+    if (!e->have_golden) return fail(e, FI_E_STATE, "fi_exact_mem_get_info: golden run required");
+    if (!e->structures) return fail(e, FI_E_STATE, "fi_exact_mem_get_info: fi_set_campaign first");
+    if (!e->exact_mem) return fail(e, FI_E_STATE, "fi_exact_mem_get_info: fi_set_exact_memory is off");
+    const char *why = exact_mem_refusal(e);
+    if (why) return fail(e, FI_E_STATE, "fi_exact_mem_get_info: %s", why);
+    HIPCHK(hipSetDevice(e->dev));
+    fi_status s = exact_mem_build(e);
+    if (s) return s;
+    const fi_engine::ExMem &m = e->xm;
+    *out = fi_exact_mem_info{};
+    out->words = m.words; out->text_words = m.text_words; out->index_words = e->mw_n;
+    out->byte_sets = m.n_rows;
+    out->build_ms = m.build_ms;
+    for (uint32_t g = 0; g < m.n_rows; g++) {
+        out->set[g].bytes = m.rows[g].fmask;
+        out->set[g].positions = m.rows[g].pos;
+        out->set[g].classes = m.classes[g];
+        out->set[g].dead_sites = m.dead[g] * m.rows[g].npos;
+    }
+    return FI_OK;
+}
+
+fi_status fi_exact_mem_classes(const uint64_t *ev, uint64_t n_ev, uint64_t ninst, uint32_t byte_mask,
+                               fi_exact_class *out, uint64_t cap, uint64_t *n, uint64_t *dead) {
+    if ((!ev && n_ev) || n_ev >= (1ULL << 32) || ninst >= (1ULL << kExactInstBits) || !byte_mask || byte_mask > 0xFF)
+        return FI_E_ARG;
+    std::vector<uint8_t> live(n_ev);
+    exact_mem_liveness(ev, (uint32_t)n_ev, live.data());
+    uint64_t sum = 0;
+    const uint64_t cnt = exact_mem_walk(ev, live.data(), (uint32_t)n_ev, ninst, byte_mask, 0, nullptr, 0, &sum);
+    std::vector<ExactMemClass> c(out ? (size_t)std::min(cap, cnt) : 0);
+    exact_mem_walk(ev, live.data(), (uint32_t)n_ev, ninst, byte_mask, 0, c.data(), c.size(), nullptr);
+    for (size_t i = 0; i < c.size(); i++) {
+        out[i].inst = c[i].inst;
+        out[i].weight = c[i].weight;
+    }
+    if (n) *n = cnt;
+    if (dead) *dead = ninst - sum;
+    return FI_OK;
+}
+
+fi_status fi_golden_mem_index(fi_engine *e, uint64_t *addr, uint64_t addr_cap, uint32_t *off, uint64_t off_cap,
+                              uint64_t *ev, uint64_t ev_cap, uint64_t counts[2]) {
+    if (!e) return FI_E_ARG;
+    if (!e->have_golden) return fail(e, FI_E_STATE, "fi_golden_mem_index: golden run required");
+    if (!e->mem_live) return fail(e, FI_E_STATE, "fi_golden_mem_index: the golden run's memory index is incomplete");
+    HIPCHK(hipSetDevice(e->dev));
+    if (counts) { counts[0] = e->mw_n; counts[1] = e->mw_nev; }
+    if (addr) HIPCHK(hipMemcpy(addr, e->d_mw_addr, std::min<uint64_t>(addr_cap, e->mw_n) * 8, hipMemcpyDeviceToHost));
+    if (off) HIPCHK(hipMemcpy(off, e->d_mw_off, std::min<uint64_t>(off_cap, (uint64_t)e->mw_n + 1) * 4, hipMemcpyDeviceToHost));
+    if (ev) HIPCHK(hipMemcpy(ev, e->d_mw_ev, std::min<uint64_t>(ev_cap, e->mw_nev) * 8, hipMemcpyDeviceToHost));
+    return FI_OK;
 }
 
 fi_status fi_exact_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site *sites, uint32_t *weights) {

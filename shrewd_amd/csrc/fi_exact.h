@@ -1,8 +1,8 @@
-// Exact register vulnerability: the fault space of a campaign
+// Exact vulnerability: the fault space of a campaign
 // enumerated by first-access class instead of sampled.  One statement for the
-// host (fi_engine.cpp fi_exact_classes, the plan of fi_run_exact;
-// tools/exact_host_check.cpp) and the device (fi_kernels.hip
-// fi_exact_sites_kernel).
+// host (fi_engine.cpp fi_exact_classes, fi_exact_mem_classes, the plan of
+// fi_run_exact; tools/exact_host_check.cpp, tools/exact_mem_host_check.cpp)
+// and the device (fi_kernels.hip fi_exact_sites_kernel, fi_exact_mem_*_kernel).
 //
 // Register r's entries ev[off[r] .. off[r + 1]) of the first-access index
 // (fi_golden_host.h first_access_index: (2 * numInst + !ecall) << 1 | reads)
@@ -52,6 +52,139 @@ inline uint64_t exact_reg_classes(const uint32_t *off, const uint32_t *ev, uint6
     return n;
 }
 
+// ---- Memory words (FI_T_MEM), by byte-liveness class.
+//
+// Words.  The space is every 8-byte word of the memory-fault candidate pages
+// (512 per page, as fi_sample_kernel draws them) that does not overlap
+// [text_lo, text_hi): mem_dead never calls an instruction word dead and
+// forwarding never moves one (fetches are not in the index), so they have no
+// classes; they are counted (text words) and left out.
+//
+// Byte sets.  A position b flips the bytes F(b) = { b / 8 .. (b + burst - 1) / 8 }
+// -- the fb that fi_forward_kernel and mem_dead compute from the mask.  The
+// eligible positions with equal F form a byte set; F's ends do not decrease
+// with b, so a byte set is a run of consecutive eligible positions and the
+// sets are ordered by their lowest one: at most 15 for burst <= 8, 64 at most.
+//
+// Byte liveness.  A word's events (DevCtx::mw_ev: numInst << 16 | bytes read
+// << 8 | bytes written, in time order) walked backwards: live_after(last) = 0,
+// live_before(i) = rd_i | (live_after(i) & ~wr_i), live_after(i - 1) =
+// live_before(i); an event that reads and writes (an AMO) reads first.  A flip
+// of the bytes F just before event i is dead iff F & live_before(i) == 0 --
+// mem_dead's forward walk, for every byte set at once.
+//
+// Intervals.  For a word and a byte set F, the events that touch F ((rd | wr)
+// & F != 0) in time order -- forwarding stops at the first one: u'_i =
+// min(ev_i >> 16, ninst - 1), prev'_i = u'_{i-1} (-1 before the first); entry
+// i heads an interval iff u'_i > prev'_i, over t in (prev'_i, u'_i].  If F &
+// live_before(i) != 0 the interval is a class: one trial per position of the
+// byte set at inst = u'_i, addr = the word, weight u'_i - prev'_i.  Otherwise
+// every site of it is dead, as are the sites after the last touching event and
+// every site of a word the index does not list.
+struct ExactMemClass {
+    uint32_t word;             // index of the word in DevCtx::mw_addr
+    uint32_t inst, weight, pad;
+};
+struct ExactMemRow {           // a byte set: a row of the plan with its own position count
+    uint64_t first;            // its first trial, counted from the plan's mem_first
+    uint64_t recip;            // class index within the row = (j - first) >> shift, or mulhi(j - first, recip)
+    uint64_t pos;              // its positions
+    uint32_t base;             // its first class in the class array
+    uint32_t npos, shift, fmask;   // fmask: F, a bit per byte
+};
+constexpr uint32_t kExactMaxMemRows = 64;
+
+FI_TM_HD inline uint32_t exact_byte_set(uint32_t b, uint32_t burst) {
+    const uint32_t lo = b >> 3, hi = (b + burst - 1) >> 3;
+    return ((2u << hi) - 1) & ~((1u << lo) - 1) & 0xFF;
+}
+
+// The byte sets of (fi_set_bits mask, burst) in their order: fmask, pos, npos
+// and the quotient constants of rows[0 .. n); returns n.
+inline uint32_t exact_mem_sets(uint64_t bits_mask, uint32_t burst, ExactMemRow *rows) {
+    uint32_t n = 0;
+    for (uint64_t m = bits_mask & burst_positions(burst); m; m &= m - 1) {
+        const uint32_t b = (uint32_t)__builtin_ctzll(m), f = exact_byte_set(b, burst);
+        if (!n || rows[n - 1].fmask != f) {
+            rows[n] = ExactMemRow{};
+            rows[n++].fmask = f;
+        }
+        rows[n - 1].pos |= 1ULL << b;
+    }
+    for (uint32_t g = 0; g < n; g++) {
+        ExactMemRow &r = rows[g];
+        r.npos = (uint32_t)__builtin_popcountll(r.pos);
+        r.shift = 64;
+        if (!(r.npos & (r.npos - 1))) r.shift = (uint32_t)__builtin_ctz(r.npos);
+        else r.recip = ~0ULL / r.npos + 1;
+    }
+    return n;
+}
+
+// Is the word at addr (8-byte aligned) in the space?  pages: the candidate
+// pages, sorted.  (Last bytes, not ends: a page at the top of the address
+// space has no end in 64 bits.)
+FI_TM_HD inline bool exact_mem_in_space(const uint64_t *pages, uint64_t n_pages, uint64_t text_lo, uint64_t text_hi,
+                                        uint64_t addr) {
+    if (addr < text_hi && addr + 7 >= text_lo) return false;
+    uint64_t lo = 0, hi = n_pages;
+    const uint64_t pg = addr & ~4095ULL;
+    while (lo < hi) {
+        const uint64_t mid = (lo + hi) >> 1;
+        if (pages[mid] < pg) lo = mid + 1; else hi = mid;
+    }
+    return lo < n_pages && pages[lo] == pg;
+}
+// The words of the candidate pages that overlap the text
+inline uint64_t exact_mem_text_words(const uint64_t *pages, uint64_t n_pages, uint64_t text_lo, uint64_t text_hi) {
+    uint64_t n = 0;
+    for (uint64_t i = 0; i < n_pages && text_lo < text_hi; i++) {
+        // the first and the last word of the page that overlap [text_lo, text_hi)
+        const uint64_t tf = text_lo & ~7ULL, tl = (text_hi - 1) & ~7ULL, pl = pages[i] + 4088;
+        const uint64_t a = pages[i] > tf ? pages[i] : tf, b = pl < tl ? pl : tl;
+        if (a <= b) n += (b - a) / 8 + 1;
+    }
+    return n;
+}
+
+// live_before of a word's n events (one byte each)
+FI_TM_HD inline void exact_mem_liveness(const uint64_t *ev, uint32_t n, uint8_t *live) {
+    uint32_t l = 0;
+    for (uint32_t i = n; i-- > 0;) {
+        const uint32_t e = (uint32_t)ev[i];
+        l = ((e >> 8) | (l & ~e)) & 0xFF;
+        live[i] = (uint8_t)l;
+    }
+}
+
+// The walk of one (word, byte set): its classes in time order to out[0 ..
+// min(count, cap)) (out may be NULL); returns the count, *wsum = the sum of
+// their weights (the word's other ninst - *wsum sites of the set are dead).
+FI_TM_HD inline uint64_t exact_mem_walk(const uint64_t *ev, const uint8_t *live, uint32_t n, uint64_t ninst,
+                                        uint32_t fmask, uint32_t word, ExactMemClass *out, uint64_t cap,
+                                        uint64_t *wsum) {
+    uint64_t cnt = 0, sum = 0;
+    int64_t prev = -1;
+    for (uint32_t i = 0; ninst && i < n; i++) {
+        const uint64_t e = ev[i];
+        if (!(((e >> 8) | e) & fmask & 0xFF)) continue;
+        const uint64_t t = e >> 16;
+        const int64_t u = (int64_t)(t < ninst - 1 ? t : ninst - 1);
+        if (u > prev && (live[i] & fmask)) {
+            if (out && cnt < cap) {
+                ExactMemClass c;
+                c.word = word; c.inst = (uint32_t)u; c.weight = (uint32_t)(u - prev); c.pad = 0;
+                out[cnt] = c;
+            }
+            cnt++;
+            sum += (uint64_t)(u - prev);
+        }
+        prev = u;
+    }
+    if (wsum) *wsum = sum;
+    return cnt;
+}
+
 // The trial ids of an exact campaign.  k counts through the selected
 // structures in ascending number, within a structure through its classes in
 // time order, within a class through the eligible bit positions ascending:
@@ -72,6 +205,14 @@ struct ExactPlan {
     uint64_t recip;            //   and class index = mulhi(k, recip), recip = floor(2^64 / nbits) + 1
     uint64_t bits;             // the eligible lowest-bit positions (limited to 0 .. 64 - burst)
     uint64_t trials;
+    // memory words (exact_plan_mem; mem_trials = 0 without them): trials [mem_first, mem_first +
+    // mem_trials) between the pc's and the result's, one row per byte set in a table beside the
+    // classes (the rows would not fit a kernel argument); the rows above count past them
+    uint64_t mem_first, mem_trials;
+    const ExactMemRow *mem_rows;
+    const ExactMemClass *mem_cls;
+    const uint64_t *mem_addr;  // the index's word addresses (DevCtx::mw_addr)
+    uint32_t n_mem_rows, pad;
 };
 
 // k / nbits without a 64-bit divide.  nbits <= 64 not a power of two:
@@ -99,6 +240,7 @@ inline ExactPlan exact_plan(uint64_t structures, const uint32_t *cls_off, uint64
     uint64_t q = 0;   // the class index so far
     for (uint32_t t = 1; t < FI_N_STRUCT; t++) {
         if (classes) classes[t] = 0;
+        if (t == FI_T_MEM) p.mem_first = q * p.nbits;   // where exact_plan_mem puts them
         if (!((structures >> t) & 1) || t == FI_T_MEM) continue;
         ExactRow &r = p.row[p.n_rows++];
         r.first = q * p.nbits;
@@ -112,20 +254,77 @@ inline ExactPlan exact_plan(uint64_t structures, const uint32_t *cls_off, uint64
     return p;
 }
 
+// Memory's trials added to a plan: rows[g].base and the classes per row give
+// each row's first trial; ids: byte sets in their order, within one the words
+// by ascending address, within a word its classes in time order, within a
+// class the set's positions ascending.  The tables are the device's (or, in a
+// host check, the host's).
+inline void exact_plan_mem(ExactPlan &p, ExactMemRow *rows, uint32_t n_rows, const uint64_t *row_classes,
+                           const ExactMemRow *tab, const ExactMemClass *cls, const uint64_t *addr) {
+    uint64_t j = 0, base = 0;
+    for (uint32_t g = 0; g < n_rows; g++) {
+        rows[g].first = j;
+        rows[g].base = (uint32_t)base;
+        j += row_classes[g] * rows[g].npos;
+        base += row_classes[g];
+    }
+    p.mem_trials = j;
+    p.trials += j;
+    p.mem_rows = tab; p.mem_cls = cls; p.mem_addr = addr;
+    p.n_mem_rows = n_rows;
+}
+
+// What the class kernels read (fi_kernels.hip fi_exact_mem_*_kernel)
+struct ExactMemCtx {
+    const uint64_t *mw_addr, *mw_ev;   // the memory liveness index (DevCtx::mw_*)
+    const uint32_t *mw_off;
+    const uint64_t *pages;             // the candidate pages, sorted
+    uint64_t n_pages, text_lo, text_hi, ninst;
+    uint32_t mw_n, pad;
+};
+
 // The dead sites of a campaign (fi_exact_dead_kernel)
 struct ExactDead {
     uint32_t dead[32];         // per register (0: not selected)
-    uint64_t bits, total;      // eligible positions; the sum of dead x the eligible positions
+    uint64_t bits, total;      // eligible positions; the sum of dead x the eligible positions (memory's included)
     uint64_t golden_ninst;
+    uint64_t mem_dead[64];     // per position b: the dead (word, t) pairs of b's byte set (0: memory not selected)
 };
 
 struct ExactSite {
-    uint64_t inst, mask;
+    uint64_t inst, mask, addr;
     uint32_t target, weight;
 };
 
+FI_TM_HD inline uint64_t exact_burst_mask(uint32_t burst) { return burst == 64 ? ~0ULL : ((1ULL << burst) - 1); }
+
+// Memory trial j of the plan's memory range (j < p.mem_trials): the last row
+// that starts at or before j (rows ascend; a row without classes starts where
+// the next one does and is never that one), the row's own quotient, the class
+// -- shared by the row's npos consecutive trials -- and the slot's position.
+FI_TM_HD inline ExactSite exact_mem_site(const ExactPlan &p, uint64_t j) {
+    uint32_t lo = 0, hi = p.n_mem_rows;   // first row with first > j
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (p.mem_rows[mid].first <= j) lo = mid + 1; else hi = mid;
+    }
+    const ExactMemRow r = p.mem_rows[lo - 1];
+    const uint64_t jr = j - r.first;
+    const uint64_t c = r.shift < 64 ? jr >> r.shift : mulhi64(jr, r.recip);
+    const ExactMemClass m = p.mem_cls[r.base + (uint32_t)c];
+    uint64_t mm = r.pos;
+    for (uint32_t s = (uint32_t)(jr - c * r.npos); s; s--) mm &= mm - 1;
+    ExactSite x;
+    x.inst = m.inst; x.target = FI_T_MEM; x.weight = m.weight;
+    x.addr = p.mem_addr[m.word];
+    x.mask = exact_burst_mask(p.burst) << (uint32_t)__builtin_ctzll(mm);
+    return x;
+}
+
 // Exact trial k (k < p.trials); classes = every register's packed words
 FI_TM_HD inline ExactSite exact_site(const ExactPlan &p, const uint64_t *classes, uint64_t k) {
+    if (k - p.mem_first < p.mem_trials) return exact_mem_site(p, k - p.mem_first);   // (k < mem_first wraps: no)
+    if (k >= p.mem_first) k -= p.mem_trials;   // the result's trials: counted as without memory
     const uint64_t q = exact_class_index(p, k);
     const uint32_t slot = (uint32_t)(k - q * p.nbits);
     // the last row that starts at or before k (rows ascend; one compare per row, no indexed access)
@@ -137,6 +336,7 @@ FI_TM_HD inline ExactSite exact_site(const ExactPlan &p, const uint64_t *classes
     }
     const uint32_t x = (uint32_t)q + delta;
     ExactSite s;
+    s.addr = 0;
     if (target) {
         s.inst = x; s.target = target; s.weight = 1;
     } else {
@@ -149,7 +349,7 @@ FI_TM_HD inline ExactSite exact_site(const ExactPlan &p, const uint64_t *classes
         for (uint32_t j = slot; j; j--) mm &= mm - 1;
         b = (uint64_t)__builtin_ctzll(mm);
     }
-    s.mask = (p.burst == 64 ? ~0ULL : ((1ULL << p.burst) - 1)) << b;
+    s.mask = exact_burst_mask(p.burst) << b;
     return s;
 }
 

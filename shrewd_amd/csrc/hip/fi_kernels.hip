@@ -4,7 +4,8 @@
 //   fi_tick_map_kernel  tick-domain sites: the same draw over ticks, mapped to numInst sites
 //   fi_predecode_kernel decodes every halfword of the golden text once
 //   fi_hist_kernel      outcome histogram (structure x first-bit x class)
-//   fi_exact_*_kernel   exact campaigns: sites by first-access class, the weighted histogram, the dead sites
+//   fi_exact_*_kernel   exact campaigns: sites by first-access class, the weighted histogram, the dead sites,
+//                       the memory words' byte-liveness classes
 //   hipcub radix sort   trials by inject time, so a wave's 64 lanes share the
 //                       golden prefix and start at the same snapshot
 //
@@ -271,11 +272,47 @@ __global__ void __launch_bounds__(256) fi_exact_sites_kernel(ExactPlan p, uint64
     if (i >= n) return;
     const ExactSite x = exact_site(p, classes, first + i);
     fi_site s;
-    s.inst = x.inst; s.mask = x.mask; s.addr = 0; s.target = x.target; s.trial = (uint32_t)(first + i);
+    s.inst = x.inst; s.mask = x.mask; s.addr = x.addr; s.target = x.target; s.trial = (uint32_t)(first + i);
     sites[i] = s;
     keys[i] = s.inst;
     perm[i] = (uint32_t)i;
     weight[i] = x.weight;
+}
+
+// Memory classes (fi_exact.h "Memory words"), built once per golden run and
+// (bits, burst) from the memory liveness index.  One thread per index word
+// walks its events backwards and stores live_before, a byte per event.
+__global__ void __launch_bounds__(256) fi_exact_mem_live_kernel(ExactMemCtx c, uint8_t *live) {
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= c.mw_n) return;
+    const uint32_t a = c.mw_off[w];
+    exact_mem_liveness(c.mw_ev + a, c.mw_off[w + 1] - a, live + a);
+}
+// One thread per (byte set = blockIdx.y, index word) walks the word's events
+// forwards (exact_mem_walk).  emit = 0: cnt[set * mw_n + word] = its classes,
+// their weights summed per byte set (in the wave first, then one atomic);
+// emit = 1: the classes to cls at the scanned counts.  A word outside the
+// space (a page that is no candidate, an instruction word) has none.
+__global__ void __launch_bounds__(256) fi_exact_mem_walk_kernel(ExactMemCtx c, const ExactMemRow *rows,
+                                                                const uint8_t *live, uint64_t *cnt,
+                                                                unsigned long long *wsum, ExactMemClass *cls,
+                                                                uint32_t emit) {
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x, g = blockIdx.y;
+    uint64_t sum = 0;
+    if (w < c.mw_n) {
+        const uint64_t id = (uint64_t)g * c.mw_n + w;
+        uint64_t n = 0;
+        if (exact_mem_in_space(c.pages, c.n_pages, c.text_lo, c.text_hi, c.mw_addr[w])) {
+            const uint32_t a = c.mw_off[w];
+            const uint64_t at = emit ? cnt[id] : 0;
+            n = exact_mem_walk(c.mw_ev + a, live + a, c.mw_off[w + 1] - a, c.ninst, rows[g].fmask, w,
+                               emit ? cls + at : nullptr, emit ? ~0ULL : 0, &sum);
+        }
+        if (!emit) cnt[id] = n;
+    }
+    if (emit) return;
+    sum = wave_sum64(sum);
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(&wsum[g], (unsigned long long)sum);
 }
 
 // fi_hist_kernel with weights: trial i counts weight[i] times in counts,
@@ -341,11 +378,13 @@ __global__ void __launch_bounds__(256) fi_exact_hist_kernel(const fi_site *sites
 
 // The dead sites of an exact campaign (no trial: the golden run, masked):
 // block r, thread b adds register r's dead count to counts[r][b][FI_MASKED]
-// for every selected r and eligible b; the totals by one thread.
+// for every selected r and eligible b, block 32 the dead (word, t) pairs of
+// b's byte set to counts[FI_T_MEM][b][FI_MASKED]; the totals by one thread.
 __global__ void __launch_bounds__(64) fi_exact_dead_kernel(ExactDead d, fi_histogram *h) {
     const uint32_t r = blockIdx.x, b = threadIdx.x;
-    const uint32_t c = d.dead[r];
-    if (c && ((d.bits >> b) & 1)) atomicAdd((unsigned long long *)&h->counts[r][b][FI_MASKED], (unsigned long long)c);
+    const uint64_t c = r < 32 ? d.dead[r] : d.mem_dead[b];
+    const uint32_t t = r < 32 ? r : (uint32_t)FI_T_MEM;
+    if (c && ((d.bits >> b) & 1)) atomicAdd((unsigned long long *)&h->counts[t][b][FI_MASKED], (unsigned long long)c);
     if (r == 0 && b == 0 && d.total) {
         atomicAdd((unsigned long long *)&h->trials, (unsigned long long)d.total);
         atomicAdd((unsigned long long *)&h->guest_insts, (unsigned long long)(d.total * d.golden_ninst));
@@ -607,8 +646,26 @@ hipError_t launch_exact_hist(const fi_site *sites, const fi_outcome *out, const 
     return hipGetLastError();
 }
 hipError_t launch_exact_dead(const ExactDead &d, fi_histogram *h, hipStream_t st) {
-    hipLaunchKernelGGL(fi_exact_dead_kernel, dim3(32), dim3(64), 0, st, d, h);
+    hipLaunchKernelGGL(fi_exact_dead_kernel, dim3(33), dim3(64), 0, st, d, h);
     return hipGetLastError();
+}
+hipError_t launch_exact_mem_live(const ExactMemCtx &c, uint8_t *live, hipStream_t st) {
+    hipLaunchKernelGGL(fi_exact_mem_live_kernel, dim3(nblk(c.mw_n, 256)), dim3(256), 0, st, c, live);
+    return hipGetLastError();
+}
+hipError_t launch_exact_mem_walk(const ExactMemCtx &c, const ExactMemRow *rows, uint32_t n_rows, const uint8_t *live,
+                                 uint64_t *cnt, unsigned long long *wsum, ExactMemClass *cls, uint32_t emit,
+                                 hipStream_t st) {
+    hipLaunchKernelGGL(fi_exact_mem_walk_kernel, dim3(nblk(c.mw_n, 256), n_rows), dim3(256), 0, st, c, rows, live, cnt,
+                       wsum, cls, emit);
+    return hipGetLastError();
+}
+hipError_t scan_u64_bytes(uint64_t n, size_t &bytes) {
+    bytes = 0;
+    return hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, (const uint64_t *)nullptr, (uint64_t *)nullptr, (int)n);
+}
+hipError_t scan_u64(void *tmp, size_t bytes, const uint64_t *in, uint64_t *out, uint64_t n, hipStream_t st) {
+    return hipcub::DeviceScan::ExclusiveSum(tmp, bytes, in, out, (int)n, st);
 }
 hipError_t launch_hist_stats(const unsigned long long *stats, fi_histogram *h, hipStream_t st) {
     hipLaunchKernelGGL(fi_hist_stats_kernel, dim3(1), dim3(64), 0, st, stats, h);

@@ -163,6 +163,23 @@ class ExactInfo(C.Structure):
                 "nbits": int(self.nbits), "classes": {s: int(c) for s, c in enumerate(self.classes) if c}}
 
 
+class _ExactMemSet(C.Structure):
+    _fields_ = [("bytes", C.c_uint32), ("pad", C.c_uint32), ("positions", C.c_uint64), ("classes", C.c_uint64),
+                ("dead_sites", C.c_uint64)]
+
+
+class ExactMemInfo(C.Structure):
+    """fi_exact_mem_info: the memory words of an exact campaign (Engine.exact_mem_info)."""
+    _fields_ = [("words", C.c_uint64), ("text_words", C.c_uint64), ("index_words", C.c_uint64),
+                ("byte_sets", C.c_uint32), ("pad", C.c_uint32), ("build_ms", C.c_double), ("set", _ExactMemSet * 64)]
+
+    def as_dict(self) -> dict:
+        return {"words": int(self.words), "text_words": int(self.text_words), "index_words": int(self.index_words),
+                "build_ms": float(self.build_ms),
+                "byte_sets": [{"bytes": int(g.bytes), "positions": int(g.positions), "classes": int(g.classes),
+                               "dead_sites": int(g.dead_sites)} for g in self.set[:self.byte_sets]]}
+
+
 class IssueParams(C.Structure):
     """fi_issue_params: the O3 issue model of SHREWD's FU contention."""
     _fields_ = [("issue_width", C.c_uint32), ("dispatch_width", C.c_uint32), ("commit_width", C.c_uint32),
@@ -267,6 +284,21 @@ def exact_classes(off, ev, ninst: int, reg: int):
     return out[:n.value].copy(), int(dead.value)
 
 
+def exact_mem_classes(ev, ninst: int, byte_mask: int):
+    """fi_exact_mem_classes (pure host code): the byte-liveness classes of one
+    memory word's events (numInst << 16 | bytes read << 8 | bytes written, in
+    time order) and one byte set (a bit per flipped byte) in a golden run of
+    ninst instructions -> (EXACT_CLASS_DT[n] in time order, dead t of the word)."""
+    ev = np.ascontiguousarray(ev, np.uint64)
+    n, dead = C.c_uint64(), C.c_uint64()
+    out = np.zeros(len(ev), EXACT_CLASS_DT)
+    rc = lib().fi_exact_mem_classes(ev.ctypes.data, len(ev), ninst, byte_mask, out.ctypes.data, len(out),
+                                    C.byref(n), C.byref(dead))
+    if rc != FI_OK:
+        raise EngineError(f"fi_exact_mem_classes: {rc}")
+    return out[:n.value].copy(), int(dead.value)
+
+
 ISSUE_PLAIN, ISSUE_LOAD, ISSUE_STORE, ISSUE_SERIAL = 0, 1, 2, 3
 FU_NAMES = ("IntALU", "IntMultDiv", "FP_ALU", "FP_MultDiv", "RdWrPort", "IprPort")
 
@@ -358,6 +390,11 @@ def lib():
         L.fi_exact_get_info.argtypes = [vp, C.POINTER(ExactInfo)]
         L.fi_exact_sites.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
         L.fi_run_exact.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
+        L.fi_set_exact_memory.argtypes = [vp, C.c_int]
+        L.fi_exact_mem_get_info.argtypes = [vp, C.POINTER(ExactMemInfo)]
+        L.fi_exact_mem_classes.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, C.c_uint64,
+                                           C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.fi_golden_mem_index.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, vp]
         L.fi_run_sites_capture.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp, vp]
         L.fi_run_trials_device.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp]
         L.fi_sync.argtypes = [vp]
@@ -685,6 +722,28 @@ class Engine:
                                       hist.ctypes.data), "fi_run_exact")
         return out, hist[0]
 
+    def set_exact_memory(self, on: bool):
+        """fi_set_exact_memory: exact campaigns that select memory words (33)
+        cover them by byte-liveness class; off (the default) refuses them."""
+        self._chk(self.L.fi_set_exact_memory(self.h, int(bool(on))), "fi_set_exact_memory")
+
+    def exact_mem_info(self) -> ExactMemInfo:
+        """fi_exact_mem_get_info: the words, the text words left out and, per
+        byte set, its bytes, positions, classes and dead sites."""
+        x = ExactMemInfo()
+        self._chk(self.L.fi_exact_mem_get_info(self.h, C.byref(x)), "fi_exact_mem_get_info")
+        return x
+
+    def golden_mem_index(self):
+        """fi_golden_mem_index: the golden run's memory liveness index
+        -> (addr uint64[w] ascending, off uint32[w + 1], ev uint64[])."""
+        cnt = np.zeros(2, np.uint64)
+        self._chk(self.L.fi_golden_mem_index(self.h, None, 0, None, 0, None, 0, cnt.ctypes.data), "fi_golden_mem_index")
+        addr, off, ev = np.zeros(int(cnt[0]), np.uint64), np.zeros(int(cnt[0]) + 1, np.uint32), np.zeros(int(cnt[1]), np.uint64)
+        self._chk(self.L.fi_golden_mem_index(self.h, addr.ctypes.data, len(addr), off.ctypes.data, len(off),
+                                             ev.ctypes.data, len(ev), cnt.ctypes.data), "fi_golden_mem_index")
+        return addr, off, ev
+
     def run_sites_capture(self, sites: np.ndarray, cap_bytes: int = 4096, stderr: bool = True):
         """run_sites, and what each trial printed besides -> (outcomes, hist,
         Capture): the first cap_bytes of every trial's stdout (and stderr)
@@ -907,7 +966,8 @@ class FaultCampaign:
     tick_contract ("numinst", the default, or "literal": a timing campaign
     runs the sites where TimingSimpleCPU differs from a numInst flip on the
     device instead of reporting them as escape/timing,
-    Engine.set_tick_contract).
+    Engine.set_tick_contract); exact_memory (run_exact() also covers the
+    memory words, structure 33, by byte-liveness class: Engine.set_exact_memory).
     """
 
     def __init__(self, workload: str, cmd: Sequence[str] | None = None, env: Sequence[str] | None = None,
@@ -917,7 +977,7 @@ class FaultCampaign:
                  shadow_fu_model: bool = False, priority_to_shadow: bool = False, issue_params: dict | None = None,
                  checkpoint: str = "", executable: str | None = None, input: str = "cin",
                  cpu_type: str = "atomic", timing_params: TimingParams | None = None, tick_map: str = "host",
-                 tick_contract: str = "numinst"):
+                 tick_contract: str = "numinst", exact_memory: bool = False):
         self.cpu_type = cpu_type.lower().removesuffix("simplecpu")
         if self.cpu_type not in ("atomic", "timing"):
             raise ValueError(f"cpu_type {cpu_type!r}: 'atomic' or 'timing'")
@@ -966,6 +1026,9 @@ class FaultCampaign:
             raise EngineError(f"cpu_type='timing': {self.engine.tick_info()['status']}")
         self.engine.set_tick_map(self.tick_map)
         self.engine.set_tick_contract(self.tick_contract)
+        self.exact_memory = bool(exact_memory)
+        if self.exact_memory:
+            self.engine.set_exact_memory(True)
         self.engine.set_campaign(seed, structures, burst)
         self.bits = bits_mask(bits)
         self.engine.set_bits(self.bits)
@@ -1042,12 +1105,15 @@ class FaultCampaign:
 
     def vulnerability(self) -> dict:
         """Per selected structure, the six outcome-class shares of its sites
-        after run_exact(): counts[s].sum(bits) / (ninst x eligible bits)."""
+        after run_exact(): counts[s].sum(bits) / (ninst x eligible bits), for
+        the memory words (33) / (words x ninst x eligible bits)."""
         x = self.engine.exact_info()
         per = int(self.golden.ninst) * int(x.nbits)
+        sel = structures_mask(self.structures)
+        words = int(self.engine.exact_mem_info().words) if (sel >> 33) & 1 else 1
         h = self._hist["counts"]
-        return {s: {CLASS_NAMES[c]: int(h[s, :, c].sum()) / per for c in range(6)}
-                for s in range(1, N_STRUCT) if (structures_mask(self.structures) >> s) & 1}
+        return {s: {CLASS_NAMES[c]: int(h[s, :, c].sum()) / (per * (words if s == 33 else 1)) for c in range(6)}
+                for s in range(1, N_STRUCT) if (sel >> s) & 1}
 
     def outputs(self, trials, max_bytes: int = 4096) -> dict:
         """What the given trials printed: {trial: (outcome, stdout, stderr)},

@@ -3,7 +3,7 @@ x1..x31 x 64-bit fault space of one workload, one trial per first-access class,
 timed end to end; the sampled run_trials of one launch's size beside it; then
 the exact vulnerability table (x1..x31 and the pc).
 
-python tools/gpu/exact_campaign.py [WORKLOAD] [--reps R] [--probe]
+python tools/gpu/exact_campaign.py [WORKLOAD] [--reps R] [--probe] [--memory]
 -> JSON lines
 
 Whole campaign: wall time around run_exact(0, trials) (it ends in a
@@ -14,26 +14,35 @@ alternating R times, L = min(trials, the engine's trials per launch).
 --probe: for a kernel trace taken around this process in a run of its own.
 Only the first launch of the campaign, then fi_run_sites on the same chunk's
 sites, so that fi_exact_hist_kernel and fi_hist_kernel each run once on the
-same sites and outcomes."""
+same sites and outcomes.
+
+--memory: the memory words (structure 33) alone, by byte-liveness class
+(Engine.set_exact_memory): the one-time class build on its own (the first
+exact_info(): wall, and the engine's own figure), then the whole campaign R
+times."""
 import json
 import os
 import statistics
 import sys
 import time
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 from shrewd_amd import CLASS_NAMES, Engine  # noqa: E402
 
-REGS, PC = (1 << 32) - 2, 1 << 32
+REGS, PC, MEM = (1 << 32) - 2, 1 << 32, 1 << 33
 SEED = 0x5EED0E8A
-argv, REPS, PROBE = [], 3, False
+argv, REPS, PROBE, MEMORY = [], 3, False, False
 it = iter(sys.argv[1:])
 for a in it:
     if a == "--reps":
         REPS = max(1, int(next(it)))
     elif a == "--probe":
         PROBE = True
+    elif a == "--memory":
+        MEMORY = True
     else:
         argv.append(a)
 name = argv[0] if argv else "crc32"
@@ -43,6 +52,48 @@ with open(os.path.join(ROOT, "workloads", f"{name}.elf"), "rb") as f:
 e = Engine(device=0)
 e.load_elf(elf, [name])
 g = e.golden_run()
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    r = fn()
+    return r, (time.perf_counter() - t0) * 1e3, e.last_kernel_ms()
+
+
+if MEMORY:
+    e.set_exact_memory(True)
+    e.set_campaign(SEED, MEM, 1)
+    t0 = time.perf_counter()
+    x = e.exact_info()                       # builds the classes
+    build_wall = (time.perf_counter() - t0) * 1e3
+    m = e.exact_mem_info()
+    _, off, _ = e.golden_mem_index()
+    trials = int(x.trials)
+    L = min(trials, e.config()["max_trials_per_launch"])
+    print(json.dumps({"workload": name, "what": "memory words, class build", "golden_ninst": int(g.ninst),
+                      "translate": e.translate_status(), "sites": int(x.space), "words": int(m.words),
+                      "text_words": int(m.text_words), "index_words": int(m.index_words),
+                      "index_events": int(off[-1]), "max_events_per_word": int(np.diff(off.astype(np.int64)).max()),
+                      "byte_sets": int(m.byte_sets), "classes": int(x.classes[33]), "exact_trials": trials,
+                      "dead_sites": int(x.dead_sites), "dead_share": round(int(x.dead_sites) / int(x.space), 9),
+                      "build_wall_ms": round(build_wall, 2), "build_ms": round(float(m.build_ms), 2)}), flush=True)
+    e.run_exact(0, L, want_outcomes=False)   # warm-up: code objects, work buffers
+    whole = []
+    for _ in range(REPS):
+        (_, h), wall, dev = timed(lambda: e.run_exact(0, trials, want_outcomes=False))
+        whole.append((wall, dev))
+    assert int(h["counts"].sum()) == int(h["trials"]) == int(x.space)
+    c = h["counts"][33].sum(axis=0)
+    print(json.dumps({"workload": name, "what": "whole campaign, memory words", "exact_trials": trials,
+                      "sites": int(x.space), "wall_ms": [round(w, 2) for w, _ in whole],
+                      "device_ms": [round(d, 2) for _, d in whole],
+                      "median_wall_ms": round(statistics.median(w for w, _ in whole), 2),
+                      "median_device_ms": round(statistics.median(d for _, d in whole), 2),
+                      "counts": {CLASS_NAMES[k]: int(c[k]) for k in range(6)},
+                      "device_insts": int(h["device_insts"])}), flush=True)
+    e.close()
+    sys.exit(0)
+
 e.set_campaign(SEED, REGS, 1)
 x = e.exact_info()
 trials, L = int(x.trials), min(int(x.trials), e.config()["max_trials_per_launch"])
@@ -57,13 +108,6 @@ if PROBE:
     print(json.dumps({"probe": name, "chunk": L}), flush=True)
     e.close()
     sys.exit(0)
-
-
-def timed(fn):
-    t0 = time.perf_counter()
-    r = fn()
-    return r, (time.perf_counter() - t0) * 1e3, e.last_kernel_ms()
-
 
 e.run_exact(0, L, want_outcomes=False)       # warm-up: code objects, work buffers
 e.run_trials(0, L, want_outcomes=False)
