@@ -161,56 +161,139 @@ static void jit_job_run(std::shared_ptr<JitJob> j) {
     j->cv.notify_all();
 }
 
-struct fi_engine {
-    fi_config cfg{};
-    std::string err;
-    int dev = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    double last_ms = 0;
-    // per-launch timing of the interpreter kernel (bench roofline)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> tpool;
-    unsigned long long *d_span = nullptr;   // per timer slot: [min wave start, max wave end] (kSpanSlots pairs)
-    std::vector<uint32_t> tkind;
-    size_t tused = 0;
+// An allocation of n elements that frees itself: device memory (hipMalloc),
+// or with kPinned pinned host memory (hipHostMalloc).  Move-only; reads as the
+// pointer it owns.  Every buffer the engine keeps is one of these, so a group
+// of them (below) is released by assigning it a fresh value.
+template <typename T, bool kPinned = false>
+class DevBuf {
+public:
+    static constexpr uint64_t elem = sizeof(T);
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { reset(); }
+    hipError_t alloc(uint64_t n) {
+        reset();
+        return kPinned ? hipHostMalloc((void **)&p_, n * sizeof(T)) : hipMalloc((void **)&p_, n * sizeof(T));
+    }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    void reset() {
+        if (p_) (void)(kPinned ? hipHostFree((void *)p_) : hipFree((void *)p_));
+        p_ = nullptr;
+    }
 
-    // process image (host copy)
+private:
+    T *p_ = nullptr;
+};
+template <typename T>
+using PinBuf = DevBuf<T, true>;
+
+// A loaded code object, unloaded with its owner.
+class Module {
+public:
+    Module() = default;
+    Module(Module &&o) noexcept : m(o.m) { o.m = nullptr; }
+    Module &operator=(Module &&o) noexcept {
+        if (this != &o) { reset(); m = o.m; o.m = nullptr; }
+        return *this;
+    }
+    ~Module() { reset(); }
+    void reset() {
+        if (m) (void)hipModuleUnload(m);
+        m = nullptr;
+    }
+    hipModule_t m = nullptr;
+};
+
+// The engine's host state, grouped by what resets it: a reset
+// is the assignment of a fresh value, after hipSetDevice(e->dev).
+
+struct Seg { uint64_t lo, hi; bool w; };
+
+// The loaded process image: fi_load_elf / fi_load_checkpoint build one and
+// move it in; the next load replaces it.
+struct Image {
     bool loaded = false;
     std::map<uint64_t, std::vector<uint8_t>> pages;   // vpn -> 4 KiB
     uint64_t entry = 0, sp0 = 0, stack_min0 = 0, svma_lo = 0, svma_hi = 0;
     uint64_t text_lo = 0, text_hi = 0, code_lo = 0, code_hi = 0;
+    uint64_t brk0 = 0;                 // roundUp(maxAddr, page): the process-start brk point
     std::vector<uint64_t> mem_pages;   // memory fault candidates (sorted)
-    struct Seg { uint64_t lo, hi; bool w; };
     std::vector<Seg> segs;             // PT_LOAD page ranges of the ELF (w = PF_W)
+    std::vector<uint64_t> alloc_order; // process-start pages in allocation order (img_write)
     // checkpoint start state beyond registers, pages and the stack VMA
     bool fp0_on = false, vm0_on = false;
     uint64_t fp0[32] = {};
     uint32_t fcsr0 = 0;
     uint64_t tick0 = 0;
     VmState vm0{};
-    uint64_t *d_fp0 = nullptr;
-    VmState *d_vm0 = nullptr;
-
-    // device image: snapshot 0 = the process-start image; the golden run
-    // appends snapshots 1..n-1
-    PreInst *d_pre = nullptr;
-    uint8_t *d_zero = nullptr, *d_text = nullptr, *d_sink = nullptr;
-    uint64_t *d_mem_pages = nullptr;
+    DevBuf<uint64_t> d_fp0;
+    DevBuf<VmState> d_vm0;
+    DevBuf<PreInst> d_pre;
+    DevBuf<uint8_t> d_zero, d_text, d_sink;
+    DevBuf<uint64_t> d_mem_pages;
+    // snapshot 0 = the process-start image, frames [0, n_start_frames); the
+    // golden run appends snapshots 1..n-1 and golden_reset
+    // truncates the tables back to the image's own
     std::vector<SnapState> snaps;
     std::vector<PageEnt> tab;
     std::vector<uint8_t> pool;            // host copy of the snapshot frames
-    uint32_t n_start_frames = 0;          // frames [0, n) = process-start pages
-    SnapState *d_snaps = nullptr;
-    PageEnt *d_tab = nullptr;
-    uint8_t *d_pool = nullptr;
+    uint32_t n_start_frames = 0;
+    DevBuf<SnapState> d_snaps;
+    DevBuf<PageEnt> d_tab;
+    DevBuf<uint8_t> d_pool;
+};
+
+// memory words of exact campaigns (fi_set_exact_memory): the classes of the golden run's memory index
+// under one (bits, burst), built on the device at the first exact call that needs them (exact_mem_build)
+struct ExMem {
+    bool ok = false;
+    uint64_t bits = 0;
+    uint32_t burst = 0, n_rows = 0;
+    ExactMemRow rows[kExactMaxMemRows] = {};
+    uint64_t classes[kExactMaxMemRows] = {}, dead[kExactMaxMemRows] = {};   // per byte set; dead: (word, t) pairs
+    uint64_t words = 0, text_words = 0, n_classes = 0;
+    double build_ms = 0;
+    DevBuf<ExactMemRow> d_rows;
+    DevBuf<ExactMemClass> d_cls;
+};
+
+// The translated kernels: the 64-lane, solo and solo-odd code objects.
+struct Tx {
+    Module mod[3];
+    hipFunction_t fn = nullptr, fn_solo = nullptr;
+    hipFunction_t fn_odd = nullptr;   // solo kernel with the odd-pc blocks (nullptr: none translated)
+};
+
+// Everything a golden run finds out: fi_golden_run starts from a fresh one,
+// and so does a load.
+struct Golden {
+    bool have_golden = false;
+    fi_golden_info info{};
+    uint32_t gdetail = 0, gsub = 0;
+    std::vector<uint8_t> gout, gerr;
+    DevBuf<uint8_t> d_gout, d_gerr;
+    bool golden_fp = false;          // the golden run wrote FP state: no snapshot start / early exit
+    uint64_t clk_until = 0;          // 1 + numInst of the golden run's last curTick read (0: none; DevCtx::clk_until)
+    bool golden_unmapped = false;    // the golden run freed frames (munmap / brk shrink)
+    bool pre_ok = true;
     uint64_t snap_I = 1ULL << 62;
-    // memory liveness index of the golden run (build_mem_index)
+    // memory liveness index (build_mem_index)
     bool mem_live = false;
     uint32_t mw_n = 0;
-    uint64_t *d_mw_addr = nullptr, *d_mw_ev = nullptr;
+    uint64_t mw_nev = 0;             // the index's events
+    DevBuf<uint64_t> d_mw_addr, d_mw_ev;
+    DevBuf<uint32_t> d_mw_off;
     // first-access forwarding: per register x1..x31, the golden trace's
     // accesses in order, entry = (2 * numInst + !ecall) << 1 | reads
-    uint32_t *d_fw_off = nullptr, *d_fw_ev = nullptr;
+    DevBuf<uint32_t> d_fw_off, d_fw_ev;
     bool fw_ok = false;
     // exact campaigns (fi_exact.h): the host copy of the index and, built from it at
     // the first exact call after a golden run, every register's classes (register r's packed words
@@ -219,151 +302,147 @@ struct fi_engine {
     bool ex_ok = false;
     uint32_t ex_off[33] = {};
     uint64_t ex_dead[32] = {};
-    uint64_t *d_ex_classes = nullptr;
-    // memory words (fi_set_exact_memory): the classes of the golden run's memory index under one
-    // (bits, burst), built on the device at the first exact call that needs them (exact_mem_build)
-    bool exact_mem = false;
-    uint64_t mw_nev = 0;             // the index's events
-    struct ExMem {
-        bool ok = false;
-        uint64_t bits = 0;
-        uint32_t burst = 0, n_rows = 0;
-        ExactMemRow rows[kExactMaxMemRows] = {};
-        uint64_t classes[kExactMaxMemRows] = {}, dead[kExactMaxMemRows] = {};   // per byte set; dead: (word, t) pairs
-        uint64_t words = 0, text_words = 0, n_classes = 0;
-        double build_ms = 0;
-        ExactMemRow *d_rows = nullptr;
-        ExactMemClass *d_cls = nullptr;
-    } xm;
-    uint64_t *d_eff = nullptr;       // [cap] effective inject time per trial (kFwDead: dead at injection)
-    uint32_t *d_mw_off = nullptr;
-    bool pre_ok = true;
+    DevBuf<uint64_t> d_ex_classes;
+    ExMem xm;
     // load-time build of the trial kernel with the translated golden blocks
-    hipModule_t tx_mod[3] = {nullptr, nullptr, nullptr};
-    std::shared_ptr<JitJob> jit;     // the build in flight (nullptr: none)
-    // builds this engine started: a finished one is joined when a build is
-    // installed (jit_install), one still running by fi_destroy
-    std::vector<std::pair<std::thread, std::shared_ptr<JitJob>>> jit_threads;
+    Tx tx;
+    std::shared_ptr<JitJob> jit;     // the build in flight (nullptr: none); its thread holds the job too
     std::vector<PreInst> jit_pre;    // golden pre-decoded text with the leader flags, uploaded when it lands
     uint64_t jit_blocks = 0, jit_insts = 0;
-    hipFunction_t tx_fn = nullptr, tx_fn_solo = nullptr;
-    hipFunction_t tx_fn_odd = nullptr;   // solo kernel with the odd-pc blocks (nullptr: none translated)
-    // the solo-odd kernel runs beside the solo kernel on its own stream
-    hipStream_t stream_odd = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::string tx_status = "no golden run";
     std::string tx_body;   // last generated translation (diagnostics)
+    DevBuf<LoopEst> d_loops;         // counted loops of the golden text (the solo order's work-left estimate)
+    uint32_t n_loops = 0;
+    // SHREWD FU contention (fi_set_issue_model): shadow issued per golden numInst index
+    fi_issue_stats issue_stats{};
+    std::vector<uint8_t> shadow;
+    DevBuf<uint32_t> d_shadow;       // the same as a bitmap, [ninst / 32 + 1]
+    std::vector<PreInst> g_pre;      // golden pre-decoded text and trace (empty: unavailable)
+    std::vector<uint32_t> g_trace;
+    // tick-domain injection (fi_tick.cpp, fi_timing.cpp): the golden run's attempts as requests
+    std::vector<fi_timing_op> t_ops;
+    std::vector<fi_timing_ticks> t_ticks;
+    fi_timing_stats t_stats{};
+    std::string t_status = "no golden run";
+    // the site map's table (fi_tick_map.h): the attempts and their ticks, packed with the tick model;
+    // the device map's copy is made at its first use (ensure_tick_table)
+    std::vector<uint64_t> tk_done;
+    std::vector<TickRec> tk_rec;
+    DevBuf<uint64_t> d_tk_done;
+    DevBuf<TickRec> d_tk_rec;
+};
 
-    // golden
-    bool have_golden = false;
-    fi_golden_info golden{};
-    uint32_t gdetail = 0, gsub = 0;
-    std::vector<uint8_t> gout, gerr;
-    uint8_t *d_gout = nullptr, *d_gerr = nullptr;
+// output capture (fi_run_sites_capture): on only while such a call runs (bytes != 0);
+// its buffers are grown on demand.  Rows alternate between the two chunks in flight like the site
+// and outcome buffers; the pinned staging mirrors them.
+struct Capture {
+    uint32_t bytes = 0, stride = 0;   // bytes kept per stream; device row pitch (bytes rounded up to 16)
+    uint64_t rows = 0;                // trials per chunk
+    uint64_t held_b = 0, held_rows = 0;   // what is allocated: bytes per row buffer, entries per length buffer
+    DevBuf<uint8_t> d_out[2], d_err[2];
+    DevBuf<fi_stream_len> d_len[2];
+    PinBuf<uint8_t> h_out[2], h_err[2];
+    PinBuf<fi_stream_len> h_len[2];
+    uint8_t *out = nullptr, *err = nullptr;   // the caller's arrays (err, lens may be NULL)
+    fi_stream_len *lens = nullptr;
+};
 
-    // campaign
+// Work buffers, sized for `cap` trials per launch (work_buffers); a larger
+// launch replaces them all.
+struct Work {
+    uint64_t cap = 0;
+    DevBuf<fi_site> d_sites, d_sites_alt;   // the chunk being run / the one being finished
+    DevBuf<uint32_t> d_weight[2];           // an exact chunk's weights, alternating like the sites
+    DevBuf<uint64_t> d_keys, d_keys2;
+    DevBuf<uint32_t> d_perm, d_perm2;
+    DevBuf<uint8_t> d_tmp;
+    size_t tmp_bytes = 0;
+    DevBuf<fi_outcome> d_out, d_out_alt;
+    DevBuf<uint64_t> d_eff;          // effective inject time per trial (kFwDead: dead at injection)
+    DevBuf<fi_histogram> d_hist;
+    DevBuf<unsigned long long> d_stats;
+    DevBuf<uint64_t> d_wave_dbg;
+    DevBuf<uint64_t> d_fregs;        // FP registers of the work slots
+    DevBuf<uint64_t> d_inpos;        // per work slot: fd 0's file offset
+    DevBuf<uint8_t> d_priv;
+    DevBuf<uint64_t> d_priv_vpn;
+    // overflow pages (DevCtx::ov_*): ov_blocks blocks of ov_pages
+    DevBuf<uint8_t> d_ov;
+    DevBuf<uint64_t> d_ov_vpn;
+    DevBuf<uint32_t> d_ov_of, d_ov_next;
+    uint32_t ov_blocks = 0, ov_pages = 0;
+    DevBuf<VmState> d_vm;            // per-slot SE memory map (trials that made a VM syscall)
+    // epochs: suspended lanes, survivor lists, counts, sort buffers
+    DevBuf<LaneSave> d_save;
+    DevBuf<uint32_t> d_surv[2], d_cnt;
+    DevBuf<uint64_t> d_skeys, d_skeys2;
+    DevBuf<uint32_t> d_svals, d_svals2;
+    DevBuf<uint32_t> d_wrange, d_nwaves;   // packed resume (FI_CFG_PACK_RUNS)
+    DevBuf<uint32_t> d_split;   // per epoch: odd-pc survivors, then the solo kernel's share of the list
+    DevBuf<uint32_t> d_dmap;    // per slot: rewritten-code map (DevCtx::dmap, kDmapWords words)
+    // second pass of the trials that ran out of private pages (chunk_end): two of each, a chunk and its predecessor
+    DevBuf<uint32_t> d_redo_idx, d_redo_cnt;
+    PinBuf<uint32_t> h_redo_cnt;
+    DevBuf<fi_site> d_redo_sites;
+    DevBuf<fi_outcome> d_redo_out;
+    // pinned staging of a chunk's outcomes on their way to the caller's (pageable) array, made on
+    // first use (chunk_end): a copy straight into pageable memory would hold the host until the
+    // stream reaches it
+    PinBuf<fi_outcome> h_stage[2];
+    // the device tick map's buffers (ensure_tick_work), [cap] each: the tick sites in fi_site
+    // layout, the dispositions, the disp 1 / 2 outcomes, uploaded explicit sites
+    bool tk_ok = false;
+    DevBuf<fi_site> d_tk_sites[2];
+    DevBuf<uint8_t> d_tk_disp[2];
+    DevBuf<fi_outcome> d_tk_res[2];
+    DevBuf<fi_tick_site> d_tk_in[2];
+    Capture cx;
+};
+
+struct fi_engine {
+    fi_config cfg{};
+    std::string err;
+    int dev = 0;
+    // streams and events: made by fi_create, released by fi_destroy.  The
+    // solo-odd kernel runs beside the solo kernel on its own stream
+    hipStream_t stream = nullptr, stream_odd = nullptr;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_cnt[2] = {nullptr, nullptr};     // a chunk's redo count has reached h_redo_cnt
+    hipEvent_t ev_stage[2] = {nullptr, nullptr};   // a chunk's outcomes have reached h_stage
+    double last_ms = 0;
+    // per-launch timing of the interpreter kernel (bench roofline)
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> tpool;
+    DevBuf<unsigned long long> d_span;   // per timer slot: [min wave start, max wave end] (kSpanSlots pairs)
+    std::vector<uint32_t> tkind;
+    size_t tused = 0;
+
+    // campaign settings (fi_set_*)
     uint64_t seed = 0x5EED0001ULL, structures = 0;
     uint32_t burst = 1;
     uint64_t bits = ~0ULL;      // eligible lowest-bit positions (fi_set_bits)
     uint64_t clk_period = 500, rnd_seed = 5489;   // fi_set_clock
-    uint8_t *d_rnd = nullptr;   // getrandom's byte stream (kRndLen bytes)
+    DevBuf<uint8_t> d_rnd;      // getrandom's byte stream (kRndLen bytes)
     std::string exe_path;       // fi_set_exe_path
-    uint8_t *d_exe = nullptr;
+    DevBuf<uint8_t> d_exe;
     bool stdin_on = false;      // fi_set_stdin: Process.input is a file (else "cin")
     std::vector<uint8_t> stdin_data;
-    uint8_t *d_stdin = nullptr;
-    uint64_t *d_inpos = nullptr;   // per work slot: fd 0's file offset
+    DevBuf<uint8_t> d_stdin;
     uint64_t protect = 0;
     uint64_t protect_opc = 0;   // SHREWD replication by OpClass (fi_set_protect_opclasses)
-    // SHREWD FU contention (fi_set_issue_model): shadow issued per golden numInst index
-    bool issue_on = false;
+    bool issue_on = false;      // fi_set_issue_model: every golden run recomputes its shadow
     fi_issue_params issue_p{};
-    fi_issue_stats issue_stats{};
-    std::vector<uint8_t> shadow;
-    uint32_t *d_shadow = nullptr;    // the same as a bitmap, [ninst / 32 + 1]
-    std::vector<PreInst> g_pre;      // golden pre-decoded text and trace (empty: unavailable)
-    std::vector<uint32_t> g_trace;
-    // tick-domain injection (fi_set_cpu_model FI_CPU_TIMING; fi_tick.cpp, fi_timing.cpp)
-    int cpu_model = FI_CPU_ATOMIC;
+    int cpu_model = FI_CPU_ATOMIC;   // fi_set_cpu_model FI_CPU_TIMING: tick-domain injection
     fi_timing_params tparams{};
-    std::vector<uint64_t> alloc_order;   // process-start pages in allocation order (fi_load_elf's writes)
-    bool golden_unmapped = false;        // the golden run freed frames (munmap / brk shrink)
-    std::vector<fi_timing_op> t_ops;     // the golden run's attempts as requests
-    std::vector<fi_timing_ticks> t_ticks;
-    fi_timing_stats t_stats{};
-    std::string t_status = "no golden run";
-    // the site map's table (fi_tick_map.h): the attempts and their ticks, packed with the tick model
-    std::vector<uint64_t> tk_done;
-    std::vector<TickRec> tk_rec;
     int tick_map = FI_TICK_MAP_HOST;                // fi_set_tick_map
     int tick_contract = FI_TICK_CONTRACT_NUMINST;   // fi_set_tick_contract
-    uint64_t *d_tk_done = nullptr;                  // the device map's copy of the table, made at its first use
-    TickRec *d_tk_rec = nullptr;
-    // ... and its per-chunk-slot work buffers (ensure_tick_work), [cap] each: the tick sites in fi_site
-    // layout, the dispositions, the disp 1 / 2 outcomes, uploaded explicit sites
-    fi_site *d_tk_sites[2] = {nullptr, nullptr};
-    uint8_t *d_tk_disp[2] = {nullptr, nullptr};
-    fi_outcome *d_tk_res[2] = {nullptr, nullptr};
-    fi_tick_site *d_tk_in[2] = {nullptr, nullptr};
+    bool exact_mem = false;     // fi_set_exact_memory
+    // builds this engine started: a finished one is joined when a build is
+    // installed (jit_install), one still running by fi_destroy
+    std::vector<std::pair<std::thread, std::shared_ptr<JitJob>>> jit_threads;
 
-    // work buffers, sized for `cap` trials per launch
-    uint64_t cap = 0;
-    fi_site *d_sites = nullptr, *d_sites_alt = nullptr;   // the chunk being run / the one being finished
-    uint32_t *d_weight[2] = {nullptr, nullptr};           // an exact chunk's weights, alternating like the sites
-    uint64_t *d_keys = nullptr, *d_keys2 = nullptr;
-    uint32_t *d_perm = nullptr, *d_perm2 = nullptr;
-    void *d_tmp = nullptr;
-    size_t tmp_bytes = 0;
-    fi_outcome *d_out = nullptr, *d_out_alt = nullptr;
-    fi_histogram *d_hist = nullptr;
-    unsigned long long *d_stats = nullptr;
-    uint64_t *d_wave_dbg = nullptr;
-    uint64_t *d_fregs = nullptr;     // FP registers of the work slots
-    bool golden_fp = false;          // the golden run wrote FP state: no snapshot start / early exit
-    uint64_t clk_until = 0;          // 1 + numInst of the golden run's last curTick read (0: none; DevCtx::clk_until)
-    uint8_t *d_priv = nullptr;
-    uint64_t *d_priv_vpn = nullptr;
-    // overflow pages (DevCtx::ov_*): ov_blocks blocks of ov_pages
-    uint8_t *d_ov = nullptr;
-    uint64_t *d_ov_vpn = nullptr;
-    uint32_t *d_ov_of = nullptr, *d_ov_next = nullptr;
-    uint32_t ov_blocks = 0, ov_pages = 0;
-    VmState *d_vm = nullptr;         // [cap] per-slot SE memory map (trials that made a VM syscall)
-    uint64_t brk0 = 0;               // roundUp(maxAddr, page): the process-start brk point
-    // epochs: suspended lanes, survivor lists, counts, sort buffers
-    LaneSave *d_save = nullptr;
-    uint32_t *d_surv[2] = {nullptr, nullptr};
-    uint32_t *d_cnt = nullptr;
-    uint64_t *d_skeys = nullptr, *d_skeys2 = nullptr;
-    uint32_t *d_svals = nullptr, *d_svals2 = nullptr;
-    uint32_t *d_wrange = nullptr, *d_nwaves = nullptr;   // packed resume (FI_CFG_PACK_RUNS)
-    uint32_t *d_split = nullptr;   // per epoch: odd-pc survivors, then the solo kernel's share of the list
-    LoopEst *d_loops = nullptr;    // counted loops of the golden text (the solo order's work-left estimate)
-    uint32_t n_loops = 0;
-    uint32_t *d_dmap = nullptr;    // per slot: rewritten-code map (DevCtx::dmap, kDmapWords words)
-    // second pass of the trials that ran out of private pages (chunk_end)
-    uint32_t *d_redo_idx = nullptr, *d_redo_cnt = nullptr, *h_redo_cnt = nullptr;   // two of each: a chunk and its predecessor
-    hipEvent_t ev_cnt[2] = {nullptr, nullptr};   // a chunk's redo count has reached h_redo_cnt
-    // pinned staging of a chunk's outcomes on their way to the caller's (pageable) array: a copy
-    // straight into pageable memory would hold the host until the stream reaches it
-    fi_outcome *h_stage[2] = {nullptr, nullptr};
-    hipEvent_t ev_stage[2] = {nullptr, nullptr};
-    fi_site *d_redo_sites = nullptr;
-    fi_outcome *d_redo_out = nullptr;
-    // output capture (fi_run_sites_capture): on only while such a call runs (bytes != 0);
-    // its buffers are grown on demand and kept until free_work.  Rows alternate between the two chunks in flight like the site and outcome
-    // buffers; the pinned staging mirrors them.
-    struct Capture {
-        uint32_t bytes = 0, stride = 0;   // bytes kept per stream; device row pitch (bytes rounded up to 16)
-        uint64_t rows = 0;                // trials per chunk
-        uint64_t held_b = 0, held_rows = 0;   // what is allocated: bytes per row buffer, entries per length buffer
-        uint8_t *d_out[2] = {nullptr, nullptr}, *d_err[2] = {nullptr, nullptr};
-        fi_stream_len *d_len[2] = {nullptr, nullptr};
-        uint8_t *h_out[2] = {nullptr, nullptr}, *h_err[2] = {nullptr, nullptr};
-        fi_stream_len *h_len[2] = {nullptr, nullptr};
-        uint8_t *out = nullptr, *err = nullptr;   // the caller's arrays (err, lens may be NULL)
-        fi_stream_len *lens = nullptr;
-    } cx;
+    Image img;
+    Golden gold;
+    Work w;
 };
 
 static fi_status fail(fi_engine *e, fi_status code, const char *fmt, ...) {
@@ -376,44 +455,13 @@ static fi_status fail(fi_engine *e, fi_status code, const char *fmt, ...) {
     return code;
 }
 
-#define HIPCHK(call)                                                                          \
-    do {                                                                                      \
-        hipError_t _e = (call);                                                               \
-        if (_e != hipSuccess) return fail(e, FI_E_HIP, "%s: %s", #call, hipGetErrorString(_e)); \
+// (what: the error text's prefix -- the call itself, or the step it belongs to)
+#define HIPCHK_AS(what, call)                                                                \
+    do {                                                                                     \
+        hipError_t _e = (call);                                                              \
+        if (_e != hipSuccess) return fail(e, FI_E_HIP, "%s: %s", what, hipGetErrorString(_e)); \
     } while (0)
-
-template <typename T>
-static void dfree(T *&p) {
-    if (p) { (void)hipFree((void *)p); p = nullptr; }
-}
-
-// A function-local device allocation of n elements: freed at reset() or at the
-// end of its scope, so that no return path has to free it.  (The engine's
-// persistent d_* buffers have one owner and one free path already.)
-template <typename T>
-class DevBuf {
-public:
-    DevBuf() = default;
-    DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
-    DevBuf &operator=(DevBuf &&o) noexcept {
-        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
-        return *this;
-    }
-    DevBuf(const DevBuf &) = delete;
-    DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { reset(); }
-    hipError_t alloc(uint64_t n) {
-        reset();
-        return hipMalloc(&p_, n * sizeof(T));
-    }
-    T *get() const { return p_; }
-    void reset() {
-        if (p_) { (void)hipFree((void *)p_); p_ = nullptr; }
-    }
-
-private:
-    T *p_ = nullptr;
-};
+#define HIPCHK(call) HIPCHK_AS(#call, call)
 
 // Diagnostics (SHREWD_FI_TRACE): a native backtrace on SIGSEGV.
 #include <execinfo.h>
@@ -440,13 +488,77 @@ static fi_status upload_rnd(fi_engine *e) {
     std::vector<uint8_t> tab(kRndLen);
     std::mt19937_64 gen((uint32_t)e->rnd_seed);
     for (auto &b : tab) b = (uint8_t)(gen() % 255);
-    if (!e->d_rnd) HIPCHK(hipMalloc(&e->d_rnd, kRndLen));
+    if (!e->d_rnd) HIPCHK(e->d_rnd.alloc(kRndLen));
     HIPCHK(hipMemcpy(e->d_rnd, tab.data(), kRndLen, hipMemcpyHostToDevice));
     return FI_OK;
 }
 
 // private pages per slot of the second pass (and so the overflow blocks): 16 P, at least 256
 static uint64_t redo_pages(uint64_t P) { return std::max<uint64_t>(P * 16ull, 256); }
+
+// The work buffers of c trials per launch, described once: allocated into w,
+// or (count) only added up -- fi_create's estimate of what a slot costs.
+static fi_status work_buffers(fi_engine *e, Work &w, uint64_t c, uint64_t *count) {
+    uint64_t total = 0;
+    auto buf = [&](auto &b, uint64_t n) {
+        total += n * b.elem;
+        return count ? hipSuccess : b.alloc(n);
+    };
+    const uint64_t P = e->cfg.private_pages, P2 = redo_pages(P);
+    HIPCHK(buf(w.d_sites, c));
+    HIPCHK(buf(w.d_sites_alt, c));
+    HIPCHK(buf(w.d_weight[0], c));
+    HIPCHK(buf(w.d_weight[1], c));
+    HIPCHK(buf(w.d_keys, c));
+    HIPCHK(buf(w.d_keys2, c));
+    HIPCHK(buf(w.d_perm, c));
+    HIPCHK(buf(w.d_perm2, c));
+    HIPCHK(sort_pairs_bytes(c, w.tmp_bytes));
+    HIPCHK(buf(w.d_tmp, std::max<size_t>(w.tmp_bytes, 16)));
+    HIPCHK(buf(w.d_out, c));
+    HIPCHK(buf(w.d_out_alt, c));
+    HIPCHK(buf(w.d_eff, c));
+    HIPCHK(buf(w.d_hist, 1));
+    HIPCHK(buf(w.d_stats, kNStats));
+    HIPCHK(buf(w.d_wave_dbg, c * kWaveDbgWords));
+    HIPCHK(buf(w.d_priv, c * P * kPage));
+    HIPCHK(buf(w.d_priv_vpn, c * P));
+    HIPCHK(buf(w.d_save, c));
+    HIPCHK(buf(w.d_vm, c));
+    HIPCHK(buf(w.d_fregs, c * 32));
+    HIPCHK(buf(w.d_inpos, c));
+    HIPCHK(buf(w.d_surv[0], c));
+    HIPCHK(buf(w.d_surv[1], c));
+    HIPCHK(buf(w.d_cnt, 16));
+    HIPCHK(buf(w.d_skeys, c));
+    HIPCHK(buf(w.d_skeys2, c));
+    HIPCHK(buf(w.d_svals, c));
+    HIPCHK(buf(w.d_svals2, c));
+    HIPCHK(buf(w.d_wrange, 2 * c));
+    HIPCHK(buf(w.d_nwaves, 16));
+    HIPCHK(buf(w.d_split, 64));
+    HIPCHK(buf(w.d_dmap, c * kDmapWords));
+    HIPCHK(buf(w.d_redo_idx, 2 * c));
+    HIPCHK(buf(w.d_redo_cnt, 4));
+    HIPCHK(buf(w.d_redo_sites, c));
+    HIPCHK(buf(w.d_redo_out, c));
+    // (the pinned staging of host-bound outcomes is made on first use:
+    // chunk_end; device-resident runs never need it)
+    if (!count) HIPCHK(w.h_redo_cnt.alloc(4));
+    // overflow pool: a trial past P pages takes a block of P' - P more (P' the
+    // redo pass's page count), one block per 2048 slots (at least 64)
+    if (!(e->cfg.flags & FI_CFG_NO_OVERFLOW) && P2 > P) {
+        w.ov_pages = (uint32_t)(P2 - P);
+        w.ov_blocks = (uint32_t)std::max<uint64_t>(64, c / 2048);
+        HIPCHK(buf(w.d_ov, (uint64_t)w.ov_blocks * w.ov_pages * kPage));
+        HIPCHK(buf(w.d_ov_vpn, (uint64_t)w.ov_blocks * w.ov_pages));
+        HIPCHK(buf(w.d_ov_of, c));
+        HIPCHK(buf(w.d_ov_next, 4));
+    }
+    if (count) *count = total;
+    else w.cap = c;
+    return FI_OK;
+}
 
 fi_status fi_create(const fi_config *cfg, fi_engine **out) {
     if (!out) { g_create_err = "fi_create: out is NULL"; return FI_E_ARG; }
@@ -482,7 +594,11 @@ fi_status fi_create(const fi_config *cfg, fi_engine **out) {
         hipStreamCreateWithFlags(&e->stream_odd, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&e->ev0) != hipSuccess || hipEventCreate(&e->ev1) != hipSuccess ||
         hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) != hipSuccess) {
+        hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&e->ev_cnt[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&e->ev_cnt[1], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&e->ev_stage[0], hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&e->ev_stage[1], hipEventDisableTiming) != hipSuccess) {
         g_create_err = "fi_create: HIP stream/event creation failed on device " + std::to_string(e->dev);
         delete e;
         return FI_E_HIP;
@@ -495,15 +611,18 @@ fi_status fi_create(const fi_config *cfg, fi_engine **out) {
     if (e->cfg.max_trials_per_launch == 0) {
         // auto: a campaign's trials in as few launches as half the free HBM
         // holds (each launch ends in its own serial tail of long trials), at
-        // (4 KiB + 8 B) per private page, the per-slot buffers of ensure_work
-        // (both site / outcome buffers of the chunks in flight, the redo
-        // lists, the rewritten-code map) and the overflow pool's share
-        // (one block of P' - P pages per 2048 slots)
+        // what work_buffers takes per slot of the largest launch
         size_t free_b = 0, total_b = 0;
-        const uint64_t P = e->cfg.private_pages, P2 = redo_pages(P);
-        const uint64_t slot_b = 3 * sizeof(fi_site) + 3 * sizeof(fi_outcome) + 8 * 8 + 10 * 4 + kWaveDbgWords * 8 +
-                                sizeof(LaneSave) + sizeof(VmState) + 33 * 8 + kDmapWords * 4 + 4 + 64;
-        const uint64_t per = P * (kPage + 8) + slot_b + (P2 > P ? (P2 - P) * (kPage + 8) / 2048 + 1 : 0);
+        const uint64_t c = 1u << 21;
+        uint64_t bytes = 0;
+        Work none;
+        if (work_buffers(e, none, c, &bytes) != FI_OK) {
+            g_create_err = "fi_create: " + e->err;
+            delete e;
+            return FI_E_HIP;
+        }
+        const uint64_t per = (bytes + c - 1) / c;
+        if (getenv("SHREWD_FI_TRACE")) fprintf(stderr, "[fi] work buffers: %llu bytes per slot\n", (unsigned long long)per);
         uint64_t cap = 65536;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) cap = (uint64_t)free_b / 2 / per;
         e->cfg.max_trials_per_launch = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cap, 65536), 1u << 21);
@@ -512,70 +631,18 @@ fi_status fi_create(const fi_config *cfg, fi_engine **out) {
     return FI_OK;
 }
 
-static void free_capture(fi_engine *e) {
-    for (int i = 0; i < 2; i++) {
-        dfree(e->cx.d_out[i]); dfree(e->cx.d_err[i]); dfree(e->cx.d_len[i]);
-        for (void **h : {(void **)&e->cx.h_out[i], (void **)&e->cx.h_err[i], (void **)&e->cx.h_len[i]})
-            if (*h) { (void)hipHostFree(*h); *h = nullptr; }
-    }
-    e->cx = fi_engine::Capture{};
-}
-
-static void free_work(fi_engine *e) {
-    free_capture(e);
-    dfree(e->d_sites); dfree(e->d_sites_alt); dfree(e->d_weight[0]); dfree(e->d_weight[1]); dfree(e->d_out_alt); dfree(e->d_keys); dfree(e->d_keys2); dfree(e->d_perm); dfree(e->d_perm2);
-    dfree(e->d_tmp); dfree(e->d_out); dfree(e->d_hist); dfree(e->d_stats); dfree(e->d_wave_dbg); dfree(e->d_fregs);
-    dfree(e->d_inpos);
-    dfree(e->d_save); dfree(e->d_surv[0]); dfree(e->d_surv[1]); dfree(e->d_cnt);
-    dfree(e->d_eff);
-    dfree(e->d_skeys); dfree(e->d_skeys2); dfree(e->d_svals); dfree(e->d_svals2); dfree(e->d_wrange); dfree(e->d_nwaves); dfree(e->d_split); dfree(e->d_dmap); dfree(e->d_priv); dfree(e->d_priv_vpn); dfree(e->d_vm);
-    dfree(e->d_ov); dfree(e->d_ov_vpn); dfree(e->d_ov_of); dfree(e->d_ov_next);
-    e->ov_blocks = e->ov_pages = 0;
-    dfree(e->d_redo_idx); dfree(e->d_redo_cnt); dfree(e->d_redo_sites); dfree(e->d_redo_out);
-    for (auto &h : e->h_stage)
-        if (h) { (void)hipHostFree(h); h = nullptr; }
-    for (int i = 0; i < 2; i++) { dfree(e->d_tk_sites[i]); dfree(e->d_tk_disp[i]); dfree(e->d_tk_res[i]); dfree(e->d_tk_in[i]); }
-    e->cap = 0;
-}
-static void free_snaps(fi_engine *e) { dfree(e->d_snaps); dfree(e->d_tab); dfree(e->d_pool); }
-static void free_mem_index(fi_engine *e) {
-    dfree(e->d_mw_addr); dfree(e->d_mw_off); dfree(e->d_mw_ev);
-    dfree(e->xm.d_rows); dfree(e->xm.d_cls);
-    e->xm.ok = false;
-    e->mw_n = 0;
-    e->mw_nev = 0;
-    e->mem_live = false;
-}
-static void free_tick_table(fi_engine *e) {
-    dfree(e->d_tk_done); dfree(e->d_tk_rec);
-}
-static void free_fw(fi_engine *e) {
-    dfree(e->d_fw_off); dfree(e->d_fw_ev); dfree(e->d_loops); dfree(e->d_ex_classes);
-    e->fw_ok = e->ex_ok = false;
-    e->fw_off.clear(); e->fw_ev.clear();
-    e->n_loops = 0;
-}
-static void free_tx(fi_engine *e) {
-    for (auto &m : e->tx_mod) {
-        if (m) (void)hipModuleUnload(m);
-        m = nullptr;
-    }
-    e->tx_fn = e->tx_fn_solo = e->tx_fn_odd = nullptr;
-    e->jit.reset();   // a build in flight finishes on its own (its thread holds the job; fi_destroy joins it)
-}
-
 // Install a finished background build (at a chunk boundary, before anything
 // of the chunk is queued on st): load the code objects and flag the block
 // leaders in the pre-decoded text.  wait = block until the build is done.
 static void jit_install(fi_engine *e, hipStream_t st, bool wait) {
-    std::shared_ptr<JitJob> j = e->jit;
+    std::shared_ptr<JitJob> j = e->gold.jit;
     if (!j) return;
     {
         std::unique_lock<std::mutex> lk(j->mu);
         if (wait) j->cv.wait(lk, [&] { return j->done; });
         if (!j->done) return;
     }
-    e->jit.reset();
+    e->gold.jit.reset();
     // join the builds that have finished (this one, and any an earlier golden
     // run left behind): a long-lived engine keeps no finished threads
     for (size_t i = 0; i < e->jit_threads.size();) {
@@ -592,44 +659,28 @@ static void jit_install(fi_engine *e, hipStream_t st, bool wait) {
         }
     }
     if (!j->err.empty()) {
-        e->tx_status = j->err;
+        e->gold.tx_status = j->err;
         return;
     }
-    hipFunction_t *fn[3] = {&e->tx_fn, &e->tx_fn_solo, &e->tx_fn_odd};
+    Tx tx;   // (unloads itself unless it is moved in)
+    hipFunction_t *fn[3] = {&tx.fn, &tx.fn_solo, &tx.fn_odd};
     for (int k = 0; k < (j->odd ? 3 : 2); k++) {
-        if (hipModuleLoadData(&e->tx_mod[k], j->code[k].data()) != hipSuccess ||
-            hipModuleGetFunction(fn[k], e->tx_mod[k], kTxKernel[k]) != hipSuccess) {
-            free_tx(e);
-            e->tx_status = "code object did not load";
+        if (hipModuleLoadData(&tx.mod[k].m, j->code[k].data()) != hipSuccess ||
+            hipModuleGetFunction(fn[k], tx.mod[k].m, kTxKernel[k]) != hipSuccess) {
+            e->gold.tx_status = "code object did not load";
             return;
         }
     }
-    if (hipMemcpyAsync(e->d_pre, e->jit_pre.data(), e->jit_pre.size() * sizeof(PreInst), hipMemcpyHostToDevice, st) !=
+    if (hipMemcpyAsync(e->img.d_pre, e->gold.jit_pre.data(), e->gold.jit_pre.size() * sizeof(PreInst), hipMemcpyHostToDevice, st) !=
         hipSuccess) {
-        free_tx(e);
-        e->tx_status = "pre-decoded text upload failed";
+        e->gold.tx_status = "pre-decoded text upload failed";
         return;
     }
-    e->tx_status = "";
-    e->golden.translated_blocks = e->jit_blocks;
-    e->golden.translated_insts = e->jit_insts;
-    e->golden.translate_us = j->cached ? 0 : j->us;
-}
-static void free_image(fi_engine *e) {
-    dfree(e->d_pre); dfree(e->d_zero); dfree(e->d_sink);
-    dfree(e->d_text); dfree(e->d_mem_pages); dfree(e->d_gout); dfree(e->d_gerr);
-    dfree(e->d_fp0); dfree(e->d_vm0);
-    e->fp0_on = e->vm0_on = false;
-    e->tick0 = 0;
-    free_snaps(e);
-    free_mem_index(e);
-    free_fw(e);
-    free_tick_table(e);
-    free_tx(e);
-    dfree(e->d_shadow);
-    e->g_pre.clear(); e->g_trace.clear(); e->shadow.clear();
-    e->have_golden = false;
-    e->loaded = false;
+    e->gold.tx = std::move(tx);
+    e->gold.tx_status = "";
+    e->gold.info.translated_blocks = e->gold.jit_blocks;
+    e->gold.info.translated_insts = e->gold.jit_insts;
+    e->gold.info.translate_us = j->cached ? 0 : j->us;
 }
 
 void fi_destroy(fi_engine *e) {
@@ -641,22 +692,11 @@ void fi_destroy(fi_engine *e) {
     for (auto &t : e->jit_threads)
         if (t.first.joinable()) t.first.join();
     (void)hipSetDevice(e->dev);
-    free_work(e);
-    free_image(e);
-    dfree(e->d_rnd); dfree(e->d_exe); dfree(e->d_stdin);
     for (auto &tp : e->tpool) { (void)hipEventDestroy(tp.first); (void)hipEventDestroy(tp.second); }
-    dfree(e->d_span);
-    if (e->ev0) (void)hipEventDestroy(e->ev0);
-    if (e->ev1) (void)hipEventDestroy(e->ev1);
+    for (hipEvent_t ev : {e->ev0, e->ev1, e->ev_fork, e->ev_join, e->ev_cnt[0], e->ev_cnt[1], e->ev_stage[0], e->ev_stage[1]})
+        if (ev) (void)hipEventDestroy(ev);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     if (e->stream_odd) (void)hipStreamDestroy(e->stream_odd);
-    if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    if (e->ev_join) (void)hipEventDestroy(e->ev_join);
-    if (e->h_redo_cnt) (void)hipHostFree(e->h_redo_cnt);
-    for (auto ev : e->ev_cnt)
-        if (ev) (void)hipEventDestroy(ev);
-    for (auto ev : e->ev_stage)
-        if (ev) (void)hipEventDestroy(ev);
     delete e;
 }
 
@@ -668,15 +708,15 @@ static uint32_t le32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1]
 static uint64_t le64(const uint8_t *p) { return (uint64_t)le32(p) | ((uint64_t)le32(p + 4) << 32); }
 
 // SETranslatingPortProxy(Always) write: allocates pages on demand.
-static void img_write(fi_engine *e, uint64_t addr, const uint8_t *src, uint64_t n) {
+static void img_write(Image &img, uint64_t addr, const uint8_t *src, uint64_t n) {
     for (uint64_t i = 0; i < n;) {
         const uint64_t a = addr + i;
-        auto &pg = e->pages[a >> 12];
+        auto &pg = img.pages[a >> 12];
         if (pg.empty()) {
             pg.assign(kPage, 0);
             // SETranslatingPortProxy (Always) allocates the frame on this first
             // write: frames go out in this order (sim/process.cc:318-343)
-            e->alloc_order.push_back(a >> 12);
+            img.alloc_order.push_back(a >> 12);
         }
         const uint64_t off = a & (kPage - 1);
         const uint64_t k = std::min<uint64_t>(n - i, kPage - off);
@@ -685,10 +725,10 @@ static void img_write(fi_engine *e, uint64_t addr, const uint8_t *src, uint64_t 
         i += k;
     }
 }
-static void img_push64(fi_engine *e, uint64_t &sp, uint64_t v) {
+static void img_push64(Image &img, uint64_t &sp, uint64_t v) {
     uint8_t b[8];
     for (int i = 0; i < 8; i++) b[i] = (uint8_t)(v >> (8 * i));
-    img_write(e, sp, b, 8);
+    img_write(img, sp, b, 8);
     sp += 8;
 }
 
@@ -725,57 +765,48 @@ struct Mt64 {
 // (ecall events are replayed but numInst does not count them), uploaded as a
 // bitmap for the result-fault commit (fi_trial.hip:replicated).
 static fi_status compute_shadow(fi_engine *e) {
-    if (e->g_trace.empty() && e->golden.ninst)
+    if (e->gold.g_trace.empty() && e->gold.info.ninst)
         return fail(e, FI_E_STATE, "issue model: the golden trace is unavailable (trace overflow or rewritten text)");
-    const std::vector<fi_issue_op> ops = issue_ops_from_trace(e->g_pre, e->g_trace);
+    const std::vector<fi_issue_op> ops = issue_ops_from_trace(e->gold.g_pre, e->gold.g_trace);
     std::vector<uint8_t> all(ops.size());
     fi_issue_stats st{};
     const fi_status s = fi_issue_model_run(ops.data(), ops.size(), &e->issue_p, all.data(), &st);
     if (s) return fail(e, s, "issue model: invalid parameters");
-    e->shadow.clear();
-    e->shadow.reserve(e->golden.ninst);
+    e->gold.shadow.clear();
+    e->gold.shadow.reserve(e->gold.info.ninst);
     for (size_t i = 0; i < ops.size(); i++)
-        if (!(e->g_trace[i] & 0x80000000u)) e->shadow.push_back(all[i]);
-    if (e->shadow.size() != e->golden.ninst)
-        return fail(e, FI_E_STATE, "issue model: trace holds %zu instructions, golden run %llu", e->shadow.size(),
-                    (unsigned long long)e->golden.ninst);
-    std::vector<uint32_t> bits(e->shadow.size() / 32 + 1, 0);
-    for (size_t k = 0; k < e->shadow.size(); k++)
-        if (e->shadow[k]) bits[k >> 5] |= 1u << (k & 31);
-    dfree(e->d_shadow);
-    HIPCHK(hipMalloc(&e->d_shadow, bits.size() * 4));
-    HIPCHK(hipMemcpy(e->d_shadow, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
-    e->issue_stats = st;
+        if (!(e->gold.g_trace[i] & 0x80000000u)) e->gold.shadow.push_back(all[i]);
+    if (e->gold.shadow.size() != e->gold.info.ninst)
+        return fail(e, FI_E_STATE, "issue model: trace holds %zu instructions, golden run %llu", e->gold.shadow.size(),
+                    (unsigned long long)e->gold.info.ninst);
+    std::vector<uint32_t> bits(e->gold.shadow.size() / 32 + 1, 0);
+    for (size_t k = 0; k < e->gold.shadow.size(); k++)
+        if (e->gold.shadow[k]) bits[k >> 5] |= 1u << (k & 31);
+    HIPCHK(e->gold.d_shadow.alloc(bits.size()));
+    HIPCHK(hipMemcpy(e->gold.d_shadow, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
+    e->gold.issue_stats = st;
     return FI_OK;
 }
 
-static fi_status upload_snaps(fi_engine *e) {
-    free_snaps(e);
-    HIPCHK(hipMalloc(&e->d_snaps, e->snaps.size() * sizeof(SnapState)));
-    HIPCHK(hipMalloc(&e->d_tab, std::max<size_t>(1, e->tab.size()) * sizeof(PageEnt)));
+static fi_status upload_snaps(fi_engine *e, Image &img) {
+    HIPCHK(img.d_snaps.alloc(img.snaps.size()));
+    HIPCHK(img.d_tab.alloc(std::max<size_t>(1, img.tab.size())));
     // (+64: solo translated code reads shared frames with dword-granular scalar
     // loads that may run up to 11 bytes past an access at a frame's end)
-    HIPCHK(hipMalloc(&e->d_pool, std::max<size_t>(kPage, e->pool.size()) + 64));
-    HIPCHK(hipMemcpy(e->d_snaps, e->snaps.data(), e->snaps.size() * sizeof(SnapState), hipMemcpyHostToDevice));
-    if (!e->tab.empty())
-        HIPCHK(hipMemcpy(e->d_tab, e->tab.data(), e->tab.size() * sizeof(PageEnt), hipMemcpyHostToDevice));
-    if (!e->pool.empty()) HIPCHK(hipMemcpy(e->d_pool, e->pool.data(), e->pool.size(), hipMemcpyHostToDevice));
+    HIPCHK(img.d_pool.alloc(std::max<size_t>(kPage, img.pool.size()) + 64));
+    HIPCHK(hipMemcpy(img.d_snaps, img.snaps.data(), img.snaps.size() * sizeof(SnapState), hipMemcpyHostToDevice));
+    if (!img.tab.empty())
+        HIPCHK(hipMemcpy(img.d_tab, img.tab.data(), img.tab.size() * sizeof(PageEnt), hipMemcpyHostToDevice));
+    if (!img.pool.empty()) HIPCHK(hipMemcpy(img.d_pool, img.pool.data(), img.pool.size(), hipMemcpyHostToDevice));
     return FI_OK;
 }
 
-static fi_status finish_load(fi_engine *e, const uint64_t regs[32], uint64_t pc);
-
-fi_status fi_load_elf(fi_engine *e, const uint8_t *elf, size_t len, const char *const *argv, const char *const *envp) {
-    if (!e || !elf || !argv || !argv[0]) return fail(e, FI_E_ARG, "fi_load_elf: elf and argv[0] required");
-    HIPCHK(hipSetDevice(e->dev));
-    free_image(e);
-    e->pages.clear();
-    e->mem_pages.clear();
-    e->segs.clear();
-    e->alloc_order.clear();
+// The host side of an ELF's process-start image, and its start registers.
+static fi_status elf_image(fi_engine *e, Image &img, const uint8_t *elf, size_t len, const char *const *argv,
+                           const char *const *envp, uint64_t regs[32]) {
     if (len < 64 || memcmp(elf, "\x7f" "ELF", 4) || elf[4] != 2 || elf[5] != 1 || le16(elf + 18) != 243)
         return fail(e, FI_E_ELF, "not an ELF64 little-endian RISC-V executable");
-    e->entry = le64(elf + 24);
+    img.entry = le64(elf + 24);
     const uint64_t phoff = le64(elf + 32);
     const uint32_t phentsize = le16(elf + 54), phnum = le16(elf + 56);
     if (phoff + (uint64_t)phentsize * phnum > len) return fail(e, FI_E_ELF, "program headers out of file");
@@ -790,10 +821,10 @@ fi_status fi_load_elf(fi_engine *e, const uint8_t *elf, size_t len, const char *
         const uint64_t filesz = le64(ph + 32), memsz = le64(ph + 40);
         if (memsz == 0) continue;                       // elf_object.cc:378-381
         if (off + filesz > len) return fail(e, FI_E_ELF, "segment %u beyond file", i);
-        img_write(e, paddr, elf + off, filesz);          // loaded at p_paddr (elf_object.cc:383)
-        if (memsz > filesz) img_write(e, paddr + filesz, nullptr, memsz - filesz);
+        img_write(img, paddr, elf + off, filesz);          // loaded at p_paddr (elf_object.cc:383)
+        if (memsz > filesz) img_write(img, paddr + filesz, nullptr, memsz - filesz);
         max_addr = std::max(max_addr, paddr + memsz);
-        e->segs.push_back({paddr & ~(kPage - 1), (paddr + memsz + kPage - 1) & ~(kPage - 1), (flags & 2) != 0});
+        img.segs.push_back({paddr & ~(kPage - 1), (paddr + memsz + kPage - 1) & ~(kPage - 1), (flags & 2) != 0});
         if (off <= phoff && off + filesz > phoff) phdr_vaddr = vaddr + (phoff - off);
         if (flags & 1) {
             xlo = std::min(xlo, paddr & ~(kPage - 1));
@@ -806,10 +837,10 @@ fi_status fi_load_elf(fi_engine *e, const uint8_t *elf, size_t len, const char *
     }
     if (xlo == ~0ULL) return fail(e, FI_E_ELF, "no executable segment");
     if ((xlo >> 32) != ((xhi - 1) >> 32)) return fail(e, FI_E_ELF, "executable segments cross a 4 GiB boundary");
-    e->text_lo = xlo;
-    e->text_hi = xhi;
-    e->code_lo = clo;
-    e->code_hi = chi;
+    img.text_lo = xlo;
+    img.text_hi = xhi;
+    img.code_lo = clo;
+    img.code_hi = chi;
 
     // RiscvProcess::argsInit<uint64_t> (src/arch/riscv/process.cc:134-261)
     std::vector<std::string> av, ev;
@@ -826,225 +857,185 @@ fi_status fi_load_elf(fi_engine *e, const uint8_t *elf, size_t len, const char *
     stack_top -= arrays;
     stack_top &= ~15ULL;
     const uint64_t stack_size = kStackBase - stack_top;
-    e->svma_lo = stack_top & ~(kPage - 1);
-    e->svma_hi = e->svma_lo + ((stack_size + kPage - 1) & ~(kPage - 1));
+    img.svma_lo = stack_top & ~(kPage - 1);
+    img.svma_hi = img.svma_lo + ((stack_size + kPage - 1) & ~(kPage - 1));
     stack_min -= 16;
     Mt64 rng(5489);
     uint8_t rnd[16];
     for (int i = 0; i < 16; i++) rnd[i] = (uint8_t)(rng() % 256);
-    img_write(e, stack_min, rnd, 16);
+    img_write(img, stack_min, rnd, 16);
     std::vector<uint64_t> argp, envptr;
-    for (auto &s : av) { stack_min -= s.size() + 1; img_write(e, stack_min, (const uint8_t *)s.c_str(), s.size() + 1); argp.push_back(stack_min); }
-    for (auto &s : ev) { stack_min -= s.size() + 1; img_write(e, stack_min, (const uint8_t *)s.c_str(), s.size() + 1); envptr.push_back(stack_min); }
+    for (auto &s : av) { stack_min -= s.size() + 1; img_write(img, stack_min, (const uint8_t *)s.c_str(), s.size() + 1); argp.push_back(stack_min); }
+    for (auto &s : ev) { stack_min -= s.size() + 1; img_write(img, stack_min, (const uint8_t *)s.c_str(), s.size() + 1); envptr.push_back(stack_min); }
     stack_min &= ~7ULL;
     stack_min -= arrays;
     stack_min &= ~15ULL;
     uint64_t sp = stack_min;
-    img_push64(e, sp, av.size());
-    for (uint64_t p : argp) img_push64(e, sp, p);
-    img_push64(e, sp, 0);
-    for (uint64_t p : envptr) img_push64(e, sp, p);
-    img_push64(e, sp, 0);
-    const uint64_t aux[8][2] = {{9, e->entry}, {5, phnum}, {4, phentsize}, {3, phdr_vaddr},
+    img_push64(img, sp, av.size());
+    for (uint64_t p : argp) img_push64(img, sp, p);
+    img_push64(img, sp, 0);
+    for (uint64_t p : envptr) img_push64(img, sp, p);
+    img_push64(img, sp, 0);
+    const uint64_t aux[8][2] = {{9, img.entry}, {5, phnum}, {4, phentsize}, {3, phdr_vaddr},
                                 {6, kPage}, {23, 0}, {25, at_random}, {0, 0}};
-    for (auto &a : aux) { img_push64(e, sp, a[0]); img_push64(e, sp, a[1]); }
-    e->sp0 = stack_min;
-    e->stack_min0 = stack_min & ~(kPage - 1);
-    for (uint64_t pg = e->stack_min0;; pg += kPage) {
+    for (auto &a : aux) { img_push64(img, sp, a[0]); img_push64(img, sp, a[1]); }
+    img.sp0 = stack_min;
+    img.stack_min0 = stack_min & ~(kPage - 1);
+    for (uint64_t pg = img.stack_min0;; pg += kPage) {
         wpages.push_back(pg);
         if (pg == (kStackBase & ~(kPage - 1))) break;
     }
     std::sort(wpages.begin(), wpages.end());
     wpages.erase(std::unique(wpages.begin(), wpages.end()), wpages.end());
-    e->mem_pages = wpages;
-    e->brk0 = (max_addr + kPage - 1) & ~(kPage - 1);   // Process brk point (process.cc: roundUp(maxAddr))
+    img.mem_pages = wpages;
+    img.brk0 = (max_addr + kPage - 1) & ~(kPage - 1);   // Process brk point (process.cc: roundUp(maxAddr))
     // RiscvProcess::argsInit leaves every register 0 but sp; pc = e_entry
-    uint64_t regs[32] = {};
-    regs[2] = e->sp0;
-    return finish_load(e, regs, e->entry);
+    regs[2] = img.sp0;
+    return FI_OK;
 }
 
-// ---- snapshot 0: the start image in e->pages (frames sorted by vpn) and the
+// ---- snapshot 0: the start image in img.pages (frames sorted by vpn) and the
 // initial architectural state; the text pre-decoded on the device.  The
 // common tail of fi_load_elf and fi_load_checkpoint.
-static fi_status finish_load(fi_engine *e, const uint64_t regs[32], uint64_t pc) {
-    const std::vector<uint64_t> &wpages = e->mem_pages;
-    e->pool.clear();
-    e->tab.clear();
-    e->snaps.clear();
-    for (auto &kv : e->pages) {
+static fi_status finish_load(fi_engine *e, Image &img, const uint64_t regs[32], uint64_t pc) {
+    const std::vector<uint64_t> &wpages = img.mem_pages;
+    img.pool.clear();
+    img.tab.clear();
+    img.snaps.clear();
+    for (auto &kv : img.pages) {
         PageEnt pe{};
         pe.vpn = kv.first;
-        pe.frame = (uint32_t)(e->pool.size() / kPage);
-        e->tab.push_back(pe);
-        e->pool.insert(e->pool.end(), kv.second.begin(), kv.second.end());
+        pe.frame = (uint32_t)(img.pool.size() / kPage);
+        img.tab.push_back(pe);
+        img.pool.insert(img.pool.end(), kv.second.begin(), kv.second.end());
     }
-    e->n_start_frames = (uint32_t)e->tab.size();
+    img.n_start_frames = (uint32_t)img.tab.size();
     SnapState s0{};
     for (int r = 1; r < 32; r++) s0.regs[r] = regs[r];
     s0.pc = pc;
-    s0.stack_min = e->stack_min0;
+    s0.stack_min = img.stack_min0;
     s0.tab_off = 0;
-    s0.tab_n = (uint32_t)e->tab.size();
-    e->snaps.push_back(s0);
-    e->snap_I = 1ULL << 62;
-    e->pre_ok = true;
+    s0.tab_n = (uint32_t)img.tab.size();
+    img.snaps.push_back(s0);
     {
-        fi_status st = upload_snaps(e);
+        fi_status st = upload_snaps(e, img);
         if (st) return st;
     }
-    HIPCHK(hipMalloc(&e->d_zero, kPage + 64));   // (+64: as the frame pool)
-    HIPCHK(hipMalloc(&e->d_sink, kPage));
-    HIPCHK(hipMalloc(&e->d_mem_pages, std::max<size_t>(1, wpages.size()) * 8));
-    HIPCHK(hipMemset(e->d_zero, 0, kPage + 64));
-    if (!wpages.empty()) HIPCHK(hipMemcpy(e->d_mem_pages, wpages.data(), wpages.size() * 8, hipMemcpyHostToDevice));
-    const uint64_t tbytes = e->text_hi - e->text_lo;
+    HIPCHK(img.d_zero.alloc(kPage + 64));   // (+64: as the frame pool)
+    HIPCHK(img.d_sink.alloc(kPage));
+    HIPCHK(img.d_mem_pages.alloc(std::max<size_t>(1, wpages.size())));
+    HIPCHK(hipMemset(img.d_zero, 0, kPage + 64));
+    if (!wpages.empty()) HIPCHK(hipMemcpy(img.d_mem_pages, wpages.data(), wpages.size() * 8, hipMemcpyHostToDevice));
+    const uint64_t tbytes = img.text_hi - img.text_lo;
     std::vector<uint8_t> text(tbytes, 0);
-    for (uint64_t a = e->text_lo; a < e->text_hi; a += kPage) {
-        auto it = e->pages.find(a >> 12);
-        if (it != e->pages.end()) memcpy(text.data() + (a - e->text_lo), it->second.data(), kPage);
+    for (uint64_t a = img.text_lo; a < img.text_hi; a += kPage) {
+        auto it = img.pages.find(a >> 12);
+        if (it != img.pages.end()) memcpy(text.data() + (a - img.text_lo), it->second.data(), kPage);
     }
-    HIPCHK(hipMalloc(&e->d_text, tbytes));
-    HIPCHK(hipMemcpy(e->d_text, text.data(), tbytes, hipMemcpyHostToDevice));
+    HIPCHK(img.d_text.alloc(tbytes));
+    HIPCHK(hipMemcpy(img.d_text, text.data(), tbytes, hipMemcpyHostToDevice));
     // + kPreTail zero entries (kind K_SLOW): the solo interpreter prefetches
     // the fall-through entry of the text's last instruction without a clamp
-    HIPCHK(hipMalloc(&e->d_pre, (tbytes / 2 + kPreTail) * sizeof(PreInst)));
-    HIPCHK(hipMemset(e->d_pre + tbytes / 2, 0, kPreTail * sizeof(PreInst)));
-    HIPCHK(launch_predecode(e->d_text, e->code_lo - e->text_lo, e->code_hi - e->text_lo, tbytes / 2, e->d_pre,
+    HIPCHK(img.d_pre.alloc(tbytes / 2 + kPreTail));
+    HIPCHK(hipMemset(img.d_pre + tbytes / 2, 0, kPreTail * sizeof(PreInst)));
+    HIPCHK(launch_predecode(img.d_text, img.code_lo - img.text_lo, img.code_hi - img.text_lo, tbytes / 2, img.d_pre,
                             e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    e->loaded = true;
+    img.loaded = true;
     return FI_OK;
+}
+
+// A load starts from an engine with no image and no golden run, and moves its
+// own image in once it is whole: a failed load leaves the engine unloaded.
+static fi_status unload(fi_engine *e) {
+    HIPCHK(hipSetDevice(e->dev));
+    e->gold = Golden{};
+    e->img = Image{};
+    return FI_OK;
+}
+
+fi_status fi_load_elf(fi_engine *e, const uint8_t *elf, size_t len, const char *const *argv, const char *const *envp) {
+    if (!e || !elf || !argv || !argv[0]) return fail(e, FI_E_ARG, "fi_load_elf: elf and argv[0] required");
+    fi_status st = unload(e);
+    Image img;
+    uint64_t regs[32] = {};
+    if (!st) st = elf_image(e, img, elf, len, argv, envp, regs);
+    if (!st) st = finish_load(e, img, regs, img.entry);
+    if (!st) e->img = std::move(img);
+    return st;
+}
+
+fi_status fi_load_checkpoint(fi_engine *e, const char *cpt_dir, const uint8_t *elf, size_t len) {
+    if (!e || !cpt_dir || !elf) return fail(e, FI_E_ARG, "fi_load_checkpoint: checkpoint directory and ELF required");
+    fi_status st = unload(e);
+    if (st) return st;
+    const char *argv[] = {"checkpoint", nullptr};
+    Image img;
+    uint64_t regs[32];
+    st = elf_image(e, img, elf, len, argv, nullptr, regs);   // executable range, segments, entry checks
+    if (st) return st;
+    CptImage cpt;
+    const std::string err = read_gem5_checkpoint(cpt_dir, cpt);
+    if (!err.empty()) return fail(e, FI_E_ARG, "fi_load_checkpoint: %s", err.c_str());
+    // the engine's SE model keeps RiscvProcess64's stack (process.cc:71-82)
+    if (cpt.stack_base != kStackBase || cpt.max_stack != kMaxStack)
+        return fail(e, FI_E_ARG, "fi_load_checkpoint: stack base / max stack differ from RiscvProcess64's");
+    if (cpt.vmas.size() > kMaxVma)
+        return fail(e, FI_E_ARG, "fi_load_checkpoint: %zu VMAs (at most %u)", cpt.vmas.size(), kMaxVma);
+    // the checkpoint's pages in the ELF's place
+    img.pages.clear();
+    img.alloc_order.clear();   // a checkpoint's frames: not in process-start order (no tick model)
+    for (auto &kv : cpt.pages) img.pages[kv.first] = kv.second;
+    // memory-fault candidates, as at process start (the ELF's writable
+    // segments and the stack): every mapped page no read-only PT_LOAD covers
+    img.mem_pages.clear();
+    for (auto &kv : cpt.pages) {
+        const uint64_t a = kv.first << 12;
+        bool ro = false, w = false;
+        for (const Seg &g : img.segs)
+            if (a >= g.lo && a < g.hi) (g.w ? w : ro) = true;
+        if (w || !ro) img.mem_pages.push_back(a);
+    }
+    img.brk0 = cpt.brk;
+    img.svma_lo = img.svma_hi = 0;
+    for (size_t i = 0; i < cpt.vmas.size(); i++)
+        if (cpt.vma_names[i] == "stack") { img.svma_lo = cpt.vmas[i].first; img.svma_hi = cpt.vmas[i].second; }
+    // a VMA list other than argsInit's lone stack VMA, or another mmap end:
+    // the trials start from it (DevCtx::vm0)
+    const bool plain = cpt.vmas.size() == 1 && cpt.vma_names[0] == "stack" && cpt.mmap_end == 0x4000000000000000ULL;
+    img.vm0_on = !plain;
+    if (img.vm0_on) {
+        img.vm0.brk = cpt.brk; img.vm0.mmap_end = cpt.mmap_end;
+        img.vm0.nvma = (uint32_t)cpt.vmas.size();
+        for (size_t i = 0; i < cpt.vmas.size(); i++) { img.vm0.vma[i][0] = cpt.vmas[i].first; img.vm0.vma[i][1] = cpt.vmas[i].second; }
+        HIPCHK(img.d_vm0.alloc(1));
+        HIPCHK(hipMemcpy(img.d_vm0, &img.vm0, sizeof(VmState), hipMemcpyHostToDevice));
+    }
+    img.fp0_on = cpt.fp_state;
+    memcpy(img.fp0, cpt.fregs, sizeof img.fp0);
+    img.fcsr0 = cpt.fflags | (cpt.frm << 5);
+    if (img.fp0_on) {
+        HIPCHK(img.d_fp0.alloc(32));
+        HIPCHK(hipMemcpy(img.d_fp0, img.fp0, 32 * 8, hipMemcpyHostToDevice));
+    }
+    img.tick0 = cpt.tick0;
+    img.sp0 = cpt.regs[2];
+    img.stack_min0 = cpt.stack_min & ~(kPage - 1);
+    st = finish_load(e, img, cpt.regs, cpt.pc);
+    if (!st) e->img = std::move(img);
+    return st;
 }
 
 // ------------------------------------------------------------------ work buffers
-fi_status fi_load_checkpoint(fi_engine *e, const char *cpt_dir, const uint8_t *elf, size_t len) {
-    if (!e || !cpt_dir || !elf) return fail(e, FI_E_ARG, "fi_load_checkpoint: checkpoint directory and ELF required");
-    const char *argv[] = {"checkpoint", nullptr};
-    fi_status st = fi_load_elf(e, elf, len, argv, nullptr);   // executable range, entry checks
-    if (st) return st;
-    CptImage img;
-    const std::string err = read_gem5_checkpoint(cpt_dir, img);
-    if (!err.empty()) return fail(e, FI_E_ARG, "fi_load_checkpoint: %s", err.c_str());
-    // the engine's SE model keeps RiscvProcess64's stack (process.cc:71-82)
-    if (img.stack_base != kStackBase || img.max_stack != kMaxStack)
-        return fail(e, FI_E_ARG, "fi_load_checkpoint: stack base / max stack differ from RiscvProcess64's");
-    if (img.vmas.size() > kMaxVma)
-        return fail(e, FI_E_ARG, "fi_load_checkpoint: %zu VMAs (at most %u)", img.vmas.size(), kMaxVma);
-    const std::vector<fi_engine::Seg> segs = e->segs;   // (fi_load_elf's; free_image keeps them)
-    free_image(e);
-    e->pages.clear();
-    e->alloc_order.clear();   // a checkpoint's frames: not in process-start order (no tick model)
-    for (auto &kv : img.pages) e->pages[kv.first] = kv.second;
-    // memory-fault candidates, as at process start (the ELF's writable
-    // segments and the stack): every mapped page no read-only PT_LOAD covers
-    e->mem_pages.clear();
-    for (auto &kv : img.pages) {
-        const uint64_t a = kv.first << 12;
-        bool ro = false, w = false;
-        for (const fi_engine::Seg &g : segs)
-            if (a >= g.lo && a < g.hi) (g.w ? w : ro) = true;
-        if (w || !ro) e->mem_pages.push_back(a);
-    }
-    e->brk0 = img.brk;
-    e->svma_lo = e->svma_hi = 0;
-    for (size_t i = 0; i < img.vmas.size(); i++)
-        if (img.vma_names[i] == "stack") { e->svma_lo = img.vmas[i].first; e->svma_hi = img.vmas[i].second; }
-    // a VMA list other than argsInit's lone stack VMA, or another mmap end:
-    // the trials start from it (DevCtx::vm0)
-    const bool plain = img.vmas.size() == 1 && img.vma_names[0] == "stack" && img.mmap_end == 0x4000000000000000ULL;
-    e->vm0_on = !plain;
-    if (e->vm0_on) {
-        e->vm0 = VmState{};
-        e->vm0.brk = img.brk; e->vm0.mmap_end = img.mmap_end;
-        e->vm0.nvma = (uint32_t)img.vmas.size();
-        for (size_t i = 0; i < img.vmas.size(); i++) { e->vm0.vma[i][0] = img.vmas[i].first; e->vm0.vma[i][1] = img.vmas[i].second; }
-    }
-    e->fp0_on = img.fp_state;
-    memcpy(e->fp0, img.fregs, sizeof e->fp0);
-    e->fcsr0 = img.fflags | (img.frm << 5);
-    e->tick0 = img.tick0;
-    e->sp0 = img.regs[2];
-    e->stack_min0 = img.stack_min & ~(kPage - 1);
-    fi_status st2 = finish_load(e, img.regs, img.pc);
-    if (st2) return st2;
-    if (e->vm0_on) {
-        HIPCHK(hipMalloc(&e->d_vm0, sizeof(VmState)));
-        HIPCHK(hipMemcpy(e->d_vm0, &e->vm0, sizeof(VmState), hipMemcpyHostToDevice));
-    }
-    if (e->fp0_on) {
-        HIPCHK(hipMalloc(&e->d_fp0, 32 * 8));
-        HIPCHK(hipMemcpy(e->d_fp0, e->fp0, 32 * 8, hipMemcpyHostToDevice));
-    }
-    return FI_OK;
-}
-
-// Private pages per trial of the second pass (chunk_end) and, with the
-// overflow pool, a trial's capacity in the first: 16 P, at least 256.
-
+// Growth replaces every work buffer (the tick map's and the capture rows
+// with them): the old ones go first, the new ones move in once all are made.
 static fi_status ensure_work(fi_engine *e, uint64_t n) {
-    if (n <= e->cap) return FI_OK;
-    free_work(e);
-    const uint64_t c = n;
-    HIPCHK(hipMalloc(&e->d_sites, c * sizeof(fi_site)));
-    HIPCHK(hipMalloc(&e->d_sites_alt, c * sizeof(fi_site)));
-    HIPCHK(hipMalloc(&e->d_weight[0], c * 4));
-    HIPCHK(hipMalloc(&e->d_weight[1], c * 4));
-    HIPCHK(hipMalloc(&e->d_keys, c * 8));
-    HIPCHK(hipMalloc(&e->d_keys2, c * 8));
-    HIPCHK(hipMalloc(&e->d_perm, c * 4));
-    HIPCHK(hipMalloc(&e->d_perm2, c * 4));
-    HIPCHK(sort_pairs_bytes(c, e->tmp_bytes));
-    HIPCHK(hipMalloc(&e->d_tmp, std::max<size_t>(e->tmp_bytes, 16)));
-    HIPCHK(hipMalloc(&e->d_out, c * sizeof(fi_outcome)));
-    HIPCHK(hipMalloc(&e->d_out_alt, c * sizeof(fi_outcome)));
-    HIPCHK(hipMalloc(&e->d_eff, c * 8));
-    HIPCHK(hipMalloc(&e->d_hist, sizeof(fi_histogram)));
-    HIPCHK(hipMalloc(&e->d_stats, kNStats * sizeof(unsigned long long)));
-    HIPCHK(hipMalloc(&e->d_wave_dbg, c * kWaveDbgWords * sizeof(uint64_t)));
-    HIPCHK(hipMalloc(&e->d_priv, c * e->cfg.private_pages * kPage));
-    HIPCHK(hipMalloc(&e->d_priv_vpn, c * e->cfg.private_pages * 8));
-    HIPCHK(hipMalloc(&e->d_save, c * sizeof(LaneSave)));
-    HIPCHK(hipMalloc(&e->d_vm, c * sizeof(VmState)));
-    HIPCHK(hipMalloc(&e->d_fregs, c * 32 * sizeof(uint64_t)));
-    HIPCHK(hipMalloc(&e->d_inpos, c * sizeof(uint64_t)));
-    HIPCHK(hipMalloc(&e->d_surv[0], c * 4));
-    HIPCHK(hipMalloc(&e->d_surv[1], c * 4));
-    HIPCHK(hipMalloc(&e->d_cnt, 16 * 4));
-    HIPCHK(hipMalloc(&e->d_skeys, c * 8));
-    HIPCHK(hipMalloc(&e->d_skeys2, c * 8));
-    HIPCHK(hipMalloc(&e->d_svals, c * 4));
-    HIPCHK(hipMalloc(&e->d_svals2, c * 4));
-    HIPCHK(hipMalloc(&e->d_wrange, c * 8));
-    HIPCHK(hipMalloc(&e->d_nwaves, 16 * 4));
-    HIPCHK(hipMalloc(&e->d_split, 64 * 4));
-    HIPCHK(hipMalloc(&e->d_dmap, c * kDmapWords * 4));
-    HIPCHK(hipMalloc(&e->d_redo_idx, 2 * c * 4));
-    HIPCHK(hipMalloc(&e->d_redo_cnt, 16));
-    HIPCHK(hipMalloc(&e->d_redo_sites, c * sizeof(fi_site)));
-    HIPCHK(hipMalloc(&e->d_redo_out, c * sizeof(fi_outcome)));
-    if (!e->h_redo_cnt) HIPCHK(hipHostMalloc(&e->h_redo_cnt, 16));
-    for (auto &ev : e->ev_cnt)
-        if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    // (the pinned staging of host-bound outcomes is made on first use:
-    // chunk_end; device-resident runs never need it)
-    for (int i = 0; i < 2; i++)
-        if (!e->ev_stage[i]) HIPCHK(hipEventCreateWithFlags(&e->ev_stage[i], hipEventDisableTiming));
-    // overflow pool: a trial past P pages takes a block of P' - P more (P' the
-    // redo pass's page count), one block per 2048 slots (at least 64)
-    {
-        const uint64_t P = e->cfg.private_pages, P2 = redo_pages(P);
-        if (!(e->cfg.flags & FI_CFG_NO_OVERFLOW) && P2 > P) {
-            e->ov_pages = (uint32_t)(P2 - P);
-            e->ov_blocks = (uint32_t)std::max<uint64_t>(64, c / 2048);
-            HIPCHK(hipMalloc(&e->d_ov, (uint64_t)e->ov_blocks * e->ov_pages * kPage));
-            HIPCHK(hipMalloc(&e->d_ov_vpn, (uint64_t)e->ov_blocks * e->ov_pages * 8));
-            HIPCHK(hipMalloc(&e->d_ov_of, c * 4));
-            HIPCHK(hipMalloc(&e->d_ov_next, 16));
-        }
-    }
-    e->cap = c;
-    return FI_OK;
+    if (n <= e->w.cap) return FI_OK;
+    e->w = Work{};
+    Work w;
+    fi_status st = work_buffers(e, w, n, nullptr);
+    if (!st) e->w = std::move(w);
+    return st;
 }
 
 // The rewritten-code map's granule: one byte, coarser for large code so that
@@ -1052,7 +1043,7 @@ static fi_status ensure_work(fi_engine *e, uint64_t n) {
 // copy, fi_trial.hip kDmapWords).  (Byte granules: a store next to a loop's
 // instructions leaves the loop's translated blocks usable.)
 static void dmap_params(const fi_engine *e, uint32_t &shift, uint32_t &words) {
-    const uint64_t cb = e->code_hi > e->code_lo ? e->code_hi - e->code_lo : 1;
+    const uint64_t cb = e->img.code_hi > e->img.code_lo ? e->img.code_hi - e->img.code_lo : 1;
     shift = 0;
     while ((cb >> shift) >= kDmapWords * 32) shift++;
     words = (uint32_t)((((cb + (1ULL << shift) - 1) >> shift) + 31) / 32);
@@ -1060,60 +1051,72 @@ static void dmap_params(const fi_engine *e, uint32_t &shift, uint32_t &words) {
 
 static DevCtx base_ctx(fi_engine *e) {
     DevCtx c{};
-    c.pre = e->d_pre; c.text_lo = e->text_lo; c.text_hi = e->text_hi; c.pre_ok = e->pre_ok ? 1 : 0;
-    c.text_bytes = (uint32_t)(e->text_hi - e->text_lo);
-    c.code_lo = e->code_lo; c.code_hi = e->code_hi;
-    c.snaps = e->d_snaps; c.snap_tab = e->d_tab; c.pool = e->d_pool; c.zero_page = e->d_zero;
+    c.pre = e->img.d_pre; c.text_lo = e->img.text_lo; c.text_hi = e->img.text_hi; c.pre_ok = e->gold.pre_ok ? 1 : 0;
+    c.text_bytes = (uint32_t)(e->img.text_hi - e->img.text_lo);
+    c.code_lo = e->img.code_lo; c.code_hi = e->img.code_hi;
+    c.snaps = e->img.d_snaps; c.snap_tab = e->img.d_tab; c.pool = e->img.d_pool; c.zero_page = e->img.d_zero;
     const bool start = !(e->cfg.flags & FI_CFG_NO_SNAPSHOT_START);
-    c.n_snap = (uint32_t)e->snaps.size();
-    c.snap_start = (start && !e->golden_fp) ? 1 : 0;
-    c.snap_interval = e->snap_I;
-    c.early_exit = (!(e->cfg.flags & FI_CFG_NO_EARLY_EXIT) && e->snaps.size() > 1 && !e->golden_fp) ? 1 : 0;
+    c.n_snap = (uint32_t)e->img.snaps.size();
+    c.snap_start = (start && !e->gold.golden_fp) ? 1 : 0;
+    c.snap_interval = e->gold.snap_I;
+    c.early_exit = (!(e->cfg.flags & FI_CFG_NO_EARLY_EXIT) && e->img.snaps.size() > 1 && !e->gold.golden_fp) ? 1 : 0;
     if (c.early_exit && !(e->cfg.flags & FI_CFG_NO_SDC_EXIT)) c.early_exit = 3;   // bit 1: SDC early exit
     c.hang_proof = (e->cfg.flags & FI_CFG_NO_HANG_PROOF) ? 0 : 1;
-    c.gout = e->d_gout; c.gerr = e->d_gerr; c.gout_len = e->gout.size(); c.gerr_len = e->gerr.size();
-    c.gexit = e->golden.exit_code;
-    c.gdetail = e->gdetail;
-    c.gsub = e->gsub;
-    c.gninst = e->golden.ninst;
+    c.gout = e->gold.d_gout; c.gerr = e->gold.d_gerr; c.gout_len = e->gold.gout.size(); c.gerr_len = e->gold.gerr.size();
+    c.gexit = e->gold.info.exit_code;
+    c.gdetail = e->gold.gdetail;
+    c.gsub = e->gold.gsub;
+    c.gninst = e->gold.info.ninst;
     c.priv_pages = e->cfg.private_pages;
-    c.hang_cap = e->golden.ninst * e->cfg.hang_factor_x16 / 16 + 1000;
+    c.hang_cap = e->gold.info.ninst * e->cfg.hang_factor_x16 / 16 + 1000;
     c.protect_mask = e->protect;
     c.protect_opc = e->protect_opc;
-    c.shadow_bits = e->issue_on ? e->d_shadow : nullptr;
-    c.priv_frames = e->d_priv; c.priv_vpn = e->d_priv_vpn;
-    c.ov_frames = e->d_ov; c.ov_vpn = e->d_ov_vpn; c.ov_of = e->d_ov_of; c.ov_next = e->d_ov_next;
-    c.ov_blocks = e->ov_blocks; c.ov_pages = e->ov_pages;
-    c.tx_sink = e->d_sink;
-    c.fregs = e->d_fregs;
-    c.wave_dbg = e->d_wave_dbg;
-    c.stats = e->d_stats;
-    c.brk0 = e->brk0; c.svma_lo = e->svma_lo; c.svma_hi = e->svma_hi; c.vm = e->d_vm;
+    c.shadow_bits = e->issue_on ? e->gold.d_shadow : nullptr;
+    c.priv_frames = e->w.d_priv; c.priv_vpn = e->w.d_priv_vpn;
+    c.ov_frames = e->w.d_ov; c.ov_vpn = e->w.d_ov_vpn; c.ov_of = e->w.d_ov_of; c.ov_next = e->w.d_ov_next;
+    c.ov_blocks = e->w.ov_blocks; c.ov_pages = e->w.ov_pages;
+    c.tx_sink = e->img.d_sink;
+    c.fregs = e->w.d_fregs;
+    c.wave_dbg = e->w.d_wave_dbg;
+    c.stats = e->w.d_stats;
+    c.brk0 = e->img.brk0; c.svma_lo = e->img.svma_lo; c.svma_hi = e->img.svma_hi; c.vm = e->w.d_vm;
     c.simt_min = (e->cfg.flags & FI_CFG_SIMT) ? 8u : 0u;
     c.rnd_tab = e->d_rnd; c.rnd_len = e->d_rnd ? kRndLen : 0; c.clk_period = e->clk_period;
     c.exe_path = e->d_exe; c.exe_len = e->d_exe ? e->exe_path.size() : 0;
-    c.tick0 = e->tick0;
-    c.clk_until = e->clk_until;
+    c.tick0 = e->img.tick0;
+    c.clk_until = e->gold.clk_until;
     c.stdin_data = e->stdin_on ? e->d_stdin : nullptr;
     c.stdin_len = e->stdin_on ? e->stdin_data.size() : 0;
-    c.in_pos = e->d_inpos;
-    c.fp0 = e->fp0_on ? e->d_fp0 : nullptr;
-    c.fcsr0 = e->fcsr0;
-    c.vm0 = e->vm0_on ? e->d_vm0 : nullptr;
-    c.dmap = e->d_dmap;
+    c.in_pos = e->w.d_inpos;
+    c.fp0 = e->img.fp0_on ? e->img.d_fp0 : nullptr;
+    c.fcsr0 = e->img.fcsr0;
+    c.vm0 = e->img.vm0_on ? e->img.d_vm0 : nullptr;
+    c.dmap = e->w.d_dmap;
     dmap_params(e, c.dmap_shift, c.dmap_words);
     c.lanes = e->cfg.lanes_per_wave;
-    c.mem_live = (e->mem_live && !(e->cfg.flags & FI_CFG_NO_EARLY_EXIT)) ? 1 : 0;
-    c.mw_n = e->mw_n; c.mw_addr = e->d_mw_addr; c.mw_off = e->d_mw_off; c.mw_ev = e->d_mw_ev;
+    c.mem_live = (e->gold.mem_live && !(e->cfg.flags & FI_CFG_NO_EARLY_EXIT)) ? 1 : 0;
+    c.mw_n = e->gold.mw_n; c.mw_addr = e->gold.d_mw_addr; c.mw_off = e->gold.d_mw_off; c.mw_ev = e->gold.d_mw_ev;
     return c;
 }
 
-// One golden (fault-free, record-mode) launch: a single lane from snapshot 0.
-// P private pages; rec_* capture snapshots every rec_I instructions (0 = off).
-static fi_status golden_launch(fi_engine *e, uint32_t P, uint64_t rec_I, uint32_t rec_max, SnapState *d_rs,
-                               uint8_t *d_rp, uint64_t *d_rv, uint32_t *d_trace, uint32_t trace_cap, uint8_t *d_ro,
-                               uint8_t *d_re, uint64_t rec_cap, fi_outcome &o, unsigned long long *stats,
-                               MemEv *d_mem = nullptr, uint32_t mem_cap = 0) {
+// What a golden launch records, each optional (NULL / 0: not recorded).
+struct GoldenRec {
+    uint8_t *out = nullptr, *err = nullptr;   // stdout / stderr, `cap` bytes each
+    uint64_t cap = 0;
+    uint64_t interval = 0;                    // a snapshot every `interval` instructions, at most max_snaps
+    uint32_t max_snaps = 0;
+    SnapState *snaps = nullptr;
+    uint8_t *pages = nullptr;
+    uint64_t *vpns = nullptr;
+    uint32_t *trace = nullptr, trace_cap = 0;   // the committed instructions and ecalls
+    MemEv *mem = nullptr;                       // the data accesses
+    uint32_t mem_cap = 0;
+};
+
+// One golden (fault-free, record-mode) launch: a single lane from snapshot 0
+// with P private pages.
+static fi_status golden_launch(fi_engine *e, uint32_t P, const GoldenRec &r, fi_outcome &o,
+                               unsigned long long *stats) {
     DevBuf<uint64_t> gvpn, gfregs;   // (declared so that they are freed in the order gpriv, gfregs, gvpn)
     DevBuf<uint8_t> gpriv;
     HIPCHK(gpriv.alloc((uint64_t)P * kPage));
@@ -1127,27 +1130,28 @@ static fi_status golden_launch(fi_engine *e, uint32_t P, uint64_t rec_I, uint32_
     c.record = 1;
     c.early_exit = 0;
     c.snap_start = 0;
-    c.rec_out = d_ro; c.rec_err = d_re; c.rec_cap = rec_cap;
+    c.rec_out = r.out; c.rec_err = r.err; c.rec_cap = r.cap;
     c.hang_cap = 1ULL << 30;   // golden safety cap
     c.priv_pages = P; c.priv_frames = gpriv.get(); c.priv_vpn = gvpn.get();
-    c.rec_snaps = d_rs; c.rec_pages = d_rp; c.rec_vpns = d_rv; c.rec_interval = rec_I; c.rec_max_snaps = rec_max;
-    c.rec_trace = d_trace; c.rec_trace_cap = d_trace ? trace_cap : 0;
-    c.rec_mem = d_mem; c.rec_mem_cap = d_mem ? mem_cap : 0;
+    c.rec_snaps = r.snaps; c.rec_pages = r.pages; c.rec_vpns = r.vpns; c.rec_interval = r.interval; c.rec_max_snaps = r.max_snaps;
+    c.rec_trace = r.trace; c.rec_trace_cap = r.trace ? r.trace_cap : 0;
+    c.rec_mem = r.mem; c.rec_mem_cap = r.mem ? r.mem_cap : 0;
     c.mem_live = 0;
-    c.out = e->d_out;
+    c.out = e->w.d_out;
     c.n = 1;
     c.n_slots = 1;
     c.sites = nullptr; c.perm = nullptr;
-    hipError_t err = hipMemsetAsync(e->d_stats, 0, kNStats * sizeof(unsigned long long), e->stream);
-    if (err == hipSuccess) err = hipEventRecord(e->ev0, e->stream);
-    if (err == hipSuccess) err = launch_trials(c, e->stream);
-    if (err == hipSuccess) err = hipEventRecord(e->ev1, e->stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(e->stream);
+#define GLCHK(call) HIPCHK_AS("golden launch", call)
+    GLCHK(hipMemsetAsync(e->w.d_stats, 0, kNStats * sizeof(unsigned long long), e->stream));
+    GLCHK(hipEventRecord(e->ev0, e->stream));
+    GLCHK(launch_trials(c, e->stream));
+    GLCHK(hipEventRecord(e->ev1, e->stream));
+    GLCHK(hipStreamSynchronize(e->stream));
     float ms = 0;
-    if (err == hipSuccess) err = hipEventElapsedTime(&ms, e->ev0, e->ev1);
-    if (err == hipSuccess) err = hipMemcpy(&o, e->d_out, sizeof o, hipMemcpyDeviceToHost);
-    if (err == hipSuccess) err = hipMemcpy(stats, e->d_stats, kNStats * sizeof(unsigned long long), hipMemcpyDeviceToHost);
-    if (err != hipSuccess) return fail(e, FI_E_HIP, "golden launch: %s", hipGetErrorString(err));
+    GLCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
+    GLCHK(hipMemcpy(&o, e->w.d_out, sizeof o, hipMemcpyDeviceToHost));
+    GLCHK(hipMemcpy(stats, e->w.d_stats, kNStats * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+#undef GLCHK
     e->last_ms = ms;
     if (o.cls != FI_MASKED)
         return fail(e, FI_E_GOLDEN, "golden run did not exit normally (class %u sub %u detail %#x after %llu insts)",
@@ -1161,7 +1165,6 @@ static fi_status golden_launch(fi_engine *e, uint32_t P, uint64_t rec_I, uint32_
 // (fi_trial.hip:mem_dead).  complete = the access trace did not overflow and
 // every golden instruction came from the pre-decoded text.
 static fi_status build_mem_index(fi_engine *e, const std::vector<MemEv> &mev, bool complete) {
-    free_mem_index(e);
     if (!complete) return FI_OK;
     std::vector<std::pair<uint64_t, uint64_t>> ent;   // (word, event)
     const uint64_t kMaxEnt = 1ULL << 26;
@@ -1191,65 +1194,65 @@ static fi_status build_mem_index(fi_engine *e, const std::vector<MemEv> &mev, bo
         evs.push_back(ent[i].second);
     }
     off.push_back((uint32_t)ent.size());
-    HIPCHK(hipMalloc(&e->d_mw_addr, std::max<size_t>(addr.size(), 1) * 8));
-    HIPCHK(hipMalloc(&e->d_mw_off, off.size() * 4));
-    HIPCHK(hipMalloc(&e->d_mw_ev, std::max<size_t>(evs.size(), 1) * 8));
-    if (!addr.empty()) HIPCHK(hipMemcpy(e->d_mw_addr, addr.data(), addr.size() * 8, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_mw_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-    if (!evs.empty()) HIPCHK(hipMemcpy(e->d_mw_ev, evs.data(), evs.size() * 8, hipMemcpyHostToDevice));
-    e->mw_n = (uint32_t)addr.size();
-    e->mw_nev = evs.size();
-    e->mem_live = true;
+    DevBuf<uint64_t> d_addr, d_ev;   // (moved in once all three are up)
+    DevBuf<uint32_t> d_off;
+    HIPCHK(d_addr.alloc(std::max<size_t>(addr.size(), 1)));
+    HIPCHK(d_off.alloc(off.size()));
+    HIPCHK(d_ev.alloc(std::max<size_t>(evs.size(), 1)));
+    if (!addr.empty()) HIPCHK(hipMemcpy(d_addr, addr.data(), addr.size() * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_off, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+    if (!evs.empty()) HIPCHK(hipMemcpy(d_ev, evs.data(), evs.size() * 8, hipMemcpyHostToDevice));
+    e->gold.d_mw_addr = std::move(d_addr);
+    e->gold.d_mw_off = std::move(d_off);
+    e->gold.d_mw_ev = std::move(d_ev);
+    e->gold.mw_n = (uint32_t)addr.size();
+    e->gold.mw_nev = evs.size();
+    e->gold.mem_live = true;
     return FI_OK;
 }
 
 // The golden run under TimingSimpleCPU (fi_tick.cpp, fi_timing.cpp): its
 // attempts as requests, then their ticks.  t_status says why not, if not.
 static void tick_prepare(fi_engine *e, const std::vector<MemEv> &mev, bool mev_ok) {
-    e->t_ops.clear(); e->t_ticks.clear(); e->tk_done.clear(); e->tk_rec.clear(); e->t_stats = fi_timing_stats{};
-    if (e->cpu_model != FI_CPU_TIMING) { e->t_status = "the CPU model is AtomicSimpleCPU (fi_set_cpu_model)"; return; }
-    if (e->alloc_order.empty()) { e->t_status = "a checkpoint start: its frame order is not known"; return; }
-    if (e->clk_until) { e->t_status = "the golden run reads curTick: its output depends on the CPU model"; return; }
-    if (e->golden_unmapped) { e->t_status = "the golden run unmaps memory: freed frames are reused"; return; }
-    if (!mev_ok || e->g_trace.empty()) { e->t_status = "the golden access record is incomplete"; return; }
-    TickGoldenIn in{&e->g_trace, &e->g_pre, e->text_lo, &mev, &e->alloc_order, e->stack_min0, e->svma_lo,
-                    e->svma_hi, kStackBase, kMaxStack, e->golden.ninst, e->golden.ncycles};
+    if (e->cpu_model != FI_CPU_TIMING) { e->gold.t_status = "the CPU model is AtomicSimpleCPU (fi_set_cpu_model)"; return; }
+    if (e->img.alloc_order.empty()) { e->gold.t_status = "a checkpoint start: its frame order is not known"; return; }
+    if (e->gold.clk_until) { e->gold.t_status = "the golden run reads curTick: its output depends on the CPU model"; return; }
+    if (e->gold.golden_unmapped) { e->gold.t_status = "the golden run unmaps memory: freed frames are reused"; return; }
+    if (!mev_ok || e->gold.g_trace.empty()) { e->gold.t_status = "the golden access record is incomplete"; return; }
+    TickGoldenIn in{&e->gold.g_trace, &e->gold.g_pre, e->img.text_lo, &mev, &e->img.alloc_order, e->img.stack_min0, e->img.svma_lo,
+                    e->img.svma_hi, kStackBase, kMaxStack, e->gold.info.ninst, e->gold.info.ncycles};
     std::vector<TickAttempt> att;
-    std::string why = build_tick_attempts(in, e->t_ops, att);
+    std::string why = build_tick_attempts(in, e->gold.t_ops, att);
     if (why.empty()) {
-        e->t_ticks.resize(e->t_ops.size());
-        if (fi_timing_model_run(e->t_ops.data(), e->t_ops.size(), &e->tparams, e->t_ticks.data(), &e->t_stats))
+        e->gold.t_ticks.resize(e->gold.t_ops.size());
+        if (fi_timing_model_run(e->gold.t_ops.data(), e->gold.t_ops.size(), &e->tparams, e->gold.t_ticks.data(), &e->gold.t_stats))
             why = "the timing model rejected the golden requests (a state gem5 asserts on)";
     }
     if (!why.empty()) {
-        e->t_ops.clear(); e->t_ticks.clear();
-        e->t_status = why;
+        e->gold.t_ops.clear(); e->gold.t_ticks.clear();
+        e->gold.t_status = why;
         return;
     }
-    pack_tick_table(att, e->t_ticks, e->tk_done, e->tk_rec);
-    e->t_status = "";
+    pack_tick_table(att, e->gold.t_ticks, e->gold.tk_done, e->gold.tk_rec);
+    e->gold.t_status = "";
 }
 
 // ---- fi_golden_run's steps, in the order it takes them
 
-// Step 1: back to the process-start image only.
+// Step 1: no golden run, and the snapshot tables back to the image's own
+// frames (the golden run appends its snapshots to them).
 static fi_status golden_reset(fi_engine *e) {
-    e->t_status = "no golden run";
-    e->t_ops.clear(); e->t_ticks.clear(); e->tk_done.clear(); e->tk_rec.clear();
-    free_tick_table(e);   // (uploaded again from the new golden run's at the next device map)
-    e->snaps.resize(1);
-    e->tab.resize(e->n_start_frames);
-    e->pool.resize((uint64_t)e->n_start_frames * kPage);
-    e->snap_I = 1ULL << 62;
-    e->pre_ok = true;
-    e->have_golden = false;
-    return upload_snaps(e);
+    e->gold = Golden{};
+    e->img.snaps.resize(1);
+    e->img.tab.resize(e->img.n_start_frames);
+    e->img.pool.resize((uint64_t)e->img.n_start_frames * kPage);
+    return upload_snaps(e, e->img);
 }
 
 constexpr uint64_t kGoldenRecCap = 1 << 24;   // bytes of stdout / stderr the golden launches record
 
 // Step 2, pass 1: the golden run itself (output, instruction count,
-// footprint) into e->golden and the golden streams.  rec_out / rec_err stay
+// footprint) into e->gold.info and the golden streams.  rec_out / rec_err stay
 // allocated for pass 2.
 static fi_status golden_pass1(fi_engine *e, DevBuf<uint8_t> &rec_out, DevBuf<uint8_t> &rec_err, fi_outcome &o,
                               uint64_t &gpages) {
@@ -1257,35 +1260,34 @@ static fi_status golden_pass1(fi_engine *e, DevBuf<uint8_t> &rec_out, DevBuf<uin
     HIPCHK(rec_out.alloc(kGoldenRecCap));
     HIPCHK(rec_err.alloc(kGoldenRecCap));
     unsigned long long stats[kNStats];
-    fi_status st = golden_launch(e, kGoldenPages, 0, 0, nullptr, nullptr, nullptr, nullptr, 0, rec_out.get(),
-                                 rec_err.get(), kGoldenRecCap, o, stats);
+    GoldenRec rec;
+    rec.out = rec_out; rec.err = rec_err; rec.cap = kGoldenRecCap;
+    fi_status st = golden_launch(e, kGoldenPages, rec, o, stats);
     if (st) return st;
     const uint64_t ol = stats[ST_GOLDEN_OUT_LEN], el = stats[ST_GOLDEN_ERR_LEN];
     gpages = stats[ST_PAGES];
     if (ol > kGoldenRecCap || el > kGoldenRecCap)
         return fail(e, FI_E_GOLDEN, "golden output exceeds %llu bytes", (unsigned long long)kGoldenRecCap);
     if (gpages >= kGoldenPages) return fail(e, FI_E_GOLDEN, "golden run writes more than %u pages", kGoldenPages);
-    e->gout.assign(ol, 0);
-    e->gerr.assign(el, 0);
-    if (ol) HIPCHK(hipMemcpy(e->gout.data(), rec_out.get(), ol, hipMemcpyDeviceToHost));
-    if (el) HIPCHK(hipMemcpy(e->gerr.data(), rec_err.get(), el, hipMemcpyDeviceToHost));
-    dfree(e->d_gout); dfree(e->d_gerr);
-    HIPCHK(hipMalloc(&e->d_gout, std::max<uint64_t>(ol, 1)));
-    HIPCHK(hipMalloc(&e->d_gerr, std::max<uint64_t>(el, 1)));
-    if (ol) HIPCHK(hipMemcpy(e->d_gout, e->gout.data(), ol, hipMemcpyHostToDevice));
-    if (el) HIPCHK(hipMemcpy(e->d_gerr, e->gerr.data(), el, hipMemcpyHostToDevice));
-    e->golden = fi_golden_info{};
-    e->golden.ninst = o.ninst;
-    e->golden.ncycles = stats[ST_GOLDEN_NCYCLES];
-    e->golden.exit_code = o.exit_code;
-    e->golden.stdout_len = ol;
-    e->golden.stderr_len = el;
-    e->golden.fetch_bytes = stats[ST_FETCH_BYTES];
-    e->golden.data_bytes = stats[ST_DATA_BYTES];
-    e->gdetail = o.detail;
-    e->gsub = o.sub;
-    e->golden_fp = stats[ST_GOLDEN_EXTRA_STATE] != 0;
-    e->clk_until = stats[ST_CLK_UNTIL];
+    e->gold.gout.assign(ol, 0);
+    e->gold.gerr.assign(el, 0);
+    if (ol) HIPCHK(hipMemcpy(e->gold.gout.data(), rec_out.get(), ol, hipMemcpyDeviceToHost));
+    if (el) HIPCHK(hipMemcpy(e->gold.gerr.data(), rec_err.get(), el, hipMemcpyDeviceToHost));
+    HIPCHK(e->gold.d_gout.alloc(std::max<uint64_t>(ol, 1)));
+    HIPCHK(e->gold.d_gerr.alloc(std::max<uint64_t>(el, 1)));
+    if (ol) HIPCHK(hipMemcpy(e->gold.d_gout, e->gold.gout.data(), ol, hipMemcpyHostToDevice));
+    if (el) HIPCHK(hipMemcpy(e->gold.d_gerr, e->gold.gerr.data(), el, hipMemcpyHostToDevice));
+    e->gold.info.ninst = o.ninst;
+    e->gold.info.ncycles = stats[ST_GOLDEN_NCYCLES];
+    e->gold.info.exit_code = o.exit_code;
+    e->gold.info.stdout_len = ol;
+    e->gold.info.stderr_len = el;
+    e->gold.info.fetch_bytes = stats[ST_FETCH_BYTES];
+    e->gold.info.data_bytes = stats[ST_DATA_BYTES];
+    e->gold.gdetail = o.detail;
+    e->gold.gsub = o.sub;
+    e->gold.golden_fp = stats[ST_GOLDEN_EXTRA_STATE] != 0;
+    e->gold.clk_until = stats[ST_CLK_UNTIL];
     return FI_OK;
 }
 
@@ -1331,8 +1333,12 @@ static fi_status golden_pass2(fi_engine *e, const fi_outcome &o, uint64_t gpages
     DevBuf<MemEv> d_mem;
     HIPCHK(d_mem.alloc(mem_cap));
     unsigned long long stats[kNStats] = {};
-    fi_status st = golden_launch(e, P, I, rec_max, d_rs.get(), d_rp.get(), d_rv.get(), d_trace.get(), trace_cap,
-                                 rec_out.get(), rec_err.get(), kGoldenRecCap, g.o, stats, d_mem.get(), mem_cap);
+    GoldenRec rec;
+    rec.out = rec_out; rec.err = rec_err; rec.cap = kGoldenRecCap;
+    rec.interval = I; rec.max_snaps = rec_max; rec.snaps = d_rs; rec.pages = d_rp; rec.vpns = d_rv;
+    rec.trace = d_trace; rec.trace_cap = trace_cap;
+    rec.mem = d_mem; rec.mem_cap = mem_cap;
+    fi_status st = golden_launch(e, P, rec, g.o, stats);
     rec_out.reset();
     rec_err.reset();
     g.I = I;
@@ -1342,10 +1348,10 @@ static fi_status golden_pass2(fi_engine *e, const fi_outcome &o, uint64_t gpages
     g.unmapped = stats[ST_GOLDEN_UNMAPPED] != 0;
     if (!st && g.n_events <= trace_cap) {
         g.trace.resize(g.n_events);
-        g.pre.resize((e->text_hi - e->text_lo) / 2);
+        g.pre.resize((e->img.text_hi - e->img.text_lo) / 2);
         hipError_t err = hipMemcpy(g.trace.data(), d_trace.get(), g.n_events * 4, hipMemcpyDeviceToHost);
         if (err == hipSuccess)
-            err = hipMemcpy(g.pre.data(), e->d_pre, g.pre.size() * sizeof(PreInst), hipMemcpyDeviceToHost);
+            err = hipMemcpy(g.pre.data(), e->img.d_pre, g.pre.size() * sizeof(PreInst), hipMemcpyDeviceToHost);
         for (auto &p : g.pre) p.flags &= (uint8_t)~(kPreLeader | kPreOddLeader);
         if (err != hipSuccess) st = fail(e, FI_E_HIP, "trace download: %s", hipGetErrorString(err));
     }
@@ -1372,25 +1378,24 @@ static fi_status golden_pass2(fi_engine *e, const fi_outcome &o, uint64_t gpages
     return st;   // (the snapshot capture buffers go here: before upload_snaps)
 }
 
-// Step 4: deduplicate the captured frames into e->pool and build one sorted
+// Step 4: deduplicate the captured frames into e->img.pool and build one sorted
 // page table per snapshot (fi_golden_host.h).
 static void golden_snap_tables(fi_engine *e, const GoldenCapture &g) {
     std::vector<SnapState> snaps;
     std::vector<PageEnt> tab;
-    e->pre_ok = dedupe_snapshot_pages(e->tab.data(), e->n_start_frames, e->pool, e->pages, e->code_lo, e->code_hi,
+    e->gold.pre_ok = dedupe_snapshot_pages(e->img.tab.data(), e->img.n_start_frames, e->img.pool, e->img.pages, e->img.code_lo, e->img.code_hi,
                                       g.snaps, g.pages, g.vpns, g.P, snaps, tab);
-    e->snaps = std::move(snaps);
-    e->tab = std::move(tab);
-    e->snap_I = g.I;
+    e->img.snaps = std::move(snaps);
+    e->img.tab = std::move(tab);
+    e->gold.snap_I = g.I;
 }
 
 // Step 5: register liveness at each snapshot (fi_golden_host.h); keeps the
 // trace and the text it indexes when it is usable.  Returns live_ok.
 static bool golden_liveness(fi_engine *e, const GoldenCapture &g, std::vector<uint32_t> &rmask,
                             std::vector<uint32_t> &wmask) {
-    const bool live_ok = trace_liveness(g.pre, g.trace, g.n_events, OP_m5op, rmask, wmask, e->snaps);
-    e->g_pre.clear(); e->g_trace.clear();
-    if (live_ok && !g.trace.empty()) { e->g_pre = g.pre; e->g_trace = g.trace; }
+    const bool live_ok = trace_liveness(g.pre, g.trace, g.n_events, OP_m5op, rmask, wmask, e->img.snaps);
+    if (live_ok && !g.trace.empty()) { e->gold.g_pre = g.pre; e->gold.g_trace = g.trace; }
     return live_ok;
 }
 
@@ -1400,27 +1405,25 @@ static bool golden_liveness(fi_engine *e, const GoldenCapture &g, std::vector<ui
 // the same machine; written first (or never touched again) it is dead.
 static fi_status golden_first_access(fi_engine *e, const GoldenCapture &g, bool live_ok,
                                      const std::vector<uint32_t> &rmask, const std::vector<uint32_t> &wmask) {
-    free_fw(e);
-    if (!live_ok || g.trace.empty() || e->golden.ninst >= (1ULL << 29)) return FI_OK;
+    if (!live_ok || g.trace.empty() || e->gold.info.ninst >= (1ULL << 29)) return FI_OK;
     std::vector<uint32_t> off, ev;
     first_access_index(g.trace, rmask, wmask, off, ev);
-    HIPCHK(hipMalloc(&e->d_fw_off, 33 * 4));
-    HIPCHK(hipMalloc(&e->d_fw_ev, std::max<size_t>(ev.size(), 1) * 4));
-    HIPCHK(hipMemcpy(e->d_fw_off, off.data(), 33 * 4, hipMemcpyHostToDevice));
-    if (!ev.empty()) HIPCHK(hipMemcpy(e->d_fw_ev, ev.data(), ev.size() * 4, hipMemcpyHostToDevice));
-    e->fw_off = std::move(off);
-    e->fw_ev = std::move(ev);
-    e->fw_ok = true;
+    HIPCHK(e->gold.d_fw_off.alloc(33));
+    HIPCHK(e->gold.d_fw_ev.alloc(std::max<size_t>(ev.size(), 1)));
+    HIPCHK(hipMemcpy(e->gold.d_fw_off, off.data(), 33 * 4, hipMemcpyHostToDevice));
+    if (!ev.empty()) HIPCHK(hipMemcpy(e->gold.d_fw_ev, ev.data(), ev.size() * 4, hipMemcpyHostToDevice));
+    e->gold.fw_off = std::move(off);
+    e->gold.fw_ev = std::move(ev);
+    e->gold.fw_ok = true;
     return FI_OK;
 }
 
 // Step 7: translate the golden basic blocks and build the trial kernel with
 // them (hipRTC); the static kernel stays the fallback.  Takes g.pre.
 static fi_status golden_translate(fi_engine *e, GoldenCapture &g, bool live_ok) {
-    free_tx(e);
-    if (e->cfg.flags & FI_CFG_NO_TRANSLATE) e->tx_status = "disabled (FI_CFG_NO_TRANSLATE)";
-    else if (!e->pre_ok) e->tx_status = "golden run rewrites its text";
-    else if (!live_ok || g.trace.empty()) e->tx_status = "golden trace unavailable";
+    if (e->cfg.flags & FI_CFG_NO_TRANSLATE) e->gold.tx_status = "disabled (FI_CFG_NO_TRANSLATE)";
+    else if (!e->gold.pre_ok) e->gold.tx_status = "golden run rewrites its text";
+    else if (!live_ok || g.trace.empty()) e->gold.tx_status = "golden trace unavailable";
     else {
         // (snapshot pcs are not leaders: they fall all over the hot loops and
         // would cut the blocks into single instructions; a wave that starts
@@ -1430,27 +1433,27 @@ static fi_status golden_translate(fi_engine *e, GoldenCapture &g, bool live_ok) 
         std::vector<LoopEst> loops;
         uint32_t n_tx = 0;
         const bool ahead = !(e->cfg.flags & FI_CFG_NO_LOAD_AHEAD);   // (part of the text, which keys the code-object caches)
-        std::string body = translate_blocks(g.pre, e->text_lo, g.trace, pcs, leaders, n_tx, true, &loops, ahead);
+        std::string body = translate_blocks(g.pre, e->img.text_lo, g.trace, pcs, leaders, n_tx, true, &loops, ahead);
         if (n_tx > 24000) {   // the odd-pc streams make it too large: without them
             leaders.clear();
             loops.clear();
-            body = translate_blocks(g.pre, e->text_lo, g.trace, pcs, leaders, n_tx, false, &loops, ahead);
+            body = translate_blocks(g.pre, e->img.text_lo, g.trace, pcs, leaders, n_tx, false, &loops, ahead);
         }
         if (!loops.empty() && !(e->cfg.flags & FI_CFG_NO_LOOP_ORDER)) {
-            HIPCHK(hipMalloc(&e->d_loops, loops.size() * sizeof(LoopEst)));
-            HIPCHK(hipMemcpy(e->d_loops, loops.data(), loops.size() * sizeof(LoopEst), hipMemcpyHostToDevice));
-            e->n_loops = (uint32_t)loops.size();
+            HIPCHK(e->gold.d_loops.alloc(loops.size()));
+            HIPCHK(hipMemcpy(e->gold.d_loops, loops.data(), loops.size() * sizeof(LoopEst), hipMemcpyHostToDevice));
+            e->gold.n_loops = (uint32_t)loops.size();
         }
-        e->tx_body = body;
+        e->gold.tx_body = body;
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, e->dev));
         if (const char *dump = getenv("SHREWD_FI_DUMP_TX")) {   // diagnostics: the generated blocks
             if (FILE *f = fopen(dump, "w")) { fputs(body.c_str(), f); fclose(f); }
         }
         if (leaders.empty()) {   // nothing hot: the static kernels (pre-decoded + general interpreter) run everything
-            e->tx_status = "nothing to translate (no code run twice)";
+            e->gold.tx_status = "nothing to translate (no code run twice)";
         } else if (n_tx > 24000) {   // more than the load-time compiler handles in reasonable time
-            e->tx_status = "translation too large";
+            e->gold.tx_status = "translation too large";
         } else {
             auto j = std::make_shared<JitJob>();
             j->body = body;
@@ -1458,11 +1461,11 @@ static fi_status golden_translate(fi_engine *e, GoldenCapture &g, bool live_ok) 
             j->odd = jit_has_odd(body);
             j->use_cache = !(e->cfg.flags & FI_CFG_JIT_NO_CACHE);
             for (uint32_t h : leaders) g.pre[h & 0x7FFFFFFFu].flags |= (h >> 31) ? kPreOddLeader : kPreLeader;
-            e->jit_pre = std::move(g.pre);
-            e->jit_blocks = leaders.size();
-            e->jit_insts = n_tx;
-            e->jit = j;
-            e->tx_status = "compiling";
+            e->gold.jit_pre = std::move(g.pre);
+            e->gold.jit_blocks = leaders.size();
+            e->gold.jit_insts = n_tx;
+            e->gold.jit = j;
+            e->gold.tx_status = "compiling";
             e->jit_threads.emplace_back(std::thread(jit_job_run, j), j);
         }
     }
@@ -1471,7 +1474,7 @@ static fi_status golden_translate(fi_engine *e, GoldenCapture &g, bool live_ok) 
 
 fi_status fi_golden_run(fi_engine *e, fi_golden_info *out) {
     if (!e) return FI_E_ARG;
-    if (!e->loaded) return fail(e, FI_E_STATE, "fi_golden_run: no workload loaded");
+    if (!e->img.loaded) return fail(e, FI_E_STATE, "fi_golden_run: no workload loaded");
     HIPCHK(hipSetDevice(e->dev));
     fi_status st = ensure_work(e, 64);
     if (st) return st;
@@ -1498,39 +1501,39 @@ fi_status fi_golden_run(fi_engine *e, fi_golden_info *out) {
     const bool live_ok = golden_liveness(e, g, rmask, wmask);
     st = golden_first_access(e, g, live_ok, rmask, wmask);
     if (st) return st;
-    st = upload_snaps(e);
+    st = upload_snaps(e, e->img);
     if (st) return st;
     st = build_mem_index(e, g.mev, live_ok && g.mem_ok);
     if (st) return st;
-    e->golden_unmapped = g.unmapped;
+    e->gold.golden_unmapped = g.unmapped;
     tick_prepare(e, g.mev, !g.trace.empty() && g.mem_ok);
     st = golden_translate(e, g, live_ok);
     if (st) return st;
 
     e->last_ms = golden_ms;
-    e->golden.snapshots = e->snaps.size();
-    e->golden.snapshot_interval = g.I;
-    e->golden.snapshot_frames = e->pool.size() / kPage;
-    e->have_golden = true;
+    e->gold.info.snapshots = e->img.snaps.size();
+    e->gold.info.snapshot_interval = g.I;
+    e->gold.info.snapshot_frames = e->img.pool.size() / kPage;
+    e->gold.have_golden = true;
     if (e->issue_on) {   // the model follows the new golden run
         st = compute_shadow(e);
         if (st) return st;
     }
-    if (out) *out = e->golden;
+    if (out) *out = e->gold.info;
     return FI_OK;
 }
 
 fi_status fi_golden_stdout(fi_engine *e, uint8_t *buf, uint64_t cap, uint64_t *len) {
-    if (!e || !e->have_golden) return fail(e, FI_E_STATE, "no golden run");
-    if (buf && cap) memcpy(buf, e->gout.data(), std::min<uint64_t>(cap, e->gout.size()));
-    if (len) *len = e->gout.size();
+    if (!e || !e->gold.have_golden) return fail(e, FI_E_STATE, "no golden run");
+    if (buf && cap) memcpy(buf, e->gold.gout.data(), std::min<uint64_t>(cap, e->gold.gout.size()));
+    if (len) *len = e->gold.gout.size();
     return FI_OK;
 }
 
 fi_status fi_golden_stderr(fi_engine *e, uint8_t *buf, uint64_t cap, uint64_t *len) {
-    if (!e || !e->have_golden) return fail(e, FI_E_STATE, "no golden run");
-    if (buf && cap) memcpy(buf, e->gerr.data(), std::min<uint64_t>(cap, e->gerr.size()));
-    if (len) *len = e->gerr.size();
+    if (!e || !e->gold.have_golden) return fail(e, FI_E_STATE, "no golden run");
+    if (buf && cap) memcpy(buf, e->gold.gerr.data(), std::min<uint64_t>(cap, e->gold.gerr.size()));
+    if (len) *len = e->gold.gerr.size();
     return FI_OK;
 }
 
@@ -1547,13 +1550,13 @@ fi_status fi_set_campaign(fi_engine *e, uint64_t seed, uint64_t structures, uint
 
 fi_status fi_set_exe_path(fi_engine *e, const char *path) {
     if (!e) return FI_E_ARG;
-    if (e->have_golden) return fail(e, FI_E_STATE, "fi_set_exe_path: set before fi_golden_run (the golden run sees it)");
+    if (e->gold.have_golden) return fail(e, FI_E_STATE, "fi_set_exe_path: set before fi_golden_run (the golden run sees it)");
     HIPCHK(hipSetDevice(e->dev));
     e->exe_path = path ? path : "";
     if (e->exe_path.size() >= 4096) { e->exe_path.clear(); return FI_E_ARG; }   // PATH_MAX
-    dfree(e->d_exe);
+    e->d_exe.reset();
     if (!e->exe_path.empty()) {
-        HIPCHK(hipMalloc(&e->d_exe, e->exe_path.size()));
+        HIPCHK(e->d_exe.alloc(e->exe_path.size()));
         HIPCHK(hipMemcpy(e->d_exe, e->exe_path.data(), e->exe_path.size(), hipMemcpyHostToDevice));
     }
     return FI_OK;
@@ -1561,22 +1564,22 @@ fi_status fi_set_exe_path(fi_engine *e, const char *path) {
 
 fi_status fi_set_stdin(fi_engine *e, const uint8_t *data, uint64_t len) {
     if (!e) return FI_E_ARG;
-    if (e->have_golden) return fail(e, FI_E_STATE, "fi_set_stdin: set before fi_golden_run (the golden run reads it)");
+    if (e->gold.have_golden) return fail(e, FI_E_STATE, "fi_set_stdin: set before fi_golden_run (the golden run reads it)");
     if (data && len >= (1ULL << 40)) return fail(e, FI_E_ARG, "fi_set_stdin: input larger than 1 TiB");
     HIPCHK(hipSetDevice(e->dev));
-    dfree(e->d_stdin);
+    e->d_stdin.reset();
     e->stdin_data.clear();
     e->stdin_on = data != nullptr;
     if (!data) return FI_OK;
     e->stdin_data.assign(data, data + len);
-    HIPCHK(hipMalloc(&e->d_stdin, std::max<uint64_t>(len, 1)));
+    HIPCHK(e->d_stdin.alloc(std::max<uint64_t>(len, 1)));
     if (len) HIPCHK(hipMemcpy(e->d_stdin, data, len, hipMemcpyHostToDevice));
     return FI_OK;
 }
 
 fi_status fi_set_clock(fi_engine *e, uint64_t period_ticks, uint64_t random_seed) {
     if (!e || !period_ticks) return FI_E_ARG;
-    if (e->have_golden) return fail(e, FI_E_STATE, "fi_set_clock: set before fi_golden_run (the golden run sees it)");
+    if (e->gold.have_golden) return fail(e, FI_E_STATE, "fi_set_clock: set before fi_golden_run (the golden run sees it)");
     HIPCHK(hipSetDevice(e->dev));
     e->clk_period = period_ticks;
     e->rnd_seed = random_seed;
@@ -1610,7 +1613,7 @@ fi_status fi_set_issue_model(fi_engine *e, const fi_issue_params *p) {
         e->issue_on = false;
         return FI_OK;
     }
-    if (!e->have_golden) return fail(e, FI_E_STATE, "fi_set_issue_model: no golden run");
+    if (!e->gold.have_golden) return fail(e, FI_E_STATE, "fi_set_issue_model: no golden run");
     const fi_issue_params keep = e->issue_p;
     e->issue_p = *p;
     const fi_status st = compute_shadow(e);
@@ -1622,39 +1625,39 @@ fi_status fi_set_issue_model(fi_engine *e, const fi_issue_params *p) {
 fi_status fi_shadow_map(fi_engine *e, uint8_t *shadow, uint64_t cap, uint64_t *n, fi_issue_stats *stats) {
     if (!e) return FI_E_ARG;
     if (!e->issue_on) return fail(e, FI_E_STATE, "fi_shadow_map: the issue model is off");
-    if (shadow && cap) memcpy(shadow, e->shadow.data(), std::min<uint64_t>(cap, e->shadow.size()));
-    if (n) *n = e->shadow.size();
-    if (stats) *stats = e->issue_stats;
+    if (shadow && cap) memcpy(shadow, e->gold.shadow.data(), std::min<uint64_t>(cap, e->gold.shadow.size()));
+    if (n) *n = e->gold.shadow.size();
+    if (stats) *stats = e->gold.issue_stats;
     return FI_OK;
 }
 
 // The campaign's draw from trial `first` on (fi_site_draw.h); memory words only where there are some
 static DrawCtx campaign_draw(fi_engine *e, uint64_t first) {
-    const uint64_t structures = e->mem_pages.empty() ? e->structures & ~(1ULL << FI_T_MEM) : e->structures;
+    const uint64_t structures = e->img.mem_pages.empty() ? e->structures & ~(1ULL << FI_T_MEM) : e->structures;
     return draw_ctx(e->seed, structures, first, e->bits, e->burst);
 }
 
 static SampleCtx sample_ctx(fi_engine *e, uint64_t first) {
     SampleCtx s{};
     s.d = campaign_draw(e, first);
-    s.golden_ninst = e->golden.ninst;
-    s.mem_pages = e->d_mem_pages;
-    s.n_mem_pages = e->mem_pages.size();
+    s.golden_ninst = e->gold.info.ninst;
+    s.mem_pages = e->img.d_mem_pages;
+    s.n_mem_pages = e->img.mem_pages.size();
     return s;
 }
 
 fi_status fi_sample_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site *out) {
     if (!e || !out) return FI_E_ARG;
-    if (!e->have_golden) return fail(e, FI_E_STATE, "golden run required before sampling");
+    if (!e->gold.have_golden) return fail(e, FI_E_STATE, "golden run required before sampling");
     if (!e->structures) return fail(e, FI_E_STATE, "fi_set_campaign first");
     HIPCHK(hipSetDevice(e->dev));
     const uint64_t chunk = e->cfg.max_trials_per_launch;
     fi_status st = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), chunk));
     if (st) return st;
     for (uint64_t done = 0; done < n;) {
-        const uint64_t k = std::min<uint64_t>(n - done, e->cap);
-        HIPCHK(launch_sample(sample_ctx(e, first + done), k, e->d_sites, e->d_keys, e->d_perm, e->stream));
-        HIPCHK(hipMemcpyAsync(out + done, e->d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        const uint64_t k = std::min<uint64_t>(n - done, e->w.cap);
+        HIPCHK(launch_sample(sample_ctx(e, first + done), k, e->w.d_sites, e->w.d_keys, e->w.d_perm, e->stream));
+        HIPCHK(hipMemcpyAsync(out + done, e->w.d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
         done += k;
     }
@@ -1667,12 +1670,12 @@ fi_status fi_sample_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site *out
 static hipError_t launch_trial_kernel(fi_engine *e, DevCtx &c, hipStream_t st, bool solo) {
     void *args[] = {&c};
     if (solo) {
-        if (!e->tx_fn_solo) return launch_trials_solo(c, st);
-        return hipModuleLaunchKernel(e->tx_fn_solo, (unsigned)c.n, 1, 1, kSoloLanes, 1, 1, 0, st, args, nullptr);
+        if (!e->gold.tx.fn_solo) return launch_trials_solo(c, st);
+        return hipModuleLaunchKernel(e->gold.tx.fn_solo, (unsigned)c.n, 1, 1, kSoloLanes, 1, 1, 0, st, args, nullptr);
     }
-    if (!e->tx_fn) return launch_trials(c, st);
+    if (!e->gold.tx.fn) return launch_trials(c, st);
     const uint32_t gl = (c.resume && c.resume_waves) ? 1u : c.lanes;   // grid for the fewest lanes per wave
-    return hipModuleLaunchKernel(e->tx_fn, (unsigned)((c.n + gl - 1) / gl), 1, 1, 64, 1, 1, 0, st, args,
+    return hipModuleLaunchKernel(e->gold.tx.fn, (unsigned)((c.n + gl - 1) / gl), 1, 1, 64, 1, 1, 0, st, args,
                                  nullptr);
 }
 
@@ -1702,48 +1705,48 @@ static std::pair<hipEvent_t, hipEvent_t> &timer_slot(fi_engine *e, uint32_t kind
 // pair of capture buffers, trial i of sites to row cidx[i] (NULL: row i).
 static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *d_out, uint32_t P, hipStream_t st,
                           bool tick, const uint8_t *disp = nullptr, int cslot = -1, const uint32_t *cidx = nullptr) {
-    int end_bit = 64 - __builtin_clzll(std::max<uint64_t>(e->golden.ninst, 1));
+    int end_bit = 64 - __builtin_clzll(std::max<uint64_t>(e->gold.info.ninst, 1));
     // (a dead site ends at injection: an early exit, so not with FI_CFG_NO_EARLY_EXIT)
-    const bool fwd = e->fw_ok && !(e->cfg.flags & (FI_CFG_NO_FORWARD | FI_CFG_NO_EARLY_EXIT));
+    const bool fwd = e->gold.fw_ok && !(e->cfg.flags & (FI_CFG_NO_FORWARD | FI_CFG_NO_EARLY_EXIT));
     if (fwd) {
         FwdCtx fc{};
-        fc.reg_off = e->d_fw_off; fc.reg_ev = e->d_fw_ev;
+        fc.reg_off = e->gold.d_fw_off; fc.reg_ev = e->gold.d_fw_ev;
         // memory sites only when the golden run's mappings are static (no VM
         // syscalls: golden_fp covers them) and its access index is complete
-        const bool memf = e->mem_live && !e->golden_fp && e->snaps.size() > 1;
-        fc.mw_n = memf ? e->mw_n : 0;
-        fc.mw_addr = e->d_mw_addr; fc.mw_off = e->d_mw_off; fc.mw_ev = e->d_mw_ev;
-        fc.snaps = e->d_snaps; fc.snap_tab = e->d_tab; fc.n_snap = (uint32_t)e->snaps.size();
-        fc.snap_interval = e->snap_I; fc.text_lo = e->text_lo; fc.text_hi = e->text_hi;
-        HIPCHK(launch_forward(sites, k, fc, e->d_keys, e->d_eff, st));
+        const bool memf = e->gold.mem_live && !e->gold.golden_fp && e->img.snaps.size() > 1;
+        fc.mw_n = memf ? e->gold.mw_n : 0;
+        fc.mw_addr = e->gold.d_mw_addr; fc.mw_off = e->gold.d_mw_off; fc.mw_ev = e->gold.d_mw_ev;
+        fc.snaps = e->img.d_snaps; fc.snap_tab = e->img.d_tab; fc.n_snap = (uint32_t)e->img.snaps.size();
+        fc.snap_interval = e->gold.snap_I; fc.text_lo = e->img.text_lo; fc.text_hi = e->img.text_hi;
+        HIPCHK(launch_forward(sites, k, fc, e->w.d_keys, e->w.d_eff, st));
     }
     // (without forwarding the parked trials still need eff: the identity for the rest)
-    if (disp) HIPCHK(launch_tick_park(sites, disp, k, fwd ? 0u : 1u, e->d_keys, e->d_eff, st));
-    HIPCHK(sort_pairs(e->d_tmp, e->tmp_bytes, e->d_keys, e->d_keys2, e->d_perm, e->d_perm2, k, end_bit, st));
+    if (disp) HIPCHK(launch_tick_park(sites, disp, k, fwd ? 0u : 1u, e->w.d_keys, e->w.d_eff, st));
+    HIPCHK(sort_pairs(e->w.d_tmp, e->w.tmp_bytes, e->w.d_keys, e->w.d_keys2, e->w.d_perm, e->w.d_perm2, k, end_bit, st));
     DevCtx c = base_ctx(e);
     c.sites = sites;
-    c.perm = e->d_perm2;
-    c.eff = (fwd || disp) ? e->d_eff : nullptr;
+    c.perm = e->w.d_perm2;
+    c.eff = (fwd || disp) ? e->w.d_eff : nullptr;
     c.out = d_out;
     c.n = k;
     c.n_slots = (uint32_t)k;
-    c.save = e->d_save;
+    c.save = e->w.d_save;
     c.priv_pages = P;
     c.clk_esc = tick ? 1u : 0u;
     if (cslot >= 0) {
-        c.cap_out = e->cx.d_out[cslot]; c.cap_err = e->cx.d_err[cslot]; c.cap_len = e->cx.d_len[cslot];
+        c.cap_out = e->w.cx.d_out[cslot]; c.cap_err = e->w.cx.d_err[cslot]; c.cap_len = e->w.cx.d_len[cslot];
         c.cap_idx = cidx;
-        c.cap_bytes = e->cx.bytes; c.cap_stride = e->cx.stride;
+        c.cap_bytes = e->w.cx.bytes; c.cap_stride = e->w.cx.stride;
     }
     if (P != e->cfg.private_pages) c.ov_blocks = 0;   // the second pass has its own P' (chunk_end)
-    if (c.ov_blocks) HIPCHK(hipMemsetAsync(e->d_ov_next, 0, 4, st));
-    HIPCHK(hipMemsetAsync(e->d_cnt, 0, 16 * 4, st));
-    HIPCHK(hipMemsetAsync(e->d_wave_dbg, 0, k * kWaveDbgWords * sizeof(uint64_t), st));
+    if (c.ov_blocks) HIPCHK(hipMemsetAsync(e->w.d_ov_next, 0, 4, st));
+    HIPCHK(hipMemsetAsync(e->w.d_cnt, 0, 16 * 4, st));
+    HIPCHK(hipMemsetAsync(e->w.d_wave_dbg, 0, k * kWaveDbgWords * sizeof(uint64_t), st));
     const bool pack = (e->cfg.flags & FI_CFG_PACK_RUNS) != 0;
     int n_cu = 0;
     HIPCHK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, e->dev));
     const uint32_t spread = (e->cfg.flags & FI_CFG_FIXED_RESUME) ? 0u : (uint32_t)std::max(1, n_cu) * 4u;   // SIMDs
-    if (pack) HIPCHK(hipMemsetAsync(e->d_nwaves, 0, 16 * 4, st));
+    if (pack) HIPCHK(hipMemsetAsync(e->w.d_nwaves, 0, 16 * 4, st));
     // epochs: each wave runs a bounded number of loop
     // iterations, then its live lanes are suspended, sorted by pc and resumed
     // densely packed; the last epoch runs to completion.  All asynchronous:
@@ -1767,14 +1770,14 @@ static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *
     // (at most kOddGrid of them; the rest stay with the solo kernel), on its
     // own stream beside the solo kernel
     constexpr uint32_t kOddGrid = 2048;
-    const bool odd_on = e->tx_fn_odd && e->tx_fn_solo && !(e->cfg.flags & FI_CFG_NO_ODD_KERNEL);
-    if (odd_on) HIPCHK(hipMemsetAsync(e->d_split, 0, 64 * 4, st));
+    const bool odd_on = e->gold.tx.fn_odd && e->gold.tx.fn_solo && !(e->cfg.flags & FI_CFG_NO_ODD_KERNEL);
+    if (odd_on) HIPCHK(hipMemsetAsync(e->w.d_split, 0, 64 * 4, st));
     for (size_t ep = 0; ep < budgets.size(); ep++) {
         const bool solo = (e->cfg.flags & FI_CFG_SOLO_ALL) || (ep > 0 && !(e->cfg.flags & FI_CFG_NO_SOLO));
         const bool odd = odd_on && solo && ep > 0 && ep < 16;
         c.wave_budget = budgets[ep];
-        c.surv = e->d_surv[ep & 1];
-        c.surv_n = e->d_cnt + ep;
+        c.surv = e->w.d_surv[ep & 1];
+        c.surv_n = e->w.d_cnt + ep;
         c.lanes = ep == 0 ? e->cfg.lanes_per_wave : e->cfg.resume_lanes;
         c.wrange = nullptr;
         c.n_waves = nullptr;
@@ -1790,36 +1793,36 @@ static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *
             // solo keys: tier above numInst, which stays below the hang cap -- a
             // key of nb + 2 bits (+ 1 for the odd-pc flag) sorts in fewer passes
             const uint32_t nb = 64u - (uint32_t)__builtin_clzll(std::max<uint64_t>(c.hang_cap, 1));
-            HIPCHK(launch_surv_keys(e->d_save, e->d_surv[(ep - 1) & 1], e->d_cnt + ep - 1, k, c.text_lo, e->d_skeys,
-                                    e->d_svals, odd ? e->d_split + 4 * ep : nullptr, skey, e->golden.ninst, nb,
-                                    e->d_loops, e->n_loops, c.hang_cap, st));
-            HIPCHK(sort_pairs(e->d_tmp, e->tmp_bytes, e->d_skeys, e->d_skeys2, e->d_svals, e->d_svals2, k,
+            HIPCHK(launch_surv_keys(e->w.d_save, e->w.d_surv[(ep - 1) & 1], e->w.d_cnt + ep - 1, k, c.text_lo, e->w.d_skeys,
+                                    e->w.d_svals, odd ? e->w.d_split + 4 * ep : nullptr, skey, e->gold.info.ninst, nb,
+                                    e->gold.d_loops, e->gold.n_loops, c.hang_cap, st));
+            HIPCHK(sort_pairs(e->w.d_tmp, e->w.tmp_bytes, e->w.d_skeys, e->w.d_skeys2, e->w.d_svals, e->w.d_svals2, k,
                               skey ? (int)std::min(64u, nb + 3u) : 64, st));
-            c.resume = e->d_svals2;
-            c.resume_n = e->d_cnt + ep - 1;
+            c.resume = e->w.d_svals2;
+            c.resume_n = e->w.d_cnt + ep - 1;
             if (odd) {   // odd survivors sort last: the solo kernel takes [0, split), the solo-odd kernel the rest
                 const uint32_t grid = (uint32_t)std::min<uint64_t>(k, kOddGrid);
-                HIPCHK(launch_odd_split(c.resume_n, e->d_split + 4 * ep, e->d_split + 4 * ep + 1, grid, st));
+                HIPCHK(launch_odd_split(c.resume_n, e->w.d_split + 4 * ep, e->w.d_split + 4 * ep + 1, grid, st));
                 DevCtx co = c;
                 co.lanes = 1; co.resume_waves = 0; co.wrange = nullptr; co.n_waves = nullptr;
-                co.resume_lo = e->d_split + 4 * ep + 1;
-                c.resume_n = e->d_split + 4 * ep + 1;
+                co.resume_lo = e->w.d_split + 4 * ep + 1;
+                c.resume_n = e->w.d_split + 4 * ep + 1;
                 HIPCHK(hipEventRecord(e->ev_fork, st));
                 HIPCHK(hipStreamWaitEvent(e->stream_odd, e->ev_fork, 0));
                 auto &tq = timer_slot(e, 2);
                 co.span = e->d_span ? e->d_span + 2 * (e->tused - 1) : nullptr;
                 HIPCHK(hipEventRecord(tq.first, e->stream_odd));
                 void *args[] = {&co};
-                HIPCHK(hipModuleLaunchKernel(e->tx_fn_odd, grid, 1, 1, kSoloLanes, 1, 1, 0, e->stream_odd, args, nullptr));
+                HIPCHK(hipModuleLaunchKernel(e->gold.tx.fn_odd, grid, 1, 1, kSoloLanes, 1, 1, 0, e->stream_odd, args, nullptr));
                 HIPCHK(hipEventRecord(tq.second, e->stream_odd));
                 HIPCHK(hipEventRecord(e->ev_join, e->stream_odd));
             }
             if (pack && !solo) {
                 // one wave per same-pc run of survivors (<= 64 lanes); the grid
                 // covers the worst case (every survivor alone), surplus waves exit
-                HIPCHK(launch_pack_runs(e->d_skeys2, c.resume_n, k, e->d_wrange + 0, e->d_nwaves + ep, st));
-                c.wrange = e->d_wrange;
-                c.n_waves = e->d_nwaves + ep;
+                HIPCHK(launch_pack_runs(e->w.d_skeys2, c.resume_n, k, e->w.d_wrange + 0, e->w.d_nwaves + ep, st));
+                c.wrange = e->w.d_wrange;
+                c.n_waves = e->w.d_nwaves + ep;
                 c.lanes = 1;
                 c.resume_waves = 0;
             }
@@ -1865,18 +1868,18 @@ struct Chunk {
 
 static fi_status chunk_begin(fi_engine *e, const Chunk &ch, hipStream_t st) {
     if (ch.capture) {   // every row = the golden stream (the prefix and golden-suffix rules)
-        const fi_engine::Capture &x = e->cx;
-        HIPCHK(launch_capture_init(x.d_out[ch.slot], ch.k, x.stride, x.bytes, e->d_gout, e->gout.size(), st));
-        HIPCHK(launch_capture_init(x.d_err[ch.slot], ch.k, x.stride, x.bytes, e->d_gerr, e->gerr.size(), st));
+        const Capture &x = e->w.cx;
+        HIPCHK(launch_capture_init(x.d_out[ch.slot], ch.k, x.stride, x.bytes, e->gold.d_gout, e->gold.gout.size(), st));
+        HIPCHK(launch_capture_init(x.d_err[ch.slot], ch.k, x.stride, x.bytes, e->gold.d_gerr, e->gold.gerr.size(), st));
     }
     fi_status s = run_pass(e, ch.sites, ch.k, ch.out, e->cfg.private_pages, st, ch.tick, ch.disp,
                            ch.capture ? (int)ch.slot : -1);
     if (s) return s;
     if (!(e->cfg.flags & FI_CFG_NO_REDO)) {
-        uint32_t *cnt = e->d_redo_cnt + ch.slot;
+        uint32_t *cnt = e->w.d_redo_cnt + ch.slot;
         HIPCHK(hipMemsetAsync(cnt, 0, 4, st));
-        HIPCHK(launch_redo_collect(ch.out, ch.k, e->d_redo_idx + ch.slot * e->cap, cnt, e->d_stats, st));
-        HIPCHK(hipMemcpyAsync(e->h_redo_cnt + ch.slot, cnt, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(launch_redo_collect(ch.out, ch.k, e->w.d_redo_idx + ch.slot * e->w.cap, cnt, e->w.d_stats, st));
+        HIPCHK(hipMemcpyAsync(e->w.h_redo_cnt + ch.slot, cnt, 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipEventRecord(e->ev_cnt[ch.slot], st));
     }
     return FI_OK;
@@ -1885,21 +1888,21 @@ static fi_status chunk_begin(fi_engine *e, const Chunk &ch, hipStream_t st) {
 static fi_status chunk_end(fi_engine *e, const Chunk &ch, fi_histogram *d_hist, hipStream_t st) {
     if (!(e->cfg.flags & FI_CFG_NO_REDO)) {
         HIPCHK(hipEventSynchronize(e->ev_cnt[ch.slot]));   // (normally long done: a chunk later was enqueued first)
-        const uint64_t nr = e->h_redo_cnt[ch.slot];
-        const uint32_t *idx = e->d_redo_idx + ch.slot * e->cap;
+        const uint64_t nr = e->w.h_redo_cnt[ch.slot];
+        const uint32_t *idx = e->w.d_redo_idx + ch.slot * e->w.cap;
         if (nr) {
             const uint64_t P = e->cfg.private_pages;
-            const uint64_t pool = e->cap * P;   // page frames a pass has
+            const uint64_t pool = e->w.cap * P;   // page frames a pass has
             const uint64_t P2 = std::min<uint64_t>(pool, redo_pages(P));
             const uint64_t B = std::max<uint64_t>(1, pool / P2);
             for (uint64_t d = 0; d < nr; d += B) {
                 const uint64_t b = std::min(B, nr - d);
-                HIPCHK(launch_redo_gather(ch.sites, idx + d, b, e->d_redo_sites, e->d_keys, e->d_perm, st));
+                HIPCHK(launch_redo_gather(ch.sites, idx + d, b, e->w.d_redo_sites, e->w.d_keys, e->w.d_perm, st));
                 // (capture: the same deterministic run, only longer, into the trial's own row again)
-                fi_status s = run_pass(e, e->d_redo_sites, b, e->d_redo_out, (uint32_t)P2, st, ch.tick, nullptr,
+                fi_status s = run_pass(e, e->w.d_redo_sites, b, e->w.d_redo_out, (uint32_t)P2, st, ch.tick, nullptr,
                                        ch.capture ? (int)ch.slot : -1, idx + d);
                 if (s) return s;
-                HIPCHK(launch_redo_scatter(idx + d, b, e->d_redo_out, ch.out, st));
+                HIPCHK(launch_redo_scatter(idx + d, b, e->w.d_redo_out, ch.out, st));
             }
         }
     }
@@ -1908,10 +1911,10 @@ static fi_status chunk_end(fi_engine *e, const Chunk &ch, fi_histogram *d_hist, 
     if (ch.weight) HIPCHK(launch_exact_hist(ch.sites, ch.out, ch.weight, ch.k, d_hist, st));
     else HIPCHK(launch_hist(ch.tsites ? ch.tsites : ch.sites, ch.out, ch.k, d_hist, nullptr, st));
     if (ch.host_out) {
-        if (!e->h_stage[ch.slot]) HIPCHK(hipHostMalloc(&e->h_stage[ch.slot], e->cap * sizeof(fi_outcome)));
-        HIPCHK(hipMemcpyAsync(e->h_stage[ch.slot], ch.out, ch.k * sizeof(fi_outcome), hipMemcpyDeviceToHost, st));
+        if (!e->w.h_stage[ch.slot]) HIPCHK(e->w.h_stage[ch.slot].alloc(e->w.cap));
+        HIPCHK(hipMemcpyAsync(e->w.h_stage[ch.slot], ch.out, ch.k * sizeof(fi_outcome), hipMemcpyDeviceToHost, st));
         if (ch.capture) {   // zeros past each stream's end, then rows and lengths to their staging
-            const fi_engine::Capture &x = e->cx;
+            const Capture &x = e->w.cx;
             const uint32_t sl = ch.slot;
             HIPCHK(launch_capture_finish(x.d_out[sl], ch.k, x.stride, x.bytes, x.d_len[sl], 0u, st));
             HIPCHK(hipMemcpyAsync(x.h_out[sl], x.d_out[sl], ch.k * x.stride, hipMemcpyDeviceToHost, st));
@@ -1931,9 +1934,9 @@ static fi_status chunk_end(fi_engine *e, const Chunk &ch, fi_histogram *d_hist, 
 static fi_status chunk_deliver(fi_engine *e, Chunk &ch) {
     if (!ch.host_out || !ch.k) return FI_OK;
     HIPCHK(hipEventSynchronize(e->ev_stage[ch.slot]));
-    memcpy(ch.host_out, e->h_stage[ch.slot], ch.k * sizeof(fi_outcome));
+    memcpy(ch.host_out, e->w.h_stage[ch.slot], ch.k * sizeof(fi_outcome));
     if (ch.capture) {
-        const fi_engine::Capture &x = e->cx;
+        const Capture &x = e->w.cx;
         capture_rows(x.out + ch.off * x.bytes, x.h_out[ch.slot], ch.k, x.bytes, x.stride);
         if (x.err) capture_rows(x.err + ch.off * x.bytes, x.h_err[ch.slot], ch.k, x.bytes, x.stride);
         if (x.lens) memcpy(x.lens + ch.off, x.h_len[ch.slot], ch.k * sizeof(fi_stream_len));
@@ -1952,11 +1955,11 @@ static void hist_add(fi_histogram *dst, const fi_histogram *src) {
 // golden outcome.  in = uploaded explicit sites (NULL: sample from `first`).
 static TickMapCtx tick_map_ctx(fi_engine *e, uint64_t first, const fi_tick_site *in) {
     TickMapCtx c{};
-    c.done = e->d_tk_done; c.rec = e->d_tk_rec; c.n_att = e->tk_done.size();
-    c.golden_ninst = e->golden.ninst; c.golden_ticks = e->t_stats.ticks;
+    c.done = e->gold.d_tk_done; c.rec = e->gold.d_tk_rec; c.n_att = e->gold.tk_done.size();
+    c.golden_ninst = e->gold.info.ninst; c.golden_ticks = e->gold.t_stats.ticks;
     c.in = in;
     c.d = campaign_draw(e, first);
-    c.gsub = e->gsub; c.gexit = e->golden.exit_code; c.gdetail = e->gdetail;
+    c.gsub = e->gold.gsub; c.gexit = e->gold.info.exit_code; c.gdetail = e->gold.gdetail;
     c.literal = e->tick_contract == FI_TICK_CONTRACT_LITERAL ? 1u : 0u;
     return c;
 }
@@ -1975,12 +1978,12 @@ struct SiteSource {
 };
 
 // Trials [first, first + n) or the given sites (src), in chunks of at most
-// e->cap; outcomes to out_dev (device, n entries) or out_host (through the
+// e->w.cap; outcomes to out_dev (device, n entries) or out_host (through the
 // alternating device buffers), histogram added to d_hist.  The event pair
 // ev0 / ev1 spans the whole call.
 static fi_status run_chunks(fi_engine *e, uint64_t first, const SiteSource &src, uint64_t n, fi_outcome *out_dev,
                             fi_outcome *out_host, fi_histogram *d_hist, hipStream_t st) {
-    HIPCHK(hipMemsetAsync(e->d_stats, 0, kNStats * sizeof(unsigned long long), st));
+    HIPCHK(hipMemsetAsync(e->w.d_stats, 0, kNStats * sizeof(unsigned long long), st));
     HIPCHK(hipEventRecord(e->ev0, st));
     Chunk prev, staged[2];   // (staged: chunks whose outcomes still sit in h_stage)
     bool have_prev = false;
@@ -1988,32 +1991,32 @@ static fi_status run_chunks(fi_engine *e, uint64_t first, const SiteSource &src,
     for (uint64_t done = 0; done < n; i++) {
         jit_install(e, st, false);   // the translated kernels, once their build has landed
         Chunk ch;
-        ch.k = std::min<uint64_t>({n - done, e->cap, e->jit ? kJitWindowChunk : e->cap});
-        if (e->cx.bytes) { ch.k = std::min(ch.k, e->cx.rows); ch.capture = true; ch.off = done; }
+        ch.k = std::min<uint64_t>({n - done, e->w.cap, e->gold.jit ? kJitWindowChunk : e->w.cap});
+        if (e->w.cx.bytes) { ch.k = std::min(ch.k, e->w.cx.rows); ch.capture = true; ch.off = done; }
         ch.slot = i & 1;
-        ch.sites = ch.slot ? e->d_sites_alt : e->d_sites;
-        ch.out = out_dev ? out_dev + done : ch.slot ? e->d_out_alt : e->d_out;
+        ch.sites = ch.slot ? e->w.d_sites_alt : e->w.d_sites;
+        ch.out = out_dev ? out_dev + done : ch.slot ? e->w.d_out_alt : e->w.d_out;
         ch.host_out = out_host ? out_host + done : nullptr;
         ch.tick = src.tick;
         if (src.sites) {
             HIPCHK(hipMemcpyAsync(ch.sites, src.sites + done, ch.k * sizeof(fi_site), hipMemcpyHostToDevice, st));
-            HIPCHK(launch_keys(ch.sites, ch.k, e->d_keys, e->d_perm, st));
+            HIPCHK(launch_keys(ch.sites, ch.k, e->w.d_keys, e->w.d_perm, st));
         } else if (src.tick) {   // tick sites: the mapper takes the sampler's place
-            ch.tsites = e->d_tk_sites[ch.slot]; ch.disp = e->d_tk_disp[ch.slot]; ch.res = e->d_tk_res[ch.slot];
+            ch.tsites = e->w.d_tk_sites[ch.slot]; ch.disp = e->w.d_tk_disp[ch.slot]; ch.res = e->w.d_tk_res[ch.slot];
             const fi_tick_site *in = nullptr;
             if (src.ticks) {
-                HIPCHK(hipMemcpyAsync(e->d_tk_in[ch.slot], src.ticks + done, ch.k * sizeof(fi_tick_site),
+                HIPCHK(hipMemcpyAsync(e->w.d_tk_in[ch.slot], src.ticks + done, ch.k * sizeof(fi_tick_site),
                                       hipMemcpyHostToDevice, st));
-                in = e->d_tk_in[ch.slot];
+                in = e->w.d_tk_in[ch.slot];
             }
-            HIPCHK(launch_tick_map(tick_map_ctx(e, first + done, in), ch.k, ch.sites, e->d_keys, e->d_perm,
-                                   e->d_tk_sites[ch.slot], e->d_tk_disp[ch.slot], e->d_tk_res[ch.slot], st));
+            HIPCHK(launch_tick_map(tick_map_ctx(e, first + done, in), ch.k, ch.sites, e->w.d_keys, e->w.d_perm,
+                                   e->w.d_tk_sites[ch.slot], e->w.d_tk_disp[ch.slot], e->w.d_tk_res[ch.slot], st));
         } else if (src.exact) {
-            ch.weight = e->d_weight[ch.slot];
-            HIPCHK(launch_exact_sites(*src.exact, first + done, ch.k, e->d_ex_classes, ch.sites, e->d_keys, e->d_perm,
-                                      e->d_weight[ch.slot], st));
+            ch.weight = e->w.d_weight[ch.slot];
+            HIPCHK(launch_exact_sites(*src.exact, first + done, ch.k, e->gold.d_ex_classes, ch.sites, e->w.d_keys, e->w.d_perm,
+                                      e->w.d_weight[ch.slot], st));
         } else {
-            HIPCHK(launch_sample(sample_ctx(e, first + done), ch.k, ch.sites, e->d_keys, e->d_perm, st));
+            HIPCHK(launch_sample(sample_ctx(e, first + done), ch.k, ch.sites, e->w.d_keys, e->w.d_perm, st));
         }
         fi_status s = chunk_begin(e, ch, st);
         if (s) return s;
@@ -2033,7 +2036,7 @@ static fi_status run_chunks(fi_engine *e, uint64_t first, const SiteSource &src,
         staged[prev.slot] = prev;
     }
     HIPCHK(hipEventRecord(e->ev1, st));
-    HIPCHK(launch_hist_stats(e->d_stats, d_hist, st));
+    HIPCHK(launch_hist_stats(e->w.d_stats, d_hist, st));
     for (auto &c : staged) {
         fi_status s = chunk_deliver(e, c);
         if (s) return s;
@@ -2041,7 +2044,7 @@ static fi_status run_chunks(fi_engine *e, uint64_t first, const SiteSource &src,
     return FI_OK;
 }
 
-// The end of a blocking run on e->stream into e->d_hist: wait for it, its
+// The end of a blocking run on e->stream into e->w.d_hist: wait for it, its
 // device time (ev0 .. ev1) to last_ms, its histogram added to hist.
 static fi_status run_finish(fi_engine *e, fi_histogram *hist) {
     HIPCHK(hipStreamSynchronize(e->stream));
@@ -2050,7 +2053,7 @@ static fi_status run_finish(fi_engine *e, fi_histogram *hist) {
     e->last_ms = ms;
     if (hist) {
         fi_histogram h;
-        HIPCHK(hipMemcpy(&h, e->d_hist, sizeof h, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(&h, e->w.d_hist, sizeof h, hipMemcpyDeviceToHost));
         hist_add(hist, &h);
     }
     return FI_OK;
@@ -2059,24 +2062,24 @@ static fi_status run_finish(fi_engine *e, fi_histogram *hist) {
 static fi_status run_common(fi_engine *e, uint64_t first, const SiteSource &src, uint64_t n, fi_outcome *out,
                             fi_histogram *hist) {
     if (!e) return FI_E_ARG;
-    if (!e->have_golden) return fail(e, FI_E_STATE, "golden run required");
+    if (!e->gold.have_golden) return fail(e, FI_E_STATE, "golden run required");
     if (src.sampled && !e->structures) return fail(e, FI_E_STATE, "fi_set_campaign first");
     HIPCHK(hipSetDevice(e->dev));
     const uint64_t chunk = e->cfg.max_trials_per_launch;
     fi_status s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), chunk));
     if (s) return s;
-    HIPCHK(hipMemsetAsync(e->d_hist, 0, sizeof(fi_histogram), e->stream));
-    s = run_chunks(e, first, src, n, nullptr, out, e->d_hist, e->stream);
+    HIPCHK(hipMemsetAsync(e->w.d_hist, 0, sizeof(fi_histogram), e->stream));
+    s = run_chunks(e, first, src, n, nullptr, out, e->w.d_hist, e->stream);
     return s ? s : run_finish(e, hist);
 }
 
 fi_status fi_wait_translation(fi_engine *e, fi_golden_info *out) {
     if (!e) return FI_E_ARG;
-    if (!e->have_golden) return fail(e, FI_E_STATE, "no golden run");
+    if (!e->gold.have_golden) return fail(e, FI_E_STATE, "no golden run");
     HIPCHK(hipSetDevice(e->dev));
     jit_install(e, e->stream, true);
     HIPCHK(hipStreamSynchronize(e->stream));
-    if (out) *out = e->golden;
+    if (out) *out = e->gold.info;
     return FI_OK;
 }
 
@@ -2108,22 +2111,23 @@ fi_status fi_exact_classes(const uint32_t *off33, const uint32_t *ev, uint64_t n
 
 // Every register's classes, once per golden run: packed, uploaded beside d_fw_ev.
 static fi_status exact_build(fi_engine *e) {
-    if (e->ex_ok) return FI_OK;
+    if (e->gold.ex_ok) return FI_OK;
     std::vector<uint64_t> words;
     for (uint32_t r = 1; r < 32; r++) {
-        e->ex_off[r] = (uint32_t)words.size();
-        const uint64_t cnt = exact_reg_classes(e->fw_off.data(), e->fw_ev.data(), e->golden.ninst, r, nullptr, 0,
-                                               &e->ex_dead[r]);
+        e->gold.ex_off[r] = (uint32_t)words.size();
+        const uint64_t cnt = exact_reg_classes(e->gold.fw_off.data(), e->gold.fw_ev.data(), e->gold.info.ninst, r, nullptr, 0,
+                                               &e->gold.ex_dead[r]);
         words.resize(words.size() + cnt);
-        exact_reg_classes(e->fw_off.data(), e->fw_ev.data(), e->golden.ninst, r, words.data() + e->ex_off[r], cnt,
+        exact_reg_classes(e->gold.fw_off.data(), e->gold.fw_ev.data(), e->gold.info.ninst, r, words.data() + e->gold.ex_off[r], cnt,
                           nullptr);
     }
-    e->ex_off[0] = 0;
-    e->ex_off[32] = (uint32_t)words.size();
-    dfree(e->d_ex_classes);
-    HIPCHK(hipMalloc(&e->d_ex_classes, std::max<size_t>(words.size(), 1) * 8));
-    if (!words.empty()) HIPCHK(hipMemcpy(e->d_ex_classes, words.data(), words.size() * 8, hipMemcpyHostToDevice));
-    e->ex_ok = true;
+    e->gold.ex_off[0] = 0;
+    e->gold.ex_off[32] = (uint32_t)words.size();
+    DevBuf<uint64_t> d_classes;
+    HIPCHK(d_classes.alloc(std::max<size_t>(words.size(), 1)));
+    if (!words.empty()) HIPCHK(hipMemcpy(d_classes, words.data(), words.size() * 8, hipMemcpyHostToDevice));
+    e->gold.d_ex_classes = std::move(d_classes);
+    e->gold.ex_ok = true;
     return FI_OK;
 }
 
@@ -2136,9 +2140,9 @@ static fi_status exact_build(fi_engine *e) {
 // merely writes FP or LR/SC state, which changes nothing about its memory.
 static const char *exact_mem_refusal(const fi_engine *e) {
     if (e->cpu_model != FI_CPU_ATOMIC) return "the CPU model is TimingSimpleCPU (exact campaigns enumerate numInst sites)";
-    if (!e->mem_live) return "the golden run's memory index is incomplete (the access trace overflowed, or an "
+    if (!e->gold.mem_live) return "the golden run's memory index is incomplete (the access trace overflowed, or an "
                              "instruction came from outside the pre-decoded text)";
-    if (e->golden_unmapped) return "the golden run unmapped memory (munmap, a shrinking brk): a word need not stay "
+    if (e->gold.golden_unmapped) return "the golden run unmapped memory (munmap, a shrinking brk): a word need not stay "
                                    "mapped up to its next access";
     return nullptr;
 }
@@ -2146,63 +2150,57 @@ static const char *exact_mem_refusal(const fi_engine *e) {
 // The memory classes under the campaign's (bits, burst), once per golden run
 // and pair: liveness, count, scan, emit (fi_kernels.hip), then the rows.
 static fi_status exact_mem_build(fi_engine *e) {
-    fi_engine::ExMem &m = e->xm;
+#define XMCHK(call) HIPCHK_AS("exact memory classes", call)
+    ExMem &m = e->gold.xm;
     const uint64_t bits = e->bits & burst_positions(e->burst);
     if (m.ok && m.bits == bits && m.burst == e->burst) return FI_OK;
-    m.ok = false;
-    dfree(m.d_rows); dfree(m.d_cls);
+    m = ExMem{};   // (not ok until the end)
     m.n_rows = exact_mem_sets(bits, e->burst, m.rows);
-    m.text_words = exact_mem_text_words(e->mem_pages.data(), e->mem_pages.size(), e->text_lo, e->text_hi);
-    m.words = e->mem_pages.size() * 512 - m.text_words;
-    m.n_classes = 0;
-    const uint64_t ninst = e->golden.ninst, pairs = m.words * ninst;
+    m.text_words = exact_mem_text_words(e->img.mem_pages.data(), e->img.mem_pages.size(), e->img.text_lo, e->img.text_hi);
+    m.words = e->img.mem_pages.size() * 512 - m.text_words;
+    const uint64_t ninst = e->gold.info.ninst, pairs = m.words * ninst;
     if (m.words && pairs / m.words != ninst) return fail(e, FI_E_ARG, "exact memory: words x ninst overflows");
     std::vector<uint64_t> offs(m.n_rows + 1, 0), wsum(kExactMaxMemRows, 0);
-    const uint64_t n_cnt = (uint64_t)m.n_rows * e->mw_n + 1;
+    const uint64_t n_cnt = (uint64_t)m.n_rows * e->gold.mw_n + 1;
     auto t0 = std::chrono::steady_clock::now();
-    if (e->mw_n && m.n_rows) {
+    if (e->gold.mw_n && m.n_rows) {
         if (n_cnt >= (1ULL << 31)) return fail(e, FI_E_ARG, "exact memory: 2^31 (byte set, word) pairs or more");
         ExactMemCtx c{};
-        c.mw_addr = e->d_mw_addr; c.mw_ev = e->d_mw_ev; c.mw_off = e->d_mw_off; c.mw_n = e->mw_n;
-        c.pages = e->d_mem_pages; c.n_pages = e->mem_pages.size();
-        c.text_lo = e->text_lo; c.text_hi = e->text_hi; c.ninst = ninst;
-        uint8_t *d_live = nullptr, *d_tmp = nullptr;
-        uint64_t *d_cnt = nullptr, *d_offs = nullptr, *d_wsum = nullptr;
+        c.mw_addr = e->gold.d_mw_addr; c.mw_ev = e->gold.d_mw_ev; c.mw_off = e->gold.d_mw_off; c.mw_n = e->gold.mw_n;
+        c.pages = e->img.d_mem_pages; c.n_pages = e->img.mem_pages.size();
+        c.text_lo = e->img.text_lo; c.text_hi = e->img.text_hi; c.ninst = ninst;
+        DevBuf<uint8_t> d_live, d_tmp;
+        DevBuf<uint64_t> d_cnt, d_offs;
+        DevBuf<unsigned long long> d_wsum;
         size_t tmp_bytes = 0;
-        hipError_t err = scan_u64_bytes(n_cnt, tmp_bytes);
-        if (err == hipSuccess) err = hipMalloc(&d_live, std::max<uint64_t>(e->mw_nev, 1));
-        if (err == hipSuccess) err = hipMalloc(&d_tmp, std::max<size_t>(tmp_bytes, 1));
-        if (err == hipSuccess) err = hipMalloc(&d_cnt, n_cnt * 8);
-        if (err == hipSuccess) err = hipMalloc(&d_offs, n_cnt * 8);
-        if (err == hipSuccess) err = hipMalloc(&d_wsum, kExactMaxMemRows * 8);
-        if (err == hipSuccess) err = hipMalloc(&m.d_rows, kExactMaxMemRows * sizeof(ExactMemRow));
+        XMCHK(scan_u64_bytes(n_cnt, tmp_bytes));
+        XMCHK(d_live.alloc(std::max<uint64_t>(e->gold.mw_nev, 1)));
+        XMCHK(d_tmp.alloc(std::max<size_t>(tmp_bytes, 1)));
+        XMCHK(d_cnt.alloc(n_cnt));
+        XMCHK(d_offs.alloc(n_cnt));
+        XMCHK(d_wsum.alloc(kExactMaxMemRows));
+        XMCHK(m.d_rows.alloc(kExactMaxMemRows));
         hipStream_t st = e->stream;
-        if (err == hipSuccess) err = hipMemsetAsync(d_cnt + (n_cnt - 1), 0, 8, st);
-        if (err == hipSuccess) err = hipMemsetAsync(d_wsum, 0, kExactMaxMemRows * 8, st);
-        if (err == hipSuccess) err = hipMemcpyAsync(m.d_rows, m.rows, m.n_rows * sizeof(ExactMemRow), hipMemcpyHostToDevice, st);
-        if (err == hipSuccess) err = launch_exact_mem_live(c, d_live, st);
-        if (err == hipSuccess) err = launch_exact_mem_walk(c, m.d_rows, m.n_rows, d_live, d_cnt,
-                                                           (unsigned long long *)d_wsum, nullptr, 0, st);
-        if (err == hipSuccess) err = scan_u64(d_tmp, tmp_bytes, d_cnt, d_offs, n_cnt, st);
+        XMCHK(hipMemsetAsync(d_cnt + (n_cnt - 1), 0, 8, st));
+        XMCHK(hipMemsetAsync(d_wsum, 0, kExactMaxMemRows * 8, st));
+        XMCHK(hipMemcpyAsync(m.d_rows, m.rows, m.n_rows * sizeof(ExactMemRow), hipMemcpyHostToDevice, st));
+        XMCHK(launch_exact_mem_live(c, d_live, st));
+        XMCHK(launch_exact_mem_walk(c, m.d_rows, m.n_rows, d_live, d_cnt, d_wsum, nullptr, 0, st));
+        XMCHK(scan_u64(d_tmp, tmp_bytes, d_cnt, d_offs, n_cnt, st));
         // the offsets at the rows' starts and the total: every mw_n-th entry
-        if (err == hipSuccess) err = hipStreamSynchronize(st);
-        if (err == hipSuccess) err = hipMemcpy2D(offs.data(), 8, d_offs, (size_t)e->mw_n * 8, 8, m.n_rows + 1,
-                                                 hipMemcpyDeviceToHost);
-        if (err == hipSuccess) err = hipMemcpy(wsum.data(), d_wsum, kExactMaxMemRows * 8, hipMemcpyDeviceToHost);
+        XMCHK(hipStreamSynchronize(st));
+        XMCHK(hipMemcpy2D(offs.data(), 8, d_offs, (size_t)e->gold.mw_n * 8, 8, m.n_rows + 1, hipMemcpyDeviceToHost));
+        XMCHK(hipMemcpy(wsum.data(), d_wsum, kExactMaxMemRows * 8, hipMemcpyDeviceToHost));
         const uint64_t total = offs[m.n_rows];
-        if (err == hipSuccess && total < (1ULL << 32)) {
-            err = hipMalloc(&m.d_cls, std::max<uint64_t>(total, 1) * sizeof(ExactMemClass));
-            if (err == hipSuccess && total)
-                err = launch_exact_mem_walk(c, m.d_rows, m.n_rows, d_live, d_offs, nullptr, m.d_cls, 1, st);
-            if (err == hipSuccess) err = hipStreamSynchronize(st);
-        }
-        (void)hipFree(d_live); (void)hipFree(d_tmp); (void)hipFree(d_cnt); (void)hipFree(d_offs); (void)hipFree(d_wsum);
-        if (err != hipSuccess) return fail(e, FI_E_HIP, "exact memory classes: %s", hipGetErrorString(err));
         if (total >= (1ULL << 32)) return fail(e, FI_E_ARG, "exact memory: 2^32 classes or more");
+        XMCHK(m.d_cls.alloc(std::max<uint64_t>(total, 1)));
+        if (total) XMCHK(launch_exact_mem_walk(c, m.d_rows, m.n_rows, d_live, d_offs, nullptr, m.d_cls, 1, st));
+        XMCHK(hipStreamSynchronize(st));
     } else {
-        HIPCHK(hipMalloc(&m.d_rows, kExactMaxMemRows * sizeof(ExactMemRow)));
-        HIPCHK(hipMalloc(&m.d_cls, sizeof(ExactMemClass)));
+        HIPCHK(m.d_rows.alloc(kExactMaxMemRows));
+        HIPCHK(m.d_cls.alloc(1));
     }
+#undef XMCHK
     for (uint32_t g = 0; g < m.n_rows; g++) {
         m.classes[g] = offs[g + 1] - offs[g];
         m.dead[g] = pairs - wsum[g];
@@ -2222,7 +2220,7 @@ static fi_status exact_mem_build(fi_engine *e) {
 // dead sites and (info, may be NULL) its sizes.
 static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, ExactDead &dd, fi_exact_info *info) {
     if (!e) return FI_E_ARG;
-    if (!e->have_golden) return fail(e, FI_E_STATE, "%s: golden run required", who);
+    if (!e->gold.have_golden) return fail(e, FI_E_STATE, "%s: golden run required", who);
     if (!e->structures) return fail(e, FI_E_STATE, "%s: fi_set_campaign first", who);
     const bool mem = (e->structures >> FI_T_MEM) & 1;
     if (mem && !e->exact_mem)
@@ -2234,7 +2232,7 @@ static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, Exac
     }
     if (e->cpu_model != FI_CPU_ATOMIC)
         return fail(e, FI_E_STATE, "%s: exact campaigns enumerate numInst sites (the CPU model is TimingSimpleCPU)", who);
-    if (!e->fw_ok)
+    if (!e->gold.fw_ok)
         return fail(e, FI_E_STATE, "%s: the golden run has no first-access index (a golden trace that is incomplete "
                     "or 2^29 instructions or more)", who);
     HIPCHK(hipSetDevice(e->dev));
@@ -2243,20 +2241,20 @@ static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, Exac
     if (s) return s;
     dd = ExactDead{};
     fi_exact_info x{};
-    const uint64_t ninst = e->golden.ninst;
-    p = exact_plan(e->structures, e->ex_off, ninst, e->bits, e->burst, x.classes);
+    const uint64_t ninst = e->gold.info.ninst;
+    p = exact_plan(e->structures, e->gold.ex_off, ninst, e->bits, e->burst, x.classes);
     for (uint32_t t = 1; t < FI_N_STRUCT; t++) {
         if (!((e->structures >> t) & 1)) continue;
         if (t == FI_T_MEM) continue;
         x.space += ninst * p.nbits;
         if (t < 32) {
-            dd.dead[t] = (uint32_t)e->ex_dead[t];
-            x.dead_sites += e->ex_dead[t] * p.nbits;
+            dd.dead[t] = (uint32_t)e->gold.ex_dead[t];
+            x.dead_sites += e->gold.ex_dead[t] * p.nbits;
         }
     }
     if (mem) {
-        fi_engine::ExMem &m = e->xm;
-        exact_plan_mem(p, m.rows, m.n_rows, m.classes, m.d_rows, m.d_cls, e->d_mw_addr);
+        ExMem &m = e->gold.xm;
+        exact_plan_mem(p, m.rows, m.n_rows, m.classes, m.d_rows, m.d_cls, e->gold.d_mw_addr);
         x.classes[FI_T_MEM] = m.n_classes;
         x.space += m.words * ninst * p.nbits;
         for (uint32_t g = 0; g < m.n_rows; g++) {
@@ -2285,7 +2283,7 @@ fi_status fi_exact_get_info(fi_engine *e, fi_exact_info *out) {
 fi_status fi_set_exact_memory(fi_engine *e, int on) {
     if (!e) return FI_E_ARG;
     if (on) {
-        if (!e->have_golden) return fail(e, FI_E_STATE, "fi_set_exact_memory: golden run required");
+        if (!e->gold.have_golden) return fail(e, FI_E_STATE, "fi_set_exact_memory: golden run required");
         const char *why = exact_mem_refusal(e);
         if (why) return fail(e, FI_E_STATE, "fi_set_exact_memory: %s", why);
     }
@@ -2295,7 +2293,7 @@ fi_status fi_set_exact_memory(fi_engine *e, int on) {
 
 fi_status fi_exact_mem_get_info(fi_engine *e, fi_exact_mem_info *out) {
     if (!e || !out) return FI_E_ARG;
-    if (!e->have_golden) return fail(e, FI_E_STATE, "fi_exact_mem_get_info: golden run required");
+    if (!e->gold.have_golden) return fail(e, FI_E_STATE, "fi_exact_mem_get_info: golden run required");
     if (!e->structures) return fail(e, FI_E_STATE, "fi_exact_mem_get_info: fi_set_campaign first");
     if (!e->exact_mem) return fail(e, FI_E_STATE, "fi_exact_mem_get_info: fi_set_exact_memory is off");
     const char *why = exact_mem_refusal(e);
@@ -2303,9 +2301,9 @@ fi_status fi_exact_mem_get_info(fi_engine *e, fi_exact_mem_info *out) {
     HIPCHK(hipSetDevice(e->dev));
     fi_status s = exact_mem_build(e);
     if (s) return s;
-    const fi_engine::ExMem &m = e->xm;
+    const ExMem &m = e->gold.xm;
     *out = fi_exact_mem_info{};
-    out->words = m.words; out->text_words = m.text_words; out->index_words = e->mw_n;
+    out->words = m.words; out->text_words = m.text_words; out->index_words = e->gold.mw_n;
     out->byte_sets = m.n_rows;
     out->build_ms = m.build_ms;
     for (uint32_t g = 0; g < m.n_rows; g++) {
@@ -2339,13 +2337,13 @@ fi_status fi_exact_mem_classes(const uint64_t *ev, uint64_t n_ev, uint64_t ninst
 fi_status fi_golden_mem_index(fi_engine *e, uint64_t *addr, uint64_t addr_cap, uint32_t *off, uint64_t off_cap,
                               uint64_t *ev, uint64_t ev_cap, uint64_t counts[2]) {
     if (!e) return FI_E_ARG;
-    if (!e->have_golden) return fail(e, FI_E_STATE, "fi_golden_mem_index: golden run required");
-    if (!e->mem_live) return fail(e, FI_E_STATE, "fi_golden_mem_index: the golden run's memory index is incomplete");
+    if (!e->gold.have_golden) return fail(e, FI_E_STATE, "fi_golden_mem_index: golden run required");
+    if (!e->gold.mem_live) return fail(e, FI_E_STATE, "fi_golden_mem_index: the golden run's memory index is incomplete");
     HIPCHK(hipSetDevice(e->dev));
-    if (counts) { counts[0] = e->mw_n; counts[1] = e->mw_nev; }
-    if (addr) HIPCHK(hipMemcpy(addr, e->d_mw_addr, std::min<uint64_t>(addr_cap, e->mw_n) * 8, hipMemcpyDeviceToHost));
-    if (off) HIPCHK(hipMemcpy(off, e->d_mw_off, std::min<uint64_t>(off_cap, (uint64_t)e->mw_n + 1) * 4, hipMemcpyDeviceToHost));
-    if (ev) HIPCHK(hipMemcpy(ev, e->d_mw_ev, std::min<uint64_t>(ev_cap, e->mw_nev) * 8, hipMemcpyDeviceToHost));
+    if (counts) { counts[0] = e->gold.mw_n; counts[1] = e->gold.mw_nev; }
+    if (addr) HIPCHK(hipMemcpy(addr, e->gold.d_mw_addr, std::min<uint64_t>(addr_cap, e->gold.mw_n) * 8, hipMemcpyDeviceToHost));
+    if (off) HIPCHK(hipMemcpy(off, e->gold.d_mw_off, std::min<uint64_t>(off_cap, (uint64_t)e->gold.mw_n + 1) * 4, hipMemcpyDeviceToHost));
+    if (ev) HIPCHK(hipMemcpy(ev, e->gold.d_mw_ev, std::min<uint64_t>(ev_cap, e->gold.mw_nev) * 8, hipMemcpyDeviceToHost));
     return FI_OK;
 }
 
@@ -2361,11 +2359,11 @@ fi_status fi_exact_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site *site
     s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch));
     if (s) return s;
     for (uint64_t done = 0; done < n;) {
-        const uint64_t k = std::min<uint64_t>(n - done, e->cap);
-        HIPCHK(launch_exact_sites(p, first + done, k, e->d_ex_classes, e->d_sites, e->d_keys, e->d_perm, e->d_weight[0],
+        const uint64_t k = std::min<uint64_t>(n - done, e->w.cap);
+        HIPCHK(launch_exact_sites(p, first + done, k, e->gold.d_ex_classes, e->w.d_sites, e->w.d_keys, e->w.d_perm, e->w.d_weight[0],
                                   e->stream));
-        HIPCHK(hipMemcpyAsync(sites + done, e->d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
-        if (weights) HIPCHK(hipMemcpyAsync(weights + done, e->d_weight[0], k * 4, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(sites + done, e->w.d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        if (weights) HIPCHK(hipMemcpyAsync(weights + done, e->w.d_weight[0], k * 4, hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
         done += k;
     }
@@ -2382,29 +2380,29 @@ fi_status fi_run_exact(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out
                     (unsigned long long)(first + n), (unsigned long long)p.trials);
     s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch));
     if (s) return s;
-    HIPCHK(hipMemsetAsync(e->d_hist, 0, sizeof(fi_histogram), e->stream));
-    if (first == 0) HIPCHK(launch_exact_dead(dd, e->d_hist, e->stream));   // the sites that need no trial
+    HIPCHK(hipMemsetAsync(e->w.d_hist, 0, sizeof(fi_histogram), e->stream));
+    if (first == 0) HIPCHK(launch_exact_dead(dd, e->w.d_hist, e->stream));   // the sites that need no trial
     SiteSource src;
     src.exact = &p;
-    s = run_chunks(e, first, src, n, nullptr, out, e->d_hist, e->stream);
+    s = run_chunks(e, first, src, n, nullptr, out, e->w.d_hist, e->stream);
     return s ? s : run_finish(e, hist);
 }
 
 // Output capture (the sizing and the staging copy: fi_capture.h).
 // The rows and their pinned mirror are grown on demand like the other work
-// buffers and released with them (free_work).
+// buffers and replaced with them.
 static fi_status ensure_capture(fi_engine *e, uint64_t rows, uint32_t stride) {
-    fi_engine::Capture &x = e->cx;
+    Capture &x = e->w.cx;
     if (rows * stride <= x.held_b && rows <= x.held_rows) return FI_OK;
     const uint64_t b = std::max(x.held_b, rows * stride), r = std::max(x.held_rows, rows);
-    free_capture(e);
+    x = Capture{};   // (holds nothing until every buffer is made)
     for (int i = 0; i < 2; i++) {
-        HIPCHK(hipMalloc(&x.d_out[i], b));
-        HIPCHK(hipMalloc(&x.d_err[i], b));
-        HIPCHK(hipMalloc(&x.d_len[i], r * sizeof(fi_stream_len)));
-        HIPCHK(hipHostMalloc(&x.h_out[i], b));
-        HIPCHK(hipHostMalloc(&x.h_err[i], b));
-        HIPCHK(hipHostMalloc(&x.h_len[i], r * sizeof(fi_stream_len)));
+        HIPCHK(x.d_out[i].alloc(b));
+        HIPCHK(x.d_err[i].alloc(b));
+        HIPCHK(x.d_len[i].alloc(r));
+        HIPCHK(x.h_out[i].alloc(b));
+        HIPCHK(x.h_err[i].alloc(b));
+        HIPCHK(x.h_len[i].alloc(r));
     }
     x.held_b = b; x.held_rows = r;
     return FI_OK;
@@ -2415,7 +2413,7 @@ fi_status fi_run_sites_capture(fi_engine *e, const fi_site *sites, uint64_t n, u
     if (!e) return FI_E_ARG;
     if (const char *why = capture_args_error(sites, n, cap_bytes, out_buf))
         return fail(e, FI_E_ARG, "fi_run_sites_capture: %s", why);
-    if (!e->have_golden) return fail(e, FI_E_STATE, "golden run required");
+    if (!e->gold.have_golden) return fail(e, FI_E_STATE, "golden run required");
     if (n == 0) return FI_OK;
     HIPCHK(hipSetDevice(e->dev));
     const uint32_t stride = capture_stride(cap_bytes);
@@ -2427,13 +2425,13 @@ fi_status fi_run_sites_capture(fi_engine *e, const fi_site *sites, uint64_t n, u
     size_t free_b = 0, total_b = 0;
     HIPCHK(hipMemGetInfo(&free_b, &total_b));
     // (what an earlier call left is counted as free: it is reused or replaced)
-    const uint64_t held = 4 * e->cx.held_b + 2 * e->cx.held_rows * sizeof(fi_stream_len);
+    const uint64_t held = 4 * e->w.cx.held_b + 2 * e->w.cx.held_rows * sizeof(fi_stream_len);
     const uint64_t rows = capture_rows_for(want, ((uint64_t)free_b + held) / 4, stride);
     std::vector<fi_outcome> own;   // the rows travel with the outcomes' staging: the run has a host array
     if (!out) { own.resize(n); out = own.data(); }
     s = ensure_capture(e, rows, stride);
     if (!s) {
-        fi_engine::Capture &x = e->cx;
+        Capture &x = e->w.cx;
         x.rows = rows; x.stride = stride;
         x.out = out_buf; x.err = err_buf; x.lens = lens;
         x.bytes = cap_bytes;   // capture is on
@@ -2449,7 +2447,7 @@ fi_status fi_run_sites_capture(fi_engine *e, const fi_site *sites, uint64_t n, u
 fi_status fi_set_cpu_model(fi_engine *e, int model, const fi_timing_params *p) {
     if (!e) return FI_E_ARG;
     if (model != FI_CPU_ATOMIC && model != FI_CPU_TIMING) return fail(e, FI_E_ARG, "unknown CPU model %d", model);
-    if (e->have_golden) return fail(e, FI_E_STATE, "fi_set_cpu_model: set before fi_golden_run");
+    if (e->gold.have_golden) return fail(e, FI_E_STATE, "fi_set_cpu_model: set before fi_golden_run");
     e->cpu_model = model;
     if (p) e->tparams = *p; else fi_timing_default_params(&e->tparams);
     return FI_OK;
@@ -2458,26 +2456,26 @@ fi_status fi_set_cpu_model(fi_engine *e, int model, const fi_timing_params *p) {
 fi_status fi_tick_golden(fi_engine *e, fi_tick_info *out) {
     if (!e || !out) return FI_E_ARG;
     *out = fi_tick_info{};
-    snprintf(out->status, sizeof out->status, "%s", e->t_status.c_str());
-    out->attempts = e->t_ops.size();
-    out->golden_ticks = e->t_stats.ticks;
-    out->stats = e->t_stats;
+    snprintf(out->status, sizeof out->status, "%s", e->gold.t_status.c_str());
+    out->attempts = e->gold.t_ops.size();
+    out->golden_ticks = e->gold.t_stats.ticks;
+    out->stats = e->gold.t_stats;
     return FI_OK;
 }
 
 fi_status fi_tick_trace(fi_engine *e, fi_timing_op *ops, fi_timing_ticks *ticks, uint64_t cap, uint64_t *n) {
     if (!e) return FI_E_ARG;
-    if (!e->t_status.empty()) return fail(e, FI_E_STATE, "tick model: %s", e->t_status.c_str());
-    const uint64_t k = std::min<uint64_t>(cap, e->t_ops.size());
-    if (ops && k) memcpy(ops, e->t_ops.data(), k * sizeof *ops);
-    if (ticks && k) memcpy(ticks, e->t_ticks.data(), k * sizeof *ticks);
-    if (n) *n = e->t_ops.size();
+    if (!e->gold.t_status.empty()) return fail(e, FI_E_STATE, "tick model: %s", e->gold.t_status.c_str());
+    const uint64_t k = std::min<uint64_t>(cap, e->gold.t_ops.size());
+    if (ops && k) memcpy(ops, e->gold.t_ops.data(), k * sizeof *ops);
+    if (ticks && k) memcpy(ticks, e->gold.t_ticks.data(), k * sizeof *ticks);
+    if (n) *n = e->gold.t_ops.size();
     return FI_OK;
 }
 
 static fi_status tick_ready(fi_engine *e) {
-    if (!e->have_golden) return fail(e, FI_E_STATE, "golden run required");
-    if (!e->t_status.empty()) return fail(e, FI_E_STATE, "tick model: %s", e->t_status.c_str());
+    if (!e->gold.have_golden) return fail(e, FI_E_STATE, "golden run required");
+    if (!e->gold.t_status.empty()) return fail(e, FI_E_STATE, "tick model: %s", e->gold.t_status.c_str());
     return FI_OK;
 }
 
@@ -2496,10 +2494,10 @@ static fi_status tick_check(fi_engine *e, const fi_tick_site *ts, uint64_t n, bo
     for (uint64_t i = 0; ts && i < n; i++) {
         const fi_tick_site &t = ts[i];
         const bool target_ok = (t.target >= 1 && t.target <= FI_T_PC) || t.target == FI_T_RESULT;
-        if (!t.mask || !target_ok || t.tick >= e->t_stats.ticks)
+        if (!t.mask || !target_ok || t.tick >= e->gold.t_stats.ticks)
             return fail(e, FI_E_ARG, "tick site %llu: target %u, tick %llu (golden run %llu ticks)",
                         (unsigned long long)i, t.target, (unsigned long long)t.tick,
-                        (unsigned long long)e->t_stats.ticks);
+                        (unsigned long long)e->gold.t_stats.ticks);
     }
     return FI_OK;
 }
@@ -2510,7 +2508,7 @@ fi_status fi_sample_tick_sites(fi_engine *e, uint64_t first, uint64_t n, fi_tick
     if (st) return st;
     const DrawCtx d = campaign_draw(e, first);   // the sampler's draw with the golden run's ticks for numInst
     for (uint64_t i = 0; i < n; i++) {
-        const SiteDraw s = draw_site(d, i, e->t_stats.ticks);
+        const SiteDraw s = draw_site(d, i, e->gold.t_stats.ticks);
         out[i] = fi_tick_site{s.when, s.mask, s.target, s.trial};
     }
     return FI_OK;
@@ -2522,13 +2520,13 @@ static void map_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi_
     const uint32_t literal = e->tick_contract == FI_TICK_CONTRACT_LITERAL ? 1u : 0u;
     for (uint64_t i = 0; i < n; i++) {
         const fi_tick_site &t = ts[i];
-        const TickMap m = tick_map_site(e->tk_done.data(), e->tk_rec.data(), e->tk_done.size(), e->golden.ninst,
+        const TickMap m = tick_map_site(e->gold.tk_done.data(), e->gold.tk_rec.data(), e->gold.tk_done.size(), e->gold.info.ninst,
                                         t.tick, t.target, t.mask, t.trial, literal);
         disp[i] = (uint8_t)m.disp;
         sites[i] = m.site;
         if (host_out)
-            host_out[i] = tick_map_outcome(m, e->tk_rec[m.attempt], e->gsub, e->golden.exit_code, e->gdetail,
-                                           e->golden.ninst);
+            host_out[i] = tick_map_outcome(m, e->gold.tk_rec[m.attempt], e->gold.gsub, e->gold.info.exit_code, e->gold.gdetail,
+                                           e->gold.info.ninst);
     }
 }
 
@@ -2560,25 +2558,33 @@ fi_status fi_set_tick_contract(fi_engine *e, int contract) {
 // The packed attempt table on the device: the host map's own, uploaded at the
 // first device map after a golden run (fi_golden_run drops the copy).
 static fi_status ensure_tick_table(fi_engine *e) {
-    if (e->d_tk_done) return FI_OK;
-    if (e->tk_done.empty()) return fail(e, FI_E_STATE, "tick model: no attempts");
-    HIPCHK(hipMalloc(&e->d_tk_done, e->tk_done.size() * sizeof(uint64_t)));
-    HIPCHK(hipMalloc(&e->d_tk_rec, e->tk_rec.size() * sizeof(TickRec)));
-    HIPCHK(hipMemcpy(e->d_tk_done, e->tk_done.data(), e->tk_done.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(e->d_tk_rec, e->tk_rec.data(), e->tk_rec.size() * sizeof(TickRec), hipMemcpyHostToDevice));
+    Golden &g = e->gold;
+    if (g.d_tk_done) return FI_OK;
+    if (g.tk_done.empty()) return fail(e, FI_E_STATE, "tick model: no attempts");
+    DevBuf<uint64_t> d_done;
+    DevBuf<TickRec> d_rec;
+    HIPCHK(d_done.alloc(g.tk_done.size()));
+    HIPCHK(d_rec.alloc(g.tk_rec.size()));
+    HIPCHK(hipMemcpy(d_done, g.tk_done.data(), g.tk_done.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_rec, g.tk_rec.data(), g.tk_rec.size() * sizeof(TickRec), hipMemcpyHostToDevice));
+    g.d_tk_rec = std::move(d_rec);
+    g.d_tk_done = std::move(d_done);
     return FI_OK;
 }
 
 // The device map's work buffers, one set per chunk slot, beside the others
-// (ensure_work, which frees them when it grows): made once a device tick run
-// or map is first asked for.
+// (growth of the work buffers drops them): made once a device tick run or map
+// is first asked for; tk_ok once all are.
 static fi_status ensure_tick_work(fi_engine *e) {
+    Work &w = e->w;
+    if (w.tk_ok) return FI_OK;
     for (int i = 0; i < 2; i++) {
-        if (!e->d_tk_sites[i]) HIPCHK(hipMalloc(&e->d_tk_sites[i], e->cap * sizeof(fi_site)));
-        if (!e->d_tk_disp[i]) HIPCHK(hipMalloc(&e->d_tk_disp[i], e->cap));
-        if (!e->d_tk_res[i]) HIPCHK(hipMalloc(&e->d_tk_res[i], e->cap * sizeof(fi_outcome)));
-        if (!e->d_tk_in[i]) HIPCHK(hipMalloc(&e->d_tk_in[i], e->cap * sizeof(fi_tick_site)));
+        HIPCHK(w.d_tk_sites[i].alloc(w.cap));
+        HIPCHK(w.d_tk_disp[i].alloc(w.cap));
+        HIPCHK(w.d_tk_res[i].alloc(w.cap));
+        HIPCHK(w.d_tk_in[i].alloc(w.cap));
     }
+    w.tk_ok = true;
     return FI_OK;
 }
 
@@ -2598,8 +2604,8 @@ static fi_status tick_run_device(fi_engine *e, uint64_t first, const fi_tick_sit
     fi_status s = tick_check(e, ts, n, !ts, true);
     if (s || !n) return s;
     if ((s = tick_device_prepare(e, n))) return s;
-    HIPCHK(hipMemsetAsync(e->d_hist, 0, sizeof(fi_histogram), e->stream));
-    s = run_chunks(e, first, SiteSource{nullptr, ts, !ts, true}, n, nullptr, out, e->d_hist, e->stream);
+    HIPCHK(hipMemsetAsync(e->w.d_hist, 0, sizeof(fi_histogram), e->stream));
+    s = run_chunks(e, first, SiteSource{nullptr, ts, !ts, true}, n, nullptr, out, e->w.d_hist, e->stream);
     return s ? s : run_finish(e, hist);
 }
 
@@ -2619,18 +2625,18 @@ fi_status fi_map_tick_sites_device(fi_engine *e, const fi_tick_site *ts, uint64_
     fi_status s = tick_check(e, ts, n, !ts, false);
     if (s || !n) return s;
     if ((s = tick_device_prepare(e, n))) return s;
-    std::vector<fi_site> tsv(ts_out ? std::min<uint64_t>(n, e->cap) : 0);
+    std::vector<fi_site> tsv(ts_out ? std::min<uint64_t>(n, e->w.cap) : 0);
     for (uint64_t done = 0; done < n;) {
-        const uint64_t k = std::min<uint64_t>(n - done, e->cap);
-        if (ts) HIPCHK(hipMemcpyAsync(e->d_tk_in[0], ts + done, k * sizeof(fi_tick_site), hipMemcpyHostToDevice, e->stream));
-        HIPCHK(launch_tick_map(tick_map_ctx(e, first + done, ts ? e->d_tk_in[0] : nullptr), k, e->d_sites, e->d_keys,
-                               e->d_perm, e->d_tk_sites[0], e->d_tk_disp[0], e->d_tk_res[0], e->stream));
-        HIPCHK(hipMemcpyAsync(sites + done, e->d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipMemcpyAsync(disp + done, e->d_tk_disp[0], k, hipMemcpyDeviceToHost, e->stream));
+        const uint64_t k = std::min<uint64_t>(n - done, e->w.cap);
+        if (ts) HIPCHK(hipMemcpyAsync(e->w.d_tk_in[0], ts + done, k * sizeof(fi_tick_site), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(launch_tick_map(tick_map_ctx(e, first + done, ts ? e->w.d_tk_in[0] : nullptr), k, e->w.d_sites, e->w.d_keys,
+                               e->w.d_perm, e->w.d_tk_sites[0], e->w.d_tk_disp[0], e->w.d_tk_res[0], e->stream));
+        HIPCHK(hipMemcpyAsync(sites + done, e->w.d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(disp + done, e->w.d_tk_disp[0], k, hipMemcpyDeviceToHost, e->stream));
         if (host_out)
-            HIPCHK(hipMemcpyAsync(host_out + done, e->d_tk_res[0], k * sizeof(fi_outcome), hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(hipMemcpyAsync(host_out + done, e->w.d_tk_res[0], k * sizeof(fi_outcome), hipMemcpyDeviceToHost, e->stream));
         if (ts_out)
-            HIPCHK(hipMemcpyAsync(tsv.data(), e->d_tk_sites[0], k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(hipMemcpyAsync(tsv.data(), e->w.d_tk_sites[0], k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
         HIPCHK(hipStreamSynchronize(e->stream));
         for (uint64_t i = 0; ts_out && i < k; i++) {
             fi_tick_site &o = ts_out[done + i];
@@ -2689,7 +2695,7 @@ fi_status fi_run_tick_trials(fi_engine *e, uint64_t first, uint64_t n, fi_outcom
 
 fi_status fi_run_trials_device(fi_engine *e, uint64_t first, uint64_t n, void *d_out, void *d_hist, void *stream) {
     if (!e || !d_out || !d_hist) return FI_E_ARG;
-    if (!e->have_golden) return fail(e, FI_E_STATE, "golden run required");
+    if (!e->gold.have_golden) return fail(e, FI_E_STATE, "golden run required");
     if (!e->structures) return fail(e, FI_E_STATE, "fi_set_campaign first");
     HIPCHK(hipSetDevice(e->dev));
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
@@ -2711,7 +2717,7 @@ fi_status fi_sync(fi_engine *e) {
 
 double fi_last_kernel_ms(fi_engine *e) { return e ? e->last_ms : 0.0; }
 
-const char *fi_translate_status(fi_engine *e) { return e ? e->tx_status.c_str() : "no engine"; }
+const char *fi_translate_status(fi_engine *e) { return e ? e->gold.tx_status.c_str() : "no engine"; }
 
 // hipRTC build of the trial kernel with `body` as translated blocks, no
 // device needed (tests; inspecting generated code offline).
@@ -2751,27 +2757,27 @@ fi_status fi_debug_jit_build(const char *body, const char *arch, int part, int u
 
 fi_status fi_debug_waves(fi_engine *e, uint64_t *out, uint64_t n_waves) {
     if (!e || !out) return FI_E_ARG;
-    if (n_waves > e->cap) return fail(e, FI_E_ARG, "more waves than the work buffers hold");
+    if (n_waves > e->w.cap) return fail(e, FI_E_ARG, "more waves than the work buffers hold");
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(out, e->d_wave_dbg, n_waves * kWaveDbgWords * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, e->w.d_wave_dbg, n_waves * kWaveDbgWords * sizeof(uint64_t), hipMemcpyDeviceToHost));
     return FI_OK;
 }
 
 fi_status fi_debug_epochs(fi_engine *e, uint32_t *out16) {
-    if (!e || !out16 || !e->d_cnt) return FI_E_ARG;
+    if (!e || !out16 || !e->w.d_cnt) return FI_E_ARG;
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(out16, e->d_cnt, 16 * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out16, e->w.d_cnt, 16 * 4, hipMemcpyDeviceToHost));
     return FI_OK;
 }
 
 fi_status fi_debug_golden_trace(fi_engine *e, void *pre_out, uint64_t pre_cap, uint64_t *n_pre, uint32_t *trace_out,
                                 uint64_t trace_cap, uint64_t *n_trace, uint64_t *text_lo) {
     if (!e) return FI_E_ARG;
-    if (pre_out) memcpy(pre_out, e->g_pre.data(), std::min<uint64_t>(pre_cap, e->g_pre.size()) * sizeof(PreInst));
-    if (trace_out) memcpy(trace_out, e->g_trace.data(), std::min<uint64_t>(trace_cap, e->g_trace.size()) * 4);
-    if (n_pre) *n_pre = e->g_pre.size();
-    if (n_trace) *n_trace = e->g_trace.size();
-    if (text_lo) *text_lo = e->text_lo;
+    if (pre_out) memcpy(pre_out, e->gold.g_pre.data(), std::min<uint64_t>(pre_cap, e->gold.g_pre.size()) * sizeof(PreInst));
+    if (trace_out) memcpy(trace_out, e->gold.g_trace.data(), std::min<uint64_t>(trace_cap, e->gold.g_trace.size()) * 4);
+    if (n_pre) *n_pre = e->gold.g_pre.size();
+    if (n_trace) *n_trace = e->gold.g_trace.size();
+    if (text_lo) *text_lo = e->img.text_lo;
     return FI_OK;
 }
 
@@ -2815,11 +2821,11 @@ fi_status fi_debug_translate_flags(const void *pre, uint64_t n_pre, uint64_t tex
 fi_status fi_debug_translation(fi_engine *e, char *buf, uint64_t cap, uint64_t *len) {
     if (!e) return FI_E_ARG;
     if (buf && cap) {
-        const uint64_t n = std::min<uint64_t>(cap - 1, e->tx_body.size());
-        memcpy(buf, e->tx_body.data(), n);
+        const uint64_t n = std::min<uint64_t>(cap - 1, e->gold.tx_body.size());
+        memcpy(buf, e->gold.tx_body.data(), n);
         buf[n] = 0;
     }
-    if (len) *len = e->tx_body.size();
+    if (len) *len = e->gold.tx_body.size();
     return FI_OK;
 }
 
@@ -2836,7 +2842,7 @@ const char *fi_debug_stat_name(uint32_t slot) {
 fi_status fi_debug_stats(fi_engine *e, uint64_t *out64) {
     if (!e || !out64) return FI_E_ARG;
     HIPCHK(hipStreamSynchronize(e->stream));
-    HIPCHK(hipMemcpy(out64, e->d_stats, kNStats * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out64, e->w.d_stats, kNStats * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return FI_OK;
 }
 
@@ -2851,7 +2857,7 @@ fi_status fi_kernel_timer_reset(fi_engine *e) {
     e->tused = 0;
     if (!e->d_span) {
         HIPCHK(hipSetDevice(e->dev));
-        HIPCHK(hipMalloc(&e->d_span, kTimerSlots * 2 * sizeof(unsigned long long)));
+        HIPCHK(e->d_span.alloc(kTimerSlots * 2));
     }
     // every slot's min starts at ~0, its max at 0 (layout: slot i at [2i, 2i + 1])
     HIPCHK(hipMemsetAsync(e->d_span, 0, kTimerSlots * 2 * sizeof(unsigned long long), e->stream));
@@ -2922,7 +2928,7 @@ fi_status fi_debug_decode(fi_engine *e, const uint32_t *raws, uint64_t n, void *
 
 fi_status fi_debug_loop_outcome(fi_engine *e, const fi_debug_loop *in, uint64_t n, fi_debug_loop_out *out) {
     if (!e || (n && (!in || !out))) return FI_E_ARG;
-    if (e->snaps.empty()) return fail(e, FI_E_STATE, "fi_debug_loop_outcome: fi_golden_run first");
+    if (e->img.snaps.empty()) return fail(e, FI_E_STATE, "fi_debug_loop_outcome: fi_golden_run first");
     if (!n) return FI_OK;
     HIPCHK(hipSetDevice(e->dev));
     DevBuf<fi_debug_loop> d_in;
