@@ -56,12 +56,17 @@ def parse(argv=None):
     ap.add_argument("--exact-memory", action="store_true",
                     help="--exact, and also cover the memory words (structure mem) by byte-liveness class "
                          "(the ctypes path)")
+    ap.add_argument("--profile", default="", metavar="FILE",
+                    help="--exact only: also attribute the space to the static instructions that consume the "
+                         "faults and write FaultCampaign.profile() to FILE as JSON (the ctypes path)")
     ap.add_argument("--num-gpus", type=int, default=1)
     ap.add_argument("--max-insts-factor", type=float, default=2.0)
     ap.add_argument("--private-pages", type=int, default=16)
     ap.add_argument("--output", default="")
     a = ap.parse_args(argv)
     a.exact = a.exact or a.exact_memory
+    if a.profile and not a.exact:
+        ap.error("--profile needs --exact")
     return a
 
 
@@ -113,7 +118,8 @@ def run_ctypes(a):
                       shadow_fu_model=a.shadow_fu_model, priority_to_shadow=a.priority_to_shadow, checkpoint=a.checkpoint,
                       issue_params={"issue_width": a.issue_width, "load_latency": a.load_latency},
                       input=a.input, executable=a.executable or None, cpu_type=a.cpu_type,
-                      tick_map=a.tick_map, tick_contract=a.tick_contract, exact_memory=a.exact_memory)
+                      tick_map=a.tick_map, tick_contract=a.tick_contract, exact_memory=a.exact_memory,
+                      profile=bool(a.profile))
     t0 = time.perf_counter()
     if a.exact:
         c.run_exact()
@@ -125,6 +131,9 @@ def run_ctypes(a):
         s.update(seconds=dt, trials_per_s=s["trials"] / dt, num_gpus=world)
         if a.exact:
             s["vulnerability"] = c.vulnerability()
+        if a.profile:
+            with open(a.profile, "w") as f:
+                json.dump(c.profile(), f, indent=1)
         print(json.dumps(s), flush=True)
     if world > 1:
         import torch.distributed as dist

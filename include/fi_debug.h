@@ -98,6 +98,14 @@ typedef struct {
  * process-start page set of the loaded workload (after fi_golden_run) --
  * the function the solo kernel calls whenever the body claims a hang. */
 fi_status fi_debug_loop_outcome(fi_engine *e, const fi_debug_loop *in, uint64_t n, fi_debug_loop_out *out);
+/* fi_exact_profile_kernel (fi_kernels.hip): the rows its per-workgroup LDS
+ * table holds; a workgroup (256 trials) that meets more adds the rest to
+ * global memory directly.  Needs no engine and no device. */
+uint32_t fi_debug_profile_slots(void);
+/* How that kernel combines adds, for A/B measurements (profiles/README.md):
+ * 0 = the default (wave-combine + LDS table), 1 = wave-combine only, 2 = one
+ * global atomic per trial.  Every variant gives the same bins. */
+fi_status fi_debug_set_profile_variant(fi_engine *e, uint32_t variant);
 #ifdef __cplusplus
 }
 #endif

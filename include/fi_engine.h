@@ -743,6 +743,61 @@ fi_status fi_exact_mem_classes(const uint64_t *ev, uint64_t n_ev, uint64_t ninst
 fi_status fi_golden_mem_index(fi_engine *e, uint64_t *addr, uint64_t addr_cap, uint32_t *off, uint64_t off_cap,
                               uint64_t *ev, uint64_t ev_cap, uint64_t counts[2]);
 
+/* ---- The profile of an exact campaign: its fault space attributed to the
+ * static instructions that consume the faults (DESIGN.md §4j "Profile").
+ *
+ * Rows: one per distinct entry of the golden trace -- every static instruction
+ * that committed and every ecall that was attempted -- ascending in pc.  raw is
+ * the 16- or 32-bit instruction word of the process-start text, len 2 or 4,
+ * ecall 1 for an ecall, execs the row's trace entries.
+ * Two tables over the trace: inst_row[t], t in [0, ninst), the row of the
+ * instruction that commits as numInst t, and ecall_row[t], t in [0, ninst], the
+ * row of the first ecall entry at numInst t (an ecall commits nothing: its
+ * entry sits at the numInst of the instruction after it), or none.
+ * The consumer of a class is the row it is charged to:
+ *  - Register r: the first-access entry ev that heads the class; its key
+ *    ev >> 1 even (an ecall) -> ecall_row[ev >> 2], else inst_row[ev >> 2], the
+ *    numInst unclipped: the exit ecall at numInst == ninst heads a class run at
+ *    inst = ninst - 1 and is still charged to the ecall.
+ *  - The pc and a result at t: inst_row[t] (for a result the instruction whose
+ *    result is flipped, also when it writes no register and the trial is
+ *    masked).
+ *  - A memory word: the index event that heads the class, at numInst u =
+ *    ev >> 16 (unclipped); recorded as a syscall's access and ecall_row[u]
+ *    exists -> that ecall, else inst_row[u] (an M5 op's reads, say).  Two
+ *    consecutive ecalls at one numInst are both charged to the first.
+ *  - Dead sites have no consumer and are in no row.
+ * Bins: counts[row][group][class], groups 0 = x1..x31 summed, 1 = the pc, 2 =
+ * memory words, 3 = an instruction's result; a trial adds its class weight to
+ * its consumer's bin (a class >= FI_N_CLASS counts as FI_ESCAPE).  Integer
+ * adds only.  Over disjoint ranges that cover [0, trials), for every group g
+ * and class c: the rows' counts[g][c] summed + (c == FI_MASKED ? g's dead
+ * sites : 0) == hist.counts summed over g's structures and all bits. */
+#define FI_N_PROFILE_GROUP 4
+typedef struct { uint64_t pc, execs; uint32_t raw; uint8_t len, ecall, pad[2]; } fi_profile_row;
+typedef struct { uint64_t counts[FI_N_PROFILE_GROUP][FI_N_CLASS]; } fi_profile_bins;
+/* Pure host function (no device, no engine), next to fi_exact_classes: the
+ * consumer of each of register reg's classes, in their order, as its entry of
+ * the golden trace (n_trace words: halfword index (pc - text_lo) / 2, bit 31 =
+ * ecall) -- the word itself, the ecall flag in bit 31.  The trace must hold
+ * ninst committing entries (else FI_E_ARG).  out, cap, n as there. */
+fi_status fi_exact_class_consumers(const uint32_t *trace, uint64_t n_trace, const uint32_t *off33, const uint32_t *ev,
+                                   uint64_t ninst, uint32_t reg, uint32_t *out, uint64_t cap, uint64_t *n);
+/* The rows of the last golden run: copies up to cap to rows (may be NULL), *n =
+ * their number.  Refusals as fi_exact_get_info. */
+fi_status fi_profile_rows(fi_engine *e, fi_profile_row *rows, uint64_t cap, uint64_t *n);
+/* The row each of exact trials [first, first + n) is charged to (what
+ * fi_exact_sites is to the run). */
+fi_status fi_exact_consumers(fi_engine *e, uint64_t first, uint64_t n, uint32_t *row);
+/* fi_run_exact plus the profile: out and hist exactly as fi_run_exact produces
+ * them; prof (prof_rows entries; prof_rows must equal fi_profile_rows' count,
+ * else FI_E_ARG) is accumulated into like hist.  The dead sites are in no
+ * row, so the call with first == 0 and n == 0 adds nothing to prof.  The
+ * tables above are built at the first of these three calls after a golden
+ * run; fi_run_exact itself builds and launches nothing for them. */
+fi_status fi_run_exact_profile(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist,
+                               fi_profile_bins *prof, uint64_t prof_rows);
+
 /* Output capture.  A trial's stdout (stderr) stream is every byte its run
  * writes to fd 1 (fd 2) from process start (or the checkpoint restore point)
  * to its end: what the serial gem5 run of that site leaves in its output

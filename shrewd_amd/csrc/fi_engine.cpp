@@ -64,6 +64,9 @@ hipError_t launch_exact_sites(const ExactPlan &p, uint64_t first, uint64_t n, co
                               uint64_t *keys, uint32_t *perm, uint32_t *weight, hipStream_t st);
 hipError_t launch_exact_hist(const fi_site *sites, const fi_outcome *out, const uint32_t *weight, uint64_t n,
                              fi_histogram *h, hipStream_t st);
+hipError_t launch_exact_profile(const ExactPlan &p, const ExactProfCtx &c, uint64_t first, uint64_t n, hipStream_t st);
+hipError_t launch_exact_consumers(const ExactPlan &p, const uint32_t *reg_cons, const uint32_t *inst_row,
+                                  uint64_t first, uint64_t n, uint32_t *row, hipStream_t st);
 hipError_t launch_exact_dead(const ExactDead &d, fi_histogram *h, hipStream_t st);
 hipError_t launch_exact_mem_live(const ExactMemCtx &c, uint8_t *live, hipStream_t st);
 hipError_t launch_exact_mem_walk(const ExactMemCtx &c, const ExactMemRow *rows, uint32_t n_rows, const uint8_t *live,
@@ -255,6 +258,8 @@ struct Image {
 // under one (bits, burst), built on the device at the first exact call that needs them (exact_mem_build)
 struct ExMem {
     bool ok = false;
+    bool cons = false;          // a profiled build: the class records carry their consumer rows
+
     uint64_t bits = 0;
     uint32_t burst = 0, n_rows = 0;
     ExactMemRow rows[kExactMaxMemRows] = {};
@@ -263,6 +268,19 @@ struct ExMem {
     double build_ms = 0;
     DevBuf<ExactMemRow> d_rows;
     DevBuf<ExactMemClass> d_cls;
+};
+
+// the profile of exact campaigns (fi_run_exact_profile, DESIGN.md §4j "Profile"): the rows of the golden
+// trace and the consumer tables, built at the first profiled call after a golden run (profile_build)
+struct ExProf {
+    bool ok = false;
+    std::vector<fi_profile_row> rows;
+    uint32_t n_ecall = 0;
+    DevBuf<uint32_t> d_inst_row;            // [ninst]: the row of the instruction that commits as numInst t
+    DevBuf<ExactEcall> d_ecall;             // (numInst, row) of the first ecall entry at a numInst, ascending
+    DevBuf<uint32_t> d_reg_cons;            // a row per register class word, beside d_ex_classes
+    DevBuf<uint32_t> d_mw_proxy;            // a bit per d_mw_ev entry (Golden::mw_proxy)
+    DevBuf<unsigned long long> d_bins;      // [rows][kProfBins]: a call's profile
 };
 
 // The translated kernels: the 64-lane, solo and solo-odd code objects.
@@ -291,6 +309,7 @@ struct Golden {
     uint64_t mw_nev = 0;             // the index's events
     DevBuf<uint64_t> d_mw_addr, d_mw_ev;
     DevBuf<uint32_t> d_mw_off;
+    std::vector<uint32_t> mw_proxy;  // a bit per event of the index: recorded as a syscall's access (kMemEvProxy)
     // first-access forwarding: per register x1..x31, the golden trace's
     // accesses in order, entry = (2 * numInst + !ecall) << 1 | reads
     DevBuf<uint32_t> d_fw_off, d_fw_ev;
@@ -304,6 +323,7 @@ struct Golden {
     uint64_t ex_dead[32] = {};
     DevBuf<uint64_t> d_ex_classes;
     ExMem xm;
+    ExProf xp;
     // load-time build of the trial kernel with the translated golden blocks
     Tx tx;
     std::shared_ptr<JitJob> jit;     // the build in flight (nullptr: none); its thread holds the job too
@@ -436,6 +456,7 @@ struct fi_engine {
     int tick_map = FI_TICK_MAP_HOST;                // fi_set_tick_map
     int tick_contract = FI_TICK_CONTRACT_NUMINST;   // fi_set_tick_contract
     bool exact_mem = false;     // fi_set_exact_memory
+    uint32_t prof_variant = 0;  // fi_debug_set_profile_variant
     // builds this engine started: a finished one is joined when a build is
     // installed (jit_install), one still running by fi_destroy
     std::vector<std::pair<std::thread, std::shared_ptr<JitJob>>> jit_threads;
@@ -1176,22 +1197,24 @@ static fi_status build_mem_index(fi_engine *e, const std::vector<MemEv> &mev, bo
             const uint64_t wd = a & ~7ULL, we = std::min(end, wd + 8);
             uint64_t bm = 0;
             for (uint64_t b = a; b < we; b++) bm |= 1ULL << (b - wd);
+            // (bit 63: the proxy flag, carried through the sort and kept out of the events)
             ent.emplace_back(wd, ((uint64_t)(ev.t & ~kMemEvProxy) << 16) | ((kind & 1) ? bm << 8 : 0) |
-                                     ((kind & 2) ? bm : 0));
+                                     ((kind & 2) ? bm : 0) | ((ev.t & kMemEvProxy) ? 1ULL << 63 : 0));
             if (ent.size() > kMaxEnt) return FI_OK;
             a = we;
         }
     }
     std::stable_sort(ent.begin(), ent.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
     std::vector<uint64_t> addr, evs;
-    std::vector<uint32_t> off;
+    std::vector<uint32_t> off, proxy(ent.size() / 32 + 1, 0);
     evs.reserve(ent.size());
     for (size_t i = 0; i < ent.size(); i++) {
         if (i == 0 || ent[i].first != ent[i - 1].first) {
             addr.push_back(ent[i].first);
             off.push_back((uint32_t)i);
         }
-        evs.push_back(ent[i].second);
+        evs.push_back(ent[i].second & ~(1ULL << 63));
+        if (ent[i].second >> 63) proxy[i >> 5] |= 1u << (i & 31);
     }
     off.push_back((uint32_t)ent.size());
     DevBuf<uint64_t> d_addr, d_ev;   // (moved in once all three are up)
@@ -1207,6 +1230,7 @@ static fi_status build_mem_index(fi_engine *e, const std::vector<MemEv> &mev, bo
     e->gold.d_mw_ev = std::move(d_ev);
     e->gold.mw_n = (uint32_t)addr.size();
     e->gold.mw_nev = evs.size();
+    e->gold.mw_proxy = std::move(proxy);
     e->gold.mem_live = true;
     return FI_OK;
 }
@@ -1861,6 +1885,8 @@ struct Chunk {
     const uint8_t *disp = nullptr;
     const fi_outcome *res = nullptr;
     const uint32_t *weight = nullptr; // an exact chunk: the sites each trial stands for (the weighted histogram)
+    const ExactPlan *prof = nullptr;  // ... of a profiled call: its plan, and the chunk's first trial
+    uint64_t prof_first = 0;
     uint32_t slot = 0;                // redo list / count / event pair
     uint64_t off = 0;                 // a capture call: the chunk's first trial (row of the caller's arrays)
     bool capture = false;             //   and its output goes to the capture buffers of `slot`
@@ -1908,7 +1934,12 @@ static fi_status chunk_end(fi_engine *e, const Chunk &ch, fi_histogram *d_hist, 
     }
     // (a redo trial is never a parked one: those end masked, not as resource escapes)
     if (ch.disp) HIPCHK(launch_tick_fix(ch.disp, ch.res, ch.k, ch.out, st));
-    if (ch.weight) HIPCHK(launch_exact_hist(ch.sites, ch.out, ch.weight, ch.k, d_hist, st));
+    if (ch.prof) {   // (an exact chunk: after its histogram)
+        const ExProf &x = e->gold.xp;
+        const ExactProfCtx c{x.d_reg_cons, x.d_inst_row, ch.out, ch.weight, x.d_bins, (uint32_t)x.rows.size(), e->prof_variant};
+        HIPCHK(launch_exact_hist(ch.sites, ch.out, ch.weight, ch.k, d_hist, st));
+        HIPCHK(launch_exact_profile(*ch.prof, c, ch.prof_first, ch.k, st));
+    } else if (ch.weight) HIPCHK(launch_exact_hist(ch.sites, ch.out, ch.weight, ch.k, d_hist, st));
     else HIPCHK(launch_hist(ch.tsites ? ch.tsites : ch.sites, ch.out, ch.k, d_hist, nullptr, st));
     if (ch.host_out) {
         if (!e->w.h_stage[ch.slot]) HIPCHK(e->w.h_stage[ch.slot].alloc(e->w.cap));
@@ -1975,6 +2006,7 @@ struct SiteSource {
     bool sampled = false;
     bool tick = false;
     const ExactPlan *exact = nullptr;
+    bool profile = false;             // ... with the profile (fi_run_exact_profile)
 };
 
 // Trials [first, first + n) or the given sites (src), in chunks of at most
@@ -2013,6 +2045,7 @@ static fi_status run_chunks(fi_engine *e, uint64_t first, const SiteSource &src,
                                    e->w.d_tk_sites[ch.slot], e->w.d_tk_disp[ch.slot], e->w.d_tk_res[ch.slot], st));
         } else if (src.exact) {
             ch.weight = e->w.d_weight[ch.slot];
+            if (src.profile) { ch.prof = src.exact; ch.prof_first = first + done; }
             HIPCHK(launch_exact_sites(*src.exact, first + done, ch.k, e->gold.d_ex_classes, ch.sites, e->w.d_keys, e->w.d_perm,
                                       e->w.d_weight[ch.slot], st));
         } else {
@@ -2131,6 +2164,77 @@ static fi_status exact_build(fi_engine *e) {
     return FI_OK;
 }
 
+fi_status fi_exact_class_consumers(const uint32_t *trace, uint64_t n_trace, const uint32_t *off33, const uint32_t *ev,
+                                   uint64_t ninst, uint32_t reg, uint32_t *out, uint64_t cap, uint64_t *n) {
+    if ((!trace && n_trace) || !off33 || (!ev && off33[32]) || reg < 1 || reg > 31 || ninst >= (1ULL << kExactInstBits))
+        return FI_E_ARG;
+    std::vector<uint32_t> inst_val;
+    std::vector<ExactEcall> ecall;
+    if (!exact_consumer_tables(trace, n_trace, nullptr, ninst, inst_val, ecall)) return FI_E_ARG;
+    const ExactConsumers c{inst_val.data(), ecall.data(), ninst, (uint32_t)ecall.size(), 0};
+    const uint64_t cnt = exact_reg_consumers(off33, ev, ninst, reg, c, out, out ? cap : 0);
+    if (n) *n = cnt;
+    return FI_OK;
+}
+
+// The process-start text's instruction word at pc (len 2 or 4), 0 where the image has no such bytes
+static uint32_t image_inst_word(const Image &img, uint64_t pc, uint32_t len) {
+    uint32_t raw = 0;
+    for (uint32_t i = 0; i < len; i++) {
+        auto it = img.pages.find((pc + i) >> 12);
+        if (it == img.pages.end()) return 0;
+        raw |= (uint32_t)it->second[(pc + i) & 4095] << (8 * i);
+    }
+    return raw;
+}
+
+// The profile's rows and consumer tables (fi_exact.h "Profile"), once per golden run, after
+// exact_build: rows and inst_row / the ecall list from the golden trace, a row per register class.
+static fi_status profile_build(fi_engine *e) {
+    Golden &g = e->gold;
+    if (g.xp.ok) return FI_OK;
+    ExProf x;
+    std::vector<uint32_t> half, row_of, inst_row;
+    std::vector<uint64_t> execs;
+    std::vector<uint8_t> is_ecall;
+    std::vector<ExactEcall> ecall;
+    exact_profile_rows(g.g_trace.data(), g.g_trace.size(), half, execs, is_ecall, row_of);
+    if (!exact_consumer_tables(g.g_trace.data(), g.g_trace.size(), row_of.data(), g.info.ninst, inst_row, ecall))
+        return fail(e, FI_E_STATE, "exact profile: the golden trace does not hold the golden run's %llu instructions",
+                    (unsigned long long)g.info.ninst);
+    if ((uint64_t)half.size() * kProfBins >= kExactNoConsumer) return fail(e, FI_E_ARG, "exact profile: too many rows");
+    x.rows.resize(half.size());
+    for (size_t r = 0; r < half.size(); r++) {
+        fi_profile_row &o = x.rows[r];
+        o = fi_profile_row{};
+        o.pc = e->img.text_lo + 2ULL * half[r];
+        o.execs = execs[r];
+        o.len = half[r] < g.g_pre.size() ? g.g_pre[half[r]].len : 0;
+        o.raw = image_inst_word(e->img, o.pc, o.len);
+        o.ecall = is_ecall[r];
+    }
+    std::vector<uint32_t> cons(g.ex_off[32]);
+    const ExactConsumers c{inst_row.data(), ecall.data(), g.info.ninst, (uint32_t)ecall.size(), 0};
+    for (uint32_t r = 1; r < 32; r++)
+        exact_reg_consumers(g.fw_off.data(), g.fw_ev.data(), g.info.ninst, r, c, cons.data() + g.ex_off[r],
+                            g.ex_off[r + 1] - g.ex_off[r]);
+    x.n_ecall = (uint32_t)ecall.size();
+    HIPCHK(x.d_inst_row.alloc(std::max<size_t>(inst_row.size(), 1)));
+    HIPCHK(x.d_ecall.alloc(std::max<size_t>(ecall.size(), 1)));
+    HIPCHK(x.d_reg_cons.alloc(std::max<size_t>(cons.size(), 1)));
+    HIPCHK(x.d_bins.alloc(std::max<size_t>(x.rows.size(), 1) * kProfBins));
+    if (!inst_row.empty()) HIPCHK(hipMemcpy(x.d_inst_row, inst_row.data(), inst_row.size() * 4, hipMemcpyHostToDevice));
+    if (!ecall.empty()) HIPCHK(hipMemcpy(x.d_ecall, ecall.data(), ecall.size() * sizeof(ExactEcall), hipMemcpyHostToDevice));
+    if (!cons.empty()) HIPCHK(hipMemcpy(x.d_reg_cons, cons.data(), cons.size() * 4, hipMemcpyHostToDevice));
+    if (g.mem_live) {
+        HIPCHK(x.d_mw_proxy.alloc(g.mw_proxy.size()));
+        HIPCHK(hipMemcpy(x.d_mw_proxy, g.mw_proxy.data(), g.mw_proxy.size() * 4, hipMemcpyHostToDevice));
+    }
+    x.ok = true;
+    g.xp = std::move(x);
+    return FI_OK;
+}
+
 // Why exact campaigns cannot cover memory words here, or NULL.  The classes
 // rest on what forwarding a memory site rests on (run_pass): a complete access
 // index and a word that stays mapped from the site's t to its next access.  The
@@ -2149,11 +2253,14 @@ static const char *exact_mem_refusal(const fi_engine *e) {
 
 // The memory classes under the campaign's (bits, burst), once per golden run
 // and pair: liveness, count, scan, emit (fi_kernels.hip), then the rows.
-static fi_status exact_mem_build(fi_engine *e) {
+// profiled (after profile_build): the emit pass also writes each class's
+// consumer row; classes built without them are built again, id for id.
+static fi_status exact_mem_build(fi_engine *e, bool profiled = false) {
 #define XMCHK(call) HIPCHK_AS("exact memory classes", call)
     ExMem &m = e->gold.xm;
     const uint64_t bits = e->bits & burst_positions(e->burst);
-    if (m.ok && m.bits == bits && m.burst == e->burst) return FI_OK;
+    if (m.ok && m.bits == bits && m.burst == e->burst && (m.cons || !profiled)) return FI_OK;
+    profiled = profiled || (m.ok && m.cons);
     m = ExMem{};   // (not ok until the end)
     m.n_rows = exact_mem_sets(bits, e->burst, m.rows);
     m.text_words = exact_mem_text_words(e->img.mem_pages.data(), e->img.mem_pages.size(), e->img.text_lo, e->img.text_hi);
@@ -2169,6 +2276,11 @@ static fi_status exact_mem_build(fi_engine *e) {
         c.mw_addr = e->gold.d_mw_addr; c.mw_ev = e->gold.d_mw_ev; c.mw_off = e->gold.d_mw_off; c.mw_n = e->gold.mw_n;
         c.pages = e->img.d_mem_pages; c.n_pages = e->img.mem_pages.size();
         c.text_lo = e->img.text_lo; c.text_hi = e->img.text_hi; c.ninst = ninst;
+        if (profiled) {
+            const ExProf &x = e->gold.xp;
+            c.cons = ExactConsumers{x.d_inst_row, x.d_ecall, ninst, x.n_ecall, 0};
+            c.proxy = x.d_mw_proxy;
+        }
         DevBuf<uint8_t> d_live, d_tmp;
         DevBuf<uint64_t> d_cnt, d_offs;
         DevBuf<unsigned long long> d_wsum;
@@ -2212,13 +2324,15 @@ static fi_status exact_mem_build(fi_engine *e) {
     HIPCHK(hipMemcpy(m.d_rows, m.rows, sizeof m.rows, hipMemcpyHostToDevice));
     m.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     m.bits = bits; m.burst = e->burst;
+    m.cons = profiled;
     m.ok = true;
     return FI_OK;
 }
 
 // The checks every exact entry point shares, then the campaign's plan, its
-// dead sites and (info, may be NULL) its sizes.
-static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, ExactDead &dd, fi_exact_info *info) {
+// dead sites and (info, may be NULL) its sizes.  profiled: the profile's tables too.
+static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, ExactDead &dd, fi_exact_info *info,
+                               bool profiled = false) {
     if (!e) return FI_E_ARG;
     if (!e->gold.have_golden) return fail(e, FI_E_STATE, "%s: golden run required", who);
     if (!e->structures) return fail(e, FI_E_STATE, "%s: fi_set_campaign first", who);
@@ -2237,7 +2351,8 @@ static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, Exac
                     "or 2^29 instructions or more)", who);
     HIPCHK(hipSetDevice(e->dev));
     fi_status s = exact_build(e);
-    if (!s && mem) s = exact_mem_build(e);
+    if (!s && profiled) s = profile_build(e);
+    if (!s && mem) s = exact_mem_build(e, profiled);
     if (s) return s;
     dd = ExactDead{};
     fi_exact_info x{};
@@ -2370,22 +2485,88 @@ fi_status fi_exact_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site *site
     return FI_OK;
 }
 
-fi_status fi_run_exact(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist) {
+// fi_run_exact (prof == NULL: nothing of the profile is built, launched or copied) and
+// fi_run_exact_profile
+static fi_status run_exact(fi_engine *e, const char *who, uint64_t first, uint64_t n, fi_outcome *out,
+                           fi_histogram *hist, fi_profile_bins *prof, uint64_t prof_rows) {
     ExactPlan p;
     ExactDead dd;
-    fi_status s = exact_prepare(e, "fi_run_exact", p, dd, nullptr);
+    fi_status s = exact_prepare(e, who, p, dd, nullptr, prof != nullptr);
     if (s) return s;
     if (first > p.trials || n > p.trials - first)
-        return fail(e, FI_E_ARG, "fi_run_exact: trials [%llu, %llu) outside the campaign's %llu", (unsigned long long)first,
+        return fail(e, FI_E_ARG, "%s: trials [%llu, %llu) outside the campaign's %llu", who, (unsigned long long)first,
                     (unsigned long long)(first + n), (unsigned long long)p.trials);
+    if (prof && prof_rows != e->gold.xp.rows.size())
+        return fail(e, FI_E_ARG, "%s: prof_rows %llu, the profile has %llu rows (fi_profile_rows)", who,
+                    (unsigned long long)prof_rows, (unsigned long long)e->gold.xp.rows.size());
     s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch));
     if (s) return s;
     HIPCHK(hipMemsetAsync(e->w.d_hist, 0, sizeof(fi_histogram), e->stream));
     if (first == 0) HIPCHK(launch_exact_dead(dd, e->w.d_hist, e->stream));   // the sites that need no trial
+    const size_t prof_bytes = prof ? prof_rows * sizeof(fi_profile_bins) : 0;
+    if (prof_bytes) HIPCHK(hipMemsetAsync(e->gold.xp.d_bins, 0, prof_bytes, e->stream));
     SiteSource src;
     src.exact = &p;
+    src.profile = prof != nullptr;
     s = run_chunks(e, first, src, n, nullptr, out, e->w.d_hist, e->stream);
-    return s ? s : run_finish(e, hist);
+    if (!s) s = run_finish(e, hist);
+    if (s || !prof_bytes) return s;
+    std::vector<fi_profile_bins> got(prof_rows);
+    HIPCHK(hipMemcpy(got.data(), e->gold.xp.d_bins, prof_bytes, hipMemcpyDeviceToHost));
+    const uint64_t *src64 = (const uint64_t *)got.data();
+    uint64_t *dst64 = (uint64_t *)prof;
+    for (size_t i = 0; i < prof_bytes / 8; i++) dst64[i] += src64[i];
+    return FI_OK;
+}
+
+fi_status fi_run_exact(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist) {
+    return run_exact(e, "fi_run_exact", first, n, out, hist, nullptr, 0);
+}
+
+fi_status fi_run_exact_profile(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist,
+                               fi_profile_bins *prof, uint64_t prof_rows) {
+    if (!prof) return e ? fail(e, FI_E_ARG, "fi_run_exact_profile: prof is NULL") : FI_E_ARG;
+    return run_exact(e, "fi_run_exact_profile", first, n, out, hist, prof, prof_rows);
+}
+
+fi_status fi_profile_rows(fi_engine *e, fi_profile_row *rows, uint64_t cap, uint64_t *n) {
+    ExactPlan p;
+    ExactDead dd;
+    fi_status s = exact_prepare(e, "fi_profile_rows", p, dd, nullptr, true);
+    if (s) return s;
+    const std::vector<fi_profile_row> &r = e->gold.xp.rows;
+    if (rows) memcpy(rows, r.data(), std::min<uint64_t>(cap, r.size()) * sizeof(fi_profile_row));
+    if (n) *n = r.size();
+    return FI_OK;
+}
+
+fi_status fi_exact_consumers(fi_engine *e, uint64_t first, uint64_t n, uint32_t *row) {
+    if (!e || (n && !row)) return FI_E_ARG;
+    ExactPlan p;
+    ExactDead dd;
+    fi_status s = exact_prepare(e, "fi_exact_consumers", p, dd, nullptr, true);
+    if (s) return s;
+    if (first > p.trials || n > p.trials - first)
+        return fail(e, FI_E_ARG, "fi_exact_consumers: trials [%llu, %llu) outside the campaign's %llu",
+                    (unsigned long long)first, (unsigned long long)(first + n), (unsigned long long)p.trials);
+    s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch));
+    if (s) return s;
+    for (uint64_t done = 0; done < n;) {   // (d_perm: a uint32 per trial of a chunk, free between runs)
+        const uint64_t k = std::min<uint64_t>(n - done, e->w.cap);
+        HIPCHK(launch_exact_consumers(p, e->gold.xp.d_reg_cons, e->gold.xp.d_inst_row, first + done, k, e->w.d_perm, e->stream));
+        HIPCHK(hipMemcpyAsync(row + done, e->w.d_perm, k * 4, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        done += k;
+    }
+    return FI_OK;
+}
+
+uint32_t fi_debug_profile_slots(void) { return kProfSlots; }
+
+fi_status fi_debug_set_profile_variant(fi_engine *e, uint32_t variant) {
+    if (!e || variant > 2) return FI_E_ARG;
+    e->prof_variant = variant;
+    return FI_OK;
 }
 
 // Output capture (the sizing and the staging copy: fi_capture.h).

@@ -17,6 +17,9 @@
 // only for t < ninst.  The pc and an instruction's result have one class of
 // weight 1 per t and no dead sites; they need no table.
 #pragma once
+#include <algorithm>
+#include <vector>
+
 #include "fi_site_draw.h"
 #include "fi_types.h"
 
@@ -32,17 +35,19 @@ FI_TM_HD inline uint64_t exact_word_inst(uint64_t w) { return w & ((1ULL << kExa
 FI_TM_HD inline uint32_t exact_word_reg(uint64_t w) { return (uint32_t)(w >> kExactInstBits) & ((1u << kExactRegBits) - 1); }
 FI_TM_HD inline uint32_t exact_word_weight(uint64_t w) { return (uint32_t)(w >> (kExactInstBits + kExactRegBits)); }
 
-// Register reg's classes in time order as packed words: out[0 .. min(count,
-// cap)) (out may be NULL); returns the count, *dead = ninst - the weights' sum.
-inline uint64_t exact_reg_classes(const uint32_t *off, const uint32_t *ev, uint64_t ninst, uint32_t reg,
-                                  uint64_t *out, uint64_t cap, uint64_t *dead) {
+// The entries that head register reg's classes, in time order: f(class number,
+// the entry, u', weight) for each; returns their count, *dead = ninst - the
+// weights' sum.
+template <typename F>
+inline uint64_t exact_reg_heads(const uint32_t *off, const uint32_t *ev, uint64_t ninst, uint32_t reg, F f,
+                                uint64_t *dead) {
     uint64_t n = 0, live = 0;
     int64_t prev = -1;
     for (uint32_t i = off[reg]; ninst && i < off[reg + 1]; i++) {
         const uint64_t t = ev[i] >> 2;
         const int64_t u = (int64_t)(t < ninst - 1 ? t : ninst - 1);
         if ((ev[i] & 1u) && u > prev) {
-            if (out && n < cap) out[n] = exact_pack((uint64_t)u, reg, (uint64_t)(u - prev));
+            f(n, ev[i], (uint64_t)u, (uint64_t)(u - prev));
             n++;
             live += (uint64_t)(u - prev);
         }
@@ -50,6 +55,113 @@ inline uint64_t exact_reg_classes(const uint32_t *off, const uint32_t *ev, uint6
     }
     if (dead) *dead = ninst - live;
     return n;
+}
+
+// Register reg's classes in time order as packed words: out[0 .. min(count,
+// cap)) (out may be NULL); returns the count, *dead = ninst - the weights' sum.
+inline uint64_t exact_reg_classes(const uint32_t *off, const uint32_t *ev, uint64_t ninst, uint32_t reg,
+                                  uint64_t *out, uint64_t cap, uint64_t *dead) {
+    return exact_reg_heads(off, ev, ninst, reg, [&](uint64_t n, uint32_t, uint64_t u, uint64_t w) {
+        if (out && n < cap) out[n] = exact_pack(u, reg, w);
+    }, dead);
+}
+
+// ---- Profile: the consumer of a class (DESIGN.md §4j "Profile").
+//
+// A class is charged to one entry of the golden trace -- a static instruction
+// that committed, or an ecall that was attempted -- named here by a value per
+// entry: the profile's row (the engine), or the trace word itself (halfword
+// index, bit 31 = ecall: fi_exact_class_consumers).  Two tables over the trace
+// (exact_consumer_tables): inst_val[t], t in [0, ninst), the value of the
+// instruction that commits as numInst t, and the ecalls as (numInst, value)
+// pairs ascending in numInst, the first ecall entry at each (an ecall commits
+// nothing: its entry sits at the numInst of the instruction after it; a second
+// ecall at the same numInst is charged to the first).
+//  - Register: the entry that heads the class, at its unclipped numInst
+//    ev >> 2: key ev >> 1 even -> that numInst's ecall, else inst_val.
+//  - The pc and an instruction's result: inst_val[t].
+//  - A memory word: the event that heads the class, at its unclipped numInst;
+//    recorded as a syscall's access (proxy) and an ecall stands at that numInst
+//    -> the ecall, else inst_val (an M5 op's proxy reads, say).
+struct ExactEcall { uint32_t t, val; };
+constexpr uint32_t kExactNoConsumer = 0xFFFFFFFFu;
+
+struct ExactConsumers {        // the two tables, the host's or the device's
+    const uint32_t *inst_val;
+    const ExactEcall *ecall;
+    uint64_t ninst;
+    uint32_t n_ecall, pad;
+};
+
+// The value of numInst t's ecall, kExactNoConsumer without one
+FI_TM_HD inline uint32_t exact_ecall_val(const ExactConsumers &c, uint64_t t) {
+    uint32_t lo = 0, hi = c.n_ecall;   // first pair with t' >= t
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (c.ecall[mid].t < t) lo = mid + 1; else hi = mid;
+    }
+    return lo < c.n_ecall && c.ecall[lo].t == t ? c.ecall[lo].val : kExactNoConsumer;
+}
+// The consumer of an access at numInst t (unclipped) made by an ecall
+// (by_ecall) or by the instruction that commits there.  (The index past the
+// last instruction is clamped: only an ecall stands there.)
+FI_TM_HD inline uint32_t exact_consumer(const ExactConsumers &c, uint64_t t, bool by_ecall) {
+    if (by_ecall) {
+        const uint32_t v = exact_ecall_val(c, t);
+        if (v != kExactNoConsumer) return v;
+    }
+    if (!c.ninst) return kExactNoConsumer;
+    return c.inst_val[t < c.ninst ? t : c.ninst - 1];
+}
+FI_TM_HD inline uint32_t exact_reg_consumer(const ExactConsumers &c, uint32_t ev) {
+    return exact_consumer(c, ev >> 2, !((ev >> 1) & 1u));
+}
+FI_TM_HD inline uint32_t exact_mem_consumer(const ExactConsumers &c, uint64_t ev, bool proxy) {
+    return exact_consumer(c, ev >> 16, proxy);
+}
+
+// Register reg's consumers, one per class in exact_reg_classes' order
+inline uint64_t exact_reg_consumers(const uint32_t *off, const uint32_t *ev, uint64_t ninst, uint32_t reg,
+                                    const ExactConsumers &c, uint32_t *out, uint64_t cap) {
+    return exact_reg_heads(off, ev, ninst, reg, [&](uint64_t n, uint32_t e, uint64_t, uint64_t) {
+        if (out && n < cap) out[n] = exact_reg_consumer(c, e);
+    }, nullptr);
+}
+
+// The tables of a trace: val[i] names entry i (NULL: the trace word itself).
+// Returns false when the trace does not hold ninst committing entries.
+inline bool exact_consumer_tables(const uint32_t *trace, uint64_t n_trace, const uint32_t *val, uint64_t ninst,
+                                  std::vector<uint32_t> &inst_val, std::vector<ExactEcall> &ecall) {
+    inst_val.clear();
+    ecall.clear();
+    for (uint64_t i = 0; i < n_trace; i++) {
+        const uint32_t v = val ? val[i] : trace[i];
+        const uint64_t t = inst_val.size();
+        if (!(trace[i] & 0x80000000u)) inst_val.push_back(v);
+        else if (ecall.empty() || ecall.back().t != t) ecall.push_back(ExactEcall{(uint32_t)t, v});
+    }
+    return inst_val.size() == ninst;
+}
+
+// The profile's rows: the distinct trace words with bit 31 cleared, ascending
+// (so ascending in pc); row_of[i] = entry i's row, execs[row] = its entries,
+// is_ecall[row] = its entries are ecalls.
+inline void exact_profile_rows(const uint32_t *trace, uint64_t n_trace, std::vector<uint32_t> &half,
+                               std::vector<uint64_t> &execs, std::vector<uint8_t> &is_ecall,
+                               std::vector<uint32_t> &row_of) {
+    half.resize(n_trace);
+    for (uint64_t i = 0; i < n_trace; i++) half[i] = trace[i] & 0x7FFFFFFFu;
+    std::sort(half.begin(), half.end());
+    half.erase(std::unique(half.begin(), half.end()), half.end());
+    execs.assign(half.size(), 0);
+    is_ecall.assign(half.size(), 0);
+    row_of.resize(n_trace);
+    for (uint64_t i = 0; i < n_trace; i++) {
+        const uint32_t r = (uint32_t)(std::lower_bound(half.begin(), half.end(), trace[i] & 0x7FFFFFFFu) - half.begin());
+        row_of[i] = r;
+        execs[r]++;
+        if (trace[i] & 0x80000000u) is_ecall[r] = 1;
+    }
 }
 
 // ---- Memory words (FI_T_MEM), by byte-liveness class.
@@ -83,7 +195,8 @@ inline uint64_t exact_reg_classes(const uint32_t *off, const uint32_t *ev, uint6
 // every site of a word the index does not list.
 struct ExactMemClass {
     uint32_t word;             // index of the word in DevCtx::mw_addr
-    uint32_t inst, weight, pad;
+    uint32_t inst, weight;
+    uint32_t cons;             // its consumer (a profiled build; else 0)
 };
 struct ExactMemRow {           // a byte set: a row of the plan with its own position count
     uint64_t first;            // its first trial, counted from the plan's mem_first
@@ -160,9 +273,13 @@ FI_TM_HD inline void exact_mem_liveness(const uint64_t *ev, uint32_t n, uint8_t 
 // The walk of one (word, byte set): its classes in time order to out[0 ..
 // min(count, cap)) (out may be NULL); returns the count, *wsum = the sum of
 // their weights (the word's other ninst - *wsum sites of the set are dead).
+// With the consumer tables (pc != NULL) and the events' proxy bits (a bit per
+// event of the whole index, this word's first at bit ev_base) each class also
+// gets its consumer.
 FI_TM_HD inline uint64_t exact_mem_walk(const uint64_t *ev, const uint8_t *live, uint32_t n, uint64_t ninst,
                                         uint32_t fmask, uint32_t word, ExactMemClass *out, uint64_t cap,
-                                        uint64_t *wsum) {
+                                        uint64_t *wsum, const ExactConsumers *pc = nullptr,
+                                        const uint32_t *proxy = nullptr, uint64_t ev_base = 0) {
     uint64_t cnt = 0, sum = 0;
     int64_t prev = -1;
     for (uint32_t i = 0; ninst && i < n; i++) {
@@ -173,7 +290,8 @@ FI_TM_HD inline uint64_t exact_mem_walk(const uint64_t *ev, const uint8_t *live,
         if (u > prev && (live[i] & fmask)) {
             if (out && cnt < cap) {
                 ExactMemClass c;
-                c.word = word; c.inst = (uint32_t)u; c.weight = (uint32_t)(u - prev); c.pad = 0;
+                c.word = word; c.inst = (uint32_t)u; c.weight = (uint32_t)(u - prev);
+                c.cons = pc ? exact_mem_consumer(*pc, e, (proxy[(ev_base + i) >> 5] >> ((ev_base + i) & 31)) & 1u) : 0;
                 out[cnt] = c;
             }
             cnt++;
@@ -281,6 +399,10 @@ struct ExactMemCtx {
     const uint64_t *pages;             // the candidate pages, sorted
     uint64_t n_pages, text_lo, text_hi, ninst;
     uint32_t mw_n, pad;
+    // a profiled build (else proxy = NULL): the consumer tables, rows as values, and the events'
+    // proxy bits (a bit per mw_ev entry: a syscall's access)
+    ExactConsumers cons;
+    const uint32_t *proxy;
 };
 
 // The dead sites of a campaign (fi_exact_dead_kernel)
@@ -300,9 +422,10 @@ FI_TM_HD inline uint64_t exact_burst_mask(uint32_t burst) { return burst == 64 ?
 
 // Memory trial j of the plan's memory range (j < p.mem_trials): the last row
 // that starts at or before j (rows ascend; a row without classes starts where
-// the next one does and is never that one), the row's own quotient, the class
-// -- shared by the row's npos consecutive trials -- and the slot's position.
-FI_TM_HD inline ExactSite exact_mem_site(const ExactPlan &p, uint64_t j) {
+// the next one does and is never that one), the row's own quotient -> the
+// class's index in the class array, shared by the row's npos consecutive
+// trials; *pos = the row's positions, *slot = the trial's among them.
+FI_TM_HD inline uint32_t exact_mem_class(const ExactPlan &p, uint64_t j, uint64_t *pos, uint32_t *slot) {
     uint32_t lo = 0, hi = p.n_mem_rows;   // first row with first > j
     while (lo < hi) {
         const uint32_t mid = (lo + hi) >> 1;
@@ -311,9 +434,15 @@ FI_TM_HD inline ExactSite exact_mem_site(const ExactPlan &p, uint64_t j) {
     const ExactMemRow r = p.mem_rows[lo - 1];
     const uint64_t jr = j - r.first;
     const uint64_t c = r.shift < 64 ? jr >> r.shift : mulhi64(jr, r.recip);
-    const ExactMemClass m = p.mem_cls[r.base + (uint32_t)c];
-    uint64_t mm = r.pos;
-    for (uint32_t s = (uint32_t)(jr - c * r.npos); s; s--) mm &= mm - 1;
+    *pos = r.pos;
+    *slot = (uint32_t)(jr - c * r.npos);
+    return r.base + (uint32_t)c;
+}
+FI_TM_HD inline ExactSite exact_mem_site(const ExactPlan &p, uint64_t j) {
+    uint64_t mm;
+    uint32_t slot;
+    const ExactMemClass m = p.mem_cls[exact_mem_class(p, j, &mm, &slot)];
+    for (uint32_t s = slot; s; s--) mm &= mm - 1;
     ExactSite x;
     x.inst = m.inst; x.target = FI_T_MEM; x.weight = m.weight;
     x.addr = p.mem_addr[m.word];
@@ -321,20 +450,29 @@ FI_TM_HD inline ExactSite exact_mem_site(const ExactPlan &p, uint64_t j) {
     return x;
 }
 
+// Trial k outside the memory range, k counted as without memory: *target = its
+// structure (0: a register) -> the class word's index (registers) or the
+// class's t (pc, result); *slot = its bit slot.
+FI_TM_HD inline uint32_t exact_class(const ExactPlan &p, uint64_t k, uint32_t *target, uint32_t *slot) {
+    const uint64_t q = exact_class_index(p, k);
+    *slot = (uint32_t)(k - q * p.nbits);
+    // the last row that starts at or before k (rows ascend; one compare per row, no indexed access)
+    uint32_t delta = p.row[0].delta, tg = p.row[0].target;
+    for (uint32_t r = 1; r < p.n_rows; r++) {
+        const bool in = p.row[r].first <= k;
+        delta = in ? p.row[r].delta : delta;
+        tg = in ? p.row[r].target : tg;
+    }
+    *target = tg;
+    return (uint32_t)q + delta;
+}
+
 // Exact trial k (k < p.trials); classes = every register's packed words
 FI_TM_HD inline ExactSite exact_site(const ExactPlan &p, const uint64_t *classes, uint64_t k) {
     if (k - p.mem_first < p.mem_trials) return exact_mem_site(p, k - p.mem_first);   // (k < mem_first wraps: no)
     if (k >= p.mem_first) k -= p.mem_trials;   // the result's trials: counted as without memory
-    const uint64_t q = exact_class_index(p, k);
-    const uint32_t slot = (uint32_t)(k - q * p.nbits);
-    // the last row that starts at or before k (rows ascend; one compare per row, no indexed access)
-    uint32_t delta = p.row[0].delta, target = p.row[0].target;
-    for (uint32_t r = 1; r < p.n_rows; r++) {
-        const bool in = p.row[r].first <= k;
-        delta = in ? p.row[r].delta : delta;
-        target = in ? p.row[r].target : target;
-    }
-    const uint32_t x = (uint32_t)q + delta;
+    uint32_t target, slot;
+    const uint32_t x = exact_class(p, k, &target, &slot);
     ExactSite s;
     s.addr = 0;
     if (target) {
@@ -351,6 +489,41 @@ FI_TM_HD inline ExactSite exact_site(const ExactPlan &p, const uint64_t *classes
     }
     s.mask = exact_burst_mask(p.burst) << b;
     return s;
+}
+
+// The profile's bins (DESIGN.md §4j "Profile"): per row FI_N_PROFILE_GROUP
+// groups x FI_N_CLASS classes; the groups: registers, the pc, memory words,
+// an instruction's result.
+constexpr uint32_t kProfBins = FI_N_PROFILE_GROUP * FI_N_CLASS;
+// fi_exact_profile_kernel's LDS table: rows per workgroup, slots a row tries
+constexpr uint32_t kProfSlots = 32, kProfProbes = 4;
+// What that kernel reads besides the plan: a chunk's outcomes and weights, the bins
+struct ExactProfCtx {
+    const uint32_t *reg_cons, *inst_row;
+    const fi_outcome *out;
+    const uint32_t *weight;
+    unsigned long long *prof;   // [n_rows][kProfBins]
+    uint32_t n_rows, variant;
+};
+FI_TM_HD inline uint32_t exact_profile_group(uint32_t target) {
+    return target == FI_T_PC ? 1u : target == FI_T_MEM ? 2u : target == FI_T_RESULT ? 3u : 0u;
+}
+// The row exact trial k is charged to and its group: reg_cons = a row per
+// register class word, beside `classes`; memory's in its class records; the pc
+// and a result at t: inst_row[t].
+FI_TM_HD inline uint32_t exact_trial_consumer(const ExactPlan &p, const uint32_t *reg_cons, const uint32_t *inst_row,
+                                              uint64_t k, uint32_t *group) {
+    if (k - p.mem_first < p.mem_trials) {
+        uint64_t pos;
+        uint32_t slot;
+        *group = 2;
+        return p.mem_cls[exact_mem_class(p, k - p.mem_first, &pos, &slot)].cons;
+    }
+    if (k >= p.mem_first) k -= p.mem_trials;
+    uint32_t target, slot;
+    const uint32_t x = exact_class(p, k, &target, &slot);
+    *group = exact_profile_group(target);
+    return target ? inst_row[x] : reg_cons[x];
 }
 
 }  // namespace fi

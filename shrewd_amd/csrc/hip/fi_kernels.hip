@@ -291,7 +291,8 @@ __global__ void __launch_bounds__(256) fi_exact_mem_live_kernel(ExactMemCtx c, u
 // One thread per (byte set = blockIdx.y, index word) walks the word's events
 // forwards (exact_mem_walk).  emit = 0: cnt[set * mw_n + word] = its classes,
 // their weights summed per byte set (in the wave first, then one atomic);
-// emit = 1: the classes to cls at the scanned counts.  A word outside the
+// emit = 1: the classes to cls at the scanned counts, each with its consumer
+// row when the build is a profiled one (c.proxy != NULL).  A word outside the
 // space (a page that is no candidate, an instruction word) has none.
 __global__ void __launch_bounds__(256) fi_exact_mem_walk_kernel(ExactMemCtx c, const ExactMemRow *rows,
                                                                 const uint8_t *live, uint64_t *cnt,
@@ -306,7 +307,7 @@ __global__ void __launch_bounds__(256) fi_exact_mem_walk_kernel(ExactMemCtx c, c
             const uint32_t a = c.mw_off[w];
             const uint64_t at = emit ? cnt[id] : 0;
             n = exact_mem_walk(c.mw_ev + a, live + a, c.mw_off[w + 1] - a, c.ninst, rows[g].fmask, w,
-                               emit ? cls + at : nullptr, emit ? ~0ULL : 0, &sum);
+                               emit ? cls + at : nullptr, emit ? ~0ULL : 0, &sum, c.proxy ? &c.cons : nullptr, c.proxy, a);
         }
         if (!emit) cnt[id] = n;
     }
@@ -374,6 +375,86 @@ __global__ void __launch_bounds__(256) fi_exact_hist_kernel(const fi_site *sites
     unsigned long long *g = (unsigned long long *)&h->counts[t0][0][0];
     for (uint32_t b = threadIdx.x; b < 64 * FI_N_CLASS; b += blockDim.x)
         if (bins[b]) atomicAdd(&g[b], bins[b]);
+}
+
+// The profile (DESIGN.md §4j "Profile"): thread i recomputes exact trial
+// first + i's class as fi_exact_sites_kernel does, takes the row the class is
+// charged to (exact_trial_consumer) and adds weight[i] to prof[row][group][cls].
+// A hot loop sends most of a campaign to a handful of rows, so the adds are
+// combined before they reach global memory:
+//  1. in the wave: equal (row, group, class) keys of consecutive lanes -- the
+//     nbits lanes of a class share the row, a loop's classes repeat it -- are
+//     summed by a segmented scan over the runs (a wave boundary cuts a run)
+//     and only a run's last lane goes on;
+//  2. in the workgroup: an LDS table of kProfSlots rows, kProfBins bins each
+//     (6 KiB + the tags: eight workgroups a CU, the 32 waves the registers
+//     allow, use 49 of its 160 KiB); a row claims a slot at row % kProfSlots
+//     or one of the next kProfProbes - 1 by compare-and-swap on the tag; a
+//     lane whose row finds none adds to global memory directly;
+//  3. the block flushes its non-zero bins with one global atomic each.
+// variant (fi_debug_set_profile_variant): 1 skips step 2, 2 skips 1 and 2.
+// Integer adds only: the bins do not depend on arrival order or the variant.
+__global__ void __launch_bounds__(256) fi_exact_profile_kernel(ExactPlan p, ExactProfCtx c, uint64_t first,
+                                                               uint64_t n) {
+    __shared__ unsigned long long bins[kProfSlots * kProfBins];
+    __shared__ uint32_t tag[kProfSlots];
+    for (uint32_t b = threadIdx.x; b < kProfSlots * kProfBins; b += blockDim.x) bins[b] = 0;
+    if (threadIdx.x < kProfSlots) tag[threadIdx.x] = kExactNoConsumer;
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t key = kExactNoConsumer;   // row * kProfBins + group * FI_N_CLASS + cls
+    uint64_t w = 0;
+    if (i < n) {
+        uint32_t group;
+        const uint32_t row = exact_trial_consumer(p, c.reg_cons, c.inst_row, first + i, &group);
+        const uint32_t cls = c.out[i].cls < FI_N_CLASS ? c.out[i].cls : (uint32_t)FI_ESCAPE;
+        if (row < c.n_rows) {   // (always: a class has a consumer)
+            key = row * kProfBins + group * FI_N_CLASS + cls;
+            w = c.weight[i];
+        }
+    }
+    bool add = key != kExactNoConsumer;
+    if (c.variant < 2) {
+        const uint32_t lane = threadIdx.x & 63;
+        const uint32_t up = __shfl_up(key, 1, 64);
+        const uint64_t heads = __ballot(lane == 0 || up != key);   // the runs' first lanes (bit 0 is set)
+        const uint32_t start = 63u - (uint32_t)__clzll(heads & (~0ULL >> (63u - lane)));
+#pragma unroll
+        for (uint32_t d = 1; d < 64; d <<= 1) {
+            const uint64_t v = (uint64_t)__shfl_up((unsigned long long)w, d, 64);
+            if (lane >= start + d) w += v;
+        }
+        add = add && (lane == 63 || ((heads >> (lane + 1)) & 1));   // the run's last lane has its sum
+    }
+    if (add) {
+        const uint32_t row = key / kProfBins, bin = key - row * kProfBins;
+        bool done = false;
+        if (c.variant == 0) {
+            uint32_t s = row & (kProfSlots - 1);
+            for (uint32_t k = 0; k < kProfProbes && !done; k++, s = (s + 1) & (kProfSlots - 1)) {
+                uint32_t old = ((volatile uint32_t *)tag)[s];   // (a tag, once set, stays)
+                if (old == kExactNoConsumer) old = atomicCAS(&tag[s], kExactNoConsumer, row);
+                if (old == kExactNoConsumer || old == row) {
+                    atomicAdd(&bins[s * kProfBins + bin], (unsigned long long)w);
+                    done = true;
+                }
+            }
+        }
+        if (!done) atomicAdd(&c.prof[key], (unsigned long long)w);
+    }
+    if (c.variant) return;   // (wave-uniform: the table is unused)
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < kProfSlots * kProfBins; b += blockDim.x)
+        if (bins[b]) atomicAdd(&c.prof[(uint64_t)tag[b / kProfBins] * kProfBins + b % kProfBins], bins[b]);
+}
+// fi_exact_consumers: the row of each of trials [first, first + n)
+__global__ void __launch_bounds__(256) fi_exact_consumers_kernel(ExactPlan p, const uint32_t *reg_cons,
+                                                                 const uint32_t *inst_row, uint64_t first, uint64_t n,
+                                                                 uint32_t *row) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    uint32_t group;
+    row[i] = exact_trial_consumer(p, reg_cons, inst_row, first + i, &group);
 }
 
 // The dead sites of an exact campaign (no trial: the golden run, masked):
@@ -643,6 +724,16 @@ hipError_t launch_exact_sites(const ExactPlan &p, uint64_t first, uint64_t n, co
 hipError_t launch_exact_hist(const fi_site *sites, const fi_outcome *out, const uint32_t *weight, uint64_t n,
                              fi_histogram *h, hipStream_t st) {
     hipLaunchKernelGGL(fi_exact_hist_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, sites, out, weight, n, h);
+    return hipGetLastError();
+}
+hipError_t launch_exact_profile(const ExactPlan &p, const ExactProfCtx &c, uint64_t first, uint64_t n, hipStream_t st) {
+    hipLaunchKernelGGL(fi_exact_profile_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, p, c, first, n);
+    return hipGetLastError();
+}
+hipError_t launch_exact_consumers(const ExactPlan &p, const uint32_t *reg_cons, const uint32_t *inst_row,
+                                  uint64_t first, uint64_t n, uint32_t *row, hipStream_t st) {
+    hipLaunchKernelGGL(fi_exact_consumers_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, p, reg_cons, inst_row, first, n,
+                       row);
     return hipGetLastError();
 }
 hipError_t launch_exact_dead(const ExactDead &d, fi_histogram *h, hipStream_t st) {

@@ -44,6 +44,10 @@ HIST_DT = np.dtype([("counts", "<u8", (N_STRUCT, 64, 6)), ("crash_sub", "<u8", (
                     ("cow_pages", "<u8"), ("device_insts", "<u8")])
 STREAM_LEN_DT = np.dtype([("out_len", "<u8"), ("err_len", "<u8")])
 EXACT_CLASS_DT = np.dtype([("inst", "<u4"), ("weight", "<u4")])   # fi_exact_class
+PROFILE_ROW_DT = np.dtype([("pc", "<u8"), ("execs", "<u8"), ("raw", "<u4"), ("len", "u1"), ("ecall", "u1"),
+                           ("pad", "u1", (2,))])                   # fi_profile_row
+N_PROFILE_GROUP = 4                                                # FI_N_PROFILE_GROUP
+PROFILE_GROUP_NAMES = ("int_reg", "pc", "mem", "result")
 
 
 class Capture:
@@ -284,6 +288,24 @@ def exact_classes(off, ev, ninst: int, reg: int):
     return out[:n.value].copy(), int(dead.value)
 
 
+def exact_class_consumers(trace, off, ev, ninst: int, reg: int) -> np.ndarray:
+    """fi_exact_class_consumers (pure host code): the consumer of each of
+    register reg's classes, in exact_classes' order, as its entry of the golden
+    trace: halfword index (pc - text_lo) / 2, bit 31 = an ecall -> uint32[]."""
+    trace = np.ascontiguousarray(trace, np.uint32)
+    off = np.ascontiguousarray(off, np.uint32)
+    ev = np.ascontiguousarray(ev, np.uint32)
+    if len(off) != 33 or int(off[32]) > len(ev):
+        raise ValueError("exact_class_consumers: off has 33 entries and off[32] <= len(ev)")
+    out = np.zeros(int(off[reg + 1]) - int(off[reg]) if 1 <= reg <= 31 else 0, np.uint32)
+    n = C.c_uint64()
+    rc = lib().fi_exact_class_consumers(trace.ctypes.data, len(trace), off.ctypes.data, ev.ctypes.data, ninst, reg,
+                                        out.ctypes.data, len(out), C.byref(n))
+    if rc != FI_OK:
+        raise EngineError(f"fi_exact_class_consumers: {rc}")
+    return out[:n.value].copy()
+
+
 def exact_mem_classes(ev, ninst: int, byte_mask: int):
     """fi_exact_mem_classes (pure host code): the byte-liveness classes of one
     memory word's events (numInst << 16 | bytes read << 8 | bytes written, in
@@ -390,6 +412,14 @@ def lib():
         L.fi_exact_get_info.argtypes = [vp, C.POINTER(ExactInfo)]
         L.fi_exact_sites.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
         L.fi_run_exact.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
+        L.fi_exact_class_consumers.argtypes = [vp, C.c_uint64, vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64,
+                                               C.POINTER(C.c_uint64)]
+        L.fi_profile_rows.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.fi_exact_consumers.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
+        L.fi_run_exact_profile.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp, C.c_uint64]
+        L.fi_debug_profile_slots.argtypes = []
+        L.fi_debug_profile_slots.restype = C.c_uint32
+        L.fi_debug_set_profile_variant.argtypes = [vp, C.c_uint32]
         L.fi_set_exact_memory.argtypes = [vp, C.c_int]
         L.fi_exact_mem_get_info.argtypes = [vp, C.POINTER(ExactMemInfo)]
         L.fi_exact_mem_classes.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, vp, C.c_uint64,
@@ -713,14 +743,43 @@ class Engine:
         self._chk(self.L.fi_exact_sites(self.h, first, n, sites.ctypes.data, w.ctypes.data), "fi_exact_sites")
         return sites, w
 
-    def run_exact(self, first: int, n: int, want_outcomes: bool = True):
+    def run_exact(self, first: int, n: int, want_outcomes: bool = True, profile: bool = False):
         """fi_run_exact: exact trials [first, first + n) -> (outcomes, weighted
-        histogram); the range that starts at 0 also counts the dead sites."""
+        histogram); the range that starts at 0 also counts the dead sites.
+        profile=True (fi_run_exact_profile) -> (outcomes, histogram, profile):
+        uint64[rows, 4, 6], the trials' weights by the row of profile_rows()
+        each is charged to, group (PROFILE_GROUP_NAMES) and outcome class."""
         out = np.zeros(n, OUTCOME_DT) if want_outcomes else None
         hist = np.zeros(1, HIST_DT)
-        self._chk(self.L.fi_run_exact(self.h, first, n, out.ctypes.data if out is not None else None,
-                                      hist.ctypes.data), "fi_run_exact")
-        return out, hist[0]
+        if not profile:
+            self._chk(self.L.fi_run_exact(self.h, first, n, out.ctypes.data if out is not None else None,
+                                          hist.ctypes.data), "fi_run_exact")
+            return out, hist[0]
+        prof = np.zeros((len(self.profile_rows()), N_PROFILE_GROUP, 6), np.uint64)
+        self._chk(self.L.fi_run_exact_profile(self.h, first, n, out.ctypes.data if out is not None else None,
+                                              hist.ctypes.data, prof.ctypes.data, len(prof)), "fi_run_exact_profile")
+        return out, hist[0], prof
+
+    def profile_rows(self) -> np.ndarray:
+        """fi_profile_rows: the static instructions (and attempted ecalls) of
+        the golden run, ascending in pc -> PROFILE_ROW_DT[rows]."""
+        n = C.c_uint64()
+        self._chk(self.L.fi_profile_rows(self.h, None, 0, C.byref(n)), "fi_profile_rows")
+        rows = np.zeros(n.value, PROFILE_ROW_DT)
+        self._chk(self.L.fi_profile_rows(self.h, rows.ctypes.data, len(rows), C.byref(n)), "fi_profile_rows")
+        return rows
+
+    def exact_consumers(self, first: int, n: int) -> np.ndarray:
+        """fi_exact_consumers: the row of profile_rows() each of exact trials
+        [first, first + n) is charged to -> uint32[n]."""
+        row = np.zeros(n, np.uint32)
+        self._chk(self.L.fi_exact_consumers(self.h, first, n, row.ctypes.data), "fi_exact_consumers")
+        return row
+
+    def debug_set_profile_variant(self, variant: int):
+        """fi_debug_set_profile_variant: how the profile kernel combines its
+        adds (0 default, 1 wave-combine only, 2 plain global atomics)."""
+        self._chk(self.L.fi_debug_set_profile_variant(self.h, variant), "fi_debug_set_profile_variant")
 
     def set_exact_memory(self, on: bool):
         """fi_set_exact_memory: exact campaigns that select memory words (33)
@@ -909,6 +968,19 @@ def shard_range(trials: int, world: int, rank: int) -> tuple[int, int]:
     return lo, hi - lo
 
 
+def allreduce_profile(prof, device=None, group=None):
+    """Sum a profile (uint64[rows, 4, 6]) over all ranks, like
+    allreduce_histogram: the rows are the same on every rank (the same
+    workload, the same golden run)."""
+    import torch
+    import torch.distributed as dist
+    t = torch.from_numpy(np.ascontiguousarray(prof, np.uint64).view(np.int64).copy())
+    if device is not None:
+        t = t.to(device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.cpu().numpy().view(np.uint64).reshape(np.shape(prof))
+
+
 def allreduce_histogram(hist, device=None, group=None):
     """Sum an outcome histogram (HIST_DT record) over all ranks: the campaign's
     only exchange.  RCCL over xGMI when `device` is a GPU and the process group
@@ -967,7 +1039,9 @@ class FaultCampaign:
     runs the sites where TimingSimpleCPU differs from a numInst flip on the
     device instead of reporting them as escape/timing,
     Engine.set_tick_contract); exact_memory (run_exact() also covers the
-    memory words, structure 33, by byte-liveness class: Engine.set_exact_memory).
+    memory words, structure 33, by byte-liveness class: Engine.set_exact_memory);
+    profile (run_exact() also attributes the space to the static instructions
+    that consume the faults: profile()).
     """
 
     def __init__(self, workload: str, cmd: Sequence[str] | None = None, env: Sequence[str] | None = None,
@@ -977,7 +1051,7 @@ class FaultCampaign:
                  shadow_fu_model: bool = False, priority_to_shadow: bool = False, issue_params: dict | None = None,
                  checkpoint: str = "", executable: str | None = None, input: str = "cin",
                  cpu_type: str = "atomic", timing_params: TimingParams | None = None, tick_map: str = "host",
-                 tick_contract: str = "numinst", exact_memory: bool = False):
+                 tick_contract: str = "numinst", exact_memory: bool = False, profile: bool = False):
         self.cpu_type = cpu_type.lower().removesuffix("simplecpu")
         if self.cpu_type not in ("atomic", "timing"):
             raise ValueError(f"cpu_type {cpu_type!r}: 'atomic' or 'timing'")
@@ -1040,6 +1114,8 @@ class FaultCampaign:
             self.engine.set_issue_model({**(issue_params or {}), "priority_to_shadow": int(priority_to_shadow)})
         self._hist = None
         self.outcomes = None
+        self.profiled = bool(profile)
+        self._prof = None
 
     # PyBindMethod("setProtectMask") analogue of setEnableShrewd (BaseO3CPU.py:69-72)
     def setProtectMask(self, mask: int):
@@ -1093,12 +1169,17 @@ class FaultCampaign:
                 rank, world = dist.get_rank(), dist.get_world_size()
         lo, cnt = shard_range(n, world, rank)
         self.first = lo
-        self.outcomes, self._hist = self.engine.run_exact(lo, cnt)
+        if self.profiled:
+            self.outcomes, self._hist, self._prof = self.engine.run_exact(lo, cnt, profile=True)
+        else:
+            self.outcomes, self._hist = self.engine.run_exact(lo, cnt)
         if world > 1:
             import torch
             import torch.distributed as dist
             dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend() == "nccl" else None
             self._hist = allreduce_histogram(self._hist, dev)
+            if self.profiled:
+                self._prof = allreduce_profile(self._prof, dev)
         if self.output:
             np.save(self.output if world == 1 else f"{self.output}.rank{rank}", self.outcomes)
         return self.outcomes
@@ -1114,6 +1195,32 @@ class FaultCampaign:
         h = self._hist["counts"]
         return {s: {CLASS_NAMES[c]: int(h[s, :, c].sum()) / (per * (words if s == 33 else 1)) for c in range(6)}
                 for s in range(1, N_STRUCT) if (sel >> s) & 1}
+
+    def profile(self, sort: str = "sdc") -> list:
+        """After run_exact() of a profile=True campaign: one dict per static
+        instruction (and attempted ecall) of the golden run that was charged
+        anything, sorted by its weight in outcome class `sort` (descending,
+        then by pc): pc, raw, inst_group (inst_group(raw): the decoder's
+        coarse opcode groups, named after what the engine does not execute
+        in them -- ordinary OP / OP-IMM instructions read "crypto" or
+        "other"), execs, ecall, counts {group: {class: weight}} over
+        PROFILE_GROUP_NAMES, and share, the same as fractions of the
+        campaign's space.  A class is charged to the instruction that first
+        consumes the fault (DESIGN.md 4j "Profile"); dead sites are in no row."""
+        if self._prof is None:
+            raise ValueError("profile(): run_exact() of a profile=True campaign first")
+        c = CLASS_NAMES.index(sort)
+        rows = self.engine.profile_rows()
+        space = int(self.engine.exact_info().space)
+        key = self._prof[:, :, c].sum(axis=1)
+        res = []
+        for r in sorted(np.flatnonzero(self._prof.sum(axis=(1, 2))).tolist(), key=lambda r: (-int(key[r]), r)):
+            cnt = {g: {CLASS_NAMES[k]: int(self._prof[r, gi, k]) for k in range(6)}
+                   for gi, g in enumerate(PROFILE_GROUP_NAMES) if self._prof[r, gi].any()}
+            res.append({"pc": int(rows["pc"][r]), "raw": int(rows["raw"][r]), "inst_group": inst_group(int(rows["raw"][r])),
+                        "execs": int(rows["execs"][r]), "ecall": int(rows["ecall"][r]), "counts": cnt,
+                        "share": {g: {k: v / space for k, v in d.items()} for g, d in cnt.items()}})
+        return res
 
     def outputs(self, trials, max_bytes: int = 4096) -> dict:
         """What the given trials printed: {trial: (outcome, stdout, stderr)},
