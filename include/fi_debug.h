@@ -52,7 +52,8 @@ fi_status fi_debug_golden_trace(fi_engine *e, void *pre_out, uint64_t pre_cap, u
 fi_status fi_debug_translate(const void *pre, uint64_t n_pre, uint64_t text_lo, const uint32_t *trace,
                              uint64_t n_trace, char *out, uint64_t cap, uint64_t *len);
 /* The same under the FI_CFG_* flags that change the generated text
- * (FI_CFG_NO_LOAD_AHEAD); flags = 0 is fi_debug_translate. */
+ * (FI_CFG_NO_LOAD_AHEAD, FI_CFG_NO_LOOP_STRETCH); flags = 0 is
+ * fi_debug_translate. */
 fi_status fi_debug_translate_flags(const void *pre, uint64_t n_pre, uint64_t text_lo, const uint32_t *trace,
                                    uint64_t n_trace, uint32_t flags, char *out, uint64_t cap, uint64_t *len);
 /* The translator's counted loops on given inputs (no device): the solo

@@ -249,6 +249,14 @@ typedef struct {
  * code-object caches are keyed by the generated text, so neither variant is
  * ever loaded for the other. */
 #define FI_CFG_NO_LOAD_AHEAD 131072u
+/* The clean solo body runs a store-free block that branches to itself in
+ * check-free stretches: on entering the block it computes how many passes fit
+ * the budget and stay inside the pages its site caches hold, and runs that
+ * many in a second copy of the body without the per-pass page, tag and budget
+ * tests (fi_translate.cpp).  This flag generates the text
+ * without stretches (A/B and parity checks; outcomes and counters are
+ * identical).  Part of the text, which keys the code-object caches. */
+#define FI_CFG_NO_LOOP_STRETCH 262144u
 
 typedef struct {
     uint64_t ninst, ncycles;

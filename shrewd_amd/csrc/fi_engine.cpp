@@ -96,7 +96,7 @@ hipError_t launch_odd_split(const uint32_t *cnt, const uint32_t *n_odd, uint32_t
 std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, const std::vector<uint32_t> &trace,
                              const std::vector<uint64_t> &extra_pcs, std::vector<uint32_t> &leaders_out,
                              uint32_t &n_insts, bool odd_streams, std::vector<LoopEst> *loops_out = nullptr,
-                             bool load_ahead = true);
+                             bool load_ahead = true, bool loop_stretch = true);
 std::vector<fi_issue_op> issue_ops_from_trace(const std::vector<PreInst> &pre, const std::vector<uint32_t> &trace);
 std::string jit_compile(const std::string &body, const char *arch, std::vector<char> &code, bool &cached, int part,
                         bool use_cache);
@@ -1457,11 +1457,12 @@ static fi_status golden_translate(fi_engine *e, GoldenCapture &g, bool live_ok) 
         std::vector<LoopEst> loops;
         uint32_t n_tx = 0;
         const bool ahead = !(e->cfg.flags & FI_CFG_NO_LOAD_AHEAD);   // (part of the text, which keys the code-object caches)
-        std::string body = translate_blocks(g.pre, e->img.text_lo, g.trace, pcs, leaders, n_tx, true, &loops, ahead);
+        const bool stretch = !(e->cfg.flags & FI_CFG_NO_LOOP_STRETCH);   // (likewise)
+        std::string body = translate_blocks(g.pre, e->img.text_lo, g.trace, pcs, leaders, n_tx, true, &loops, ahead, stretch);
         if (n_tx > 24000) {   // the odd-pc streams make it too large: without them
             leaders.clear();
             loops.clear();
-            body = translate_blocks(g.pre, e->img.text_lo, g.trace, pcs, leaders, n_tx, false, &loops, ahead);
+            body = translate_blocks(g.pre, e->img.text_lo, g.trace, pcs, leaders, n_tx, false, &loops, ahead, stretch);
         }
         if (!loops.empty() && !(e->cfg.flags & FI_CFG_NO_LOOP_ORDER)) {
             HIPCHK(e->gold.d_loops.alloc(loops.size()));
@@ -2989,7 +2990,7 @@ fi_status fi_debug_translate_flags(const void *pre, uint64_t n_pre, uint64_t tex
     std::vector<uint32_t> leaders;
     uint32_t n_tx = 0;
     const std::string body = translate_blocks(p, text_lo, t, {}, leaders, n_tx, true, nullptr,
-                                              !(flags & FI_CFG_NO_LOAD_AHEAD));
+                                              !(flags & FI_CFG_NO_LOAD_AHEAD), !(flags & FI_CFG_NO_LOOP_STRETCH));
     if (out && cap) {
         const uint64_t n = std::min<uint64_t>(cap - 1, body.size());
         memcpy(out, body.data(), n);

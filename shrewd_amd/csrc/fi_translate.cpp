@@ -367,7 +367,8 @@ struct Block {
 // takes the full solo body).
 std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, const std::vector<uint32_t> &trace,
                              const std::vector<uint64_t> &extra_pcs, std::vector<uint32_t> &leaders_out,
-                             uint32_t &n_insts, bool odd_streams, std::vector<LoopEst> *loops_out, bool load_ahead) {
+                             uint32_t &n_insts, bool odd_streams, std::vector<LoopEst> *loops_out, bool load_ahead,
+                             bool loop_stretch) {
     std::set<uint32_t> executed, leaders;
     auto valid = [&](uint32_t h) { return h < pre.size() && (pre[h].flags & kPreValid); };
     // only code the golden run executed more than once is translated: straight-
@@ -599,6 +600,7 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
     // bits at the load, the conversion -- and with it the wait for the load -- lands in the pass
     // that issues it, not in the one that uses it
     std::map<uint32_t, uint32_t> ahead_sites;
+    std::map<uint32_t, uint32_t> stretch_held;   // site caches whose stretch holds a value a pass ahead (WV_i) -> size
     n_insts = 0;
     auto hex = [](uint64_t v) {
         char b[32];
@@ -767,6 +769,16 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
     // now (ahead_at: the load's pre-decoded index -> the step).  This needs
     // none of the proof's other conditions (one exit, a counter, its steps).
     std::map<uint32_t, int> ahead_at;
+    // ---- check-free stretches (clean body).  The same kind of
+    // block -- it branches to itself by its terminating branch and holds only
+    // ALU instructions and loads -- whose every load is a walking site (at an
+    // induction register plus an immediate, kind 3 of the walk above) or a
+    // bounded site (at a register the block never writes plus an offset in
+    // static bounds, kind 1) can run K passes without any of the per-pass
+    // tests once K is known to fit the budget and the sites' cached pages:
+    // stretch_at holds the block's sites by instruction position.
+    struct StretchSite { bool walk; uint32_t reg, size; int step; int64_t off, span; };
+    std::map<uint32_t, std::map<uint32_t, StretchSite>> stretch_at;
     for (uint32_t H : S.headers) {
         std::vector<uint32_t> cyc;
         bool nested = false;
@@ -810,14 +822,40 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
             }
             if (ok && !b.term) to(text_lo + 2ULL * b.insts.back() + pre[b.insts.back()].len, false);
         }
-        if (load_ahead && ok && in.size() == 1 && !nx[H].empty()) {
+        // (one address walk of a self-loop serves the ahead loads and the stretch)
+        const bool self_loop = ok && in.size() == 1 && !nx[H].empty();
+        const RunOff self_ro = self_loop && (load_ahead || loop_stretch) ? runoff_walk(*bl[H], writes, 0) : RunOff{};
+        if (load_ahead && self_loop) {
             const Block &L = *bl[H];
-            const RunOff ro = runoff_walk(L, writes, 0);
+            const RunOff &ro = self_ro;
             for (const ProofLoad &l : ro.loads) {
                 const PreInst &p = pre[L.insts[l.pos]];
                 if (!ro.stores && l.kind == 3 && p.rs1 == l.reg && p.rd && p.rd != l.reg)
                     ahead_at[L.insts[l.pos]] = (int)(int32_t)(uint32_t)l.span;
             }
+        }
+        if (loop_stretch && self_loop) {
+            const Block &L = *bl[H];
+            const PreInst &br = pre[L.insts.back()];
+            std::string e;
+            uint32_t sz;
+            int sx;
+            const char *cond;
+            const RunOff &ro = self_ro;
+            bool fit = L.term && classify(br, e, sz, sx, cond) == C_BR &&
+                       g.pc_of(L.insts.back()) + (int64_t)br.imm == g.pc_of(H) && ro.ok && !ro.stores && !ro.loads.empty();
+            std::map<uint32_t, StretchSite> sites;
+            for (const ProofLoad &l : ro.loads) {
+                const PreInst &p = pre[L.insts[l.pos]];
+                const int64_t lim = (int64_t)1 << 20;
+                if (l.kind == 3 && p.rs1 == l.reg && l.off > -lim && l.off < lim)
+                    sites[l.pos] = {true, l.reg, l.size, (int)(int32_t)(uint32_t)l.span, l.off, 0};
+                else if (l.kind == 1 && l.reg && p.rs1 && l.off > -lim && l.off < lim && (int64_t)l.span < lim)
+                    sites[l.pos] = {false, l.reg, l.size, 0, l.off, (int64_t)l.span};
+                else
+                    fit = false;
+            }
+            if (fit) stretch_at[H] = sites;
         }
         if (!ok || n_exit != 1) continue;
         const Block &E = *bl[eblk];
@@ -1267,6 +1305,26 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
             for (const auto &kv : blk_ahead) sc.put("  HT%u = ~0ULL;\n", kv.second);
             if (!blk_ahead.empty()) sc.put("%s%u_L: ;\n", SB.c_str(), h0);
         }
+        // clean body: a stretch block whose every load has a site cache; the
+        // stretch comes back to the label S_<h>_K, below the tags' reset like
+        // the block's own back edge
+        const std::map<uint32_t, StretchSite> *stretch = nullptr;
+        std::map<uint32_t, uint32_t> st_site;   // instruction -> site cache
+        if (!oddon && !cur_odd && stretch_at.count(h0)) {
+            uint32_t ns = n_sites;
+            bool all = true;
+            for (uint32_t i = 0; i < n; i++) {
+                std::string e;
+                uint32_t sz;
+                int sx;
+                const char *cond;
+                if (classify(pre[insts[i]], e, sz, sx, cond) != C_LOAD) continue;
+                if (ns < kSiteCaches) st_site[i] = ns++;
+                else all = false;
+            }
+            if (all) stretch = &stretch_at[h0];
+        }
+        if (stretch) sc.put("%s%u_K: ;\n", SB.c_str(), h0);
         if (!cur_odd && S.headers.count(h0)) {   // a cycle header routes an entry into its cycle one level on (etgt)
             std::string rw_, rs_, rc_;
             for (uint32_t x : leaders) {
@@ -1313,6 +1371,25 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
         so_.put(" | SDIRTY(%uu, %uu)) { spc = %s; goto S_out; }\n", (uint32_t)(blo - text_lo),
                 (uint32_t)(bhi - text_lo), P0.c_str());
         if (!oddon && is_cp(h0)) sc.put("  if (SOVER(%uu)) { spc = %s; bst = 1u; goto S_out; }\n", run_len[h0], P0.c_str());
+        // the stretch's pass count: what the budget and every site's cached
+        // page allow (the sites' registers hold their values at the block's entry)
+        if (stretch) {
+            // (the entry's budget test also covers the blocks after the exit that test
+            // nothing themselves, run_len: the stretch leaves them their share)
+            if (run_len[h0] > n) sc.put("  k_ = (brem - %uu) / %uu;\n", run_len[h0] - n, n);
+            else sc.put("  k_ = brem / %uu;\n", n);
+            for (const auto &kv : *stretch) {
+                const StretchSite &t = kv.second;
+                const uint32_t site = st_site[kv.first];
+                if (t.walk)
+                    sc.put("  k_ = SMINU(k_, SWALK(%u, X%u + (uint64_t)(int64_t)%lldLL, %d, %uu, %d));\n", site, t.reg,
+                           (long long)t.off, t.step, t.size, pre[insts[kv.first]].rd ? 1 : 0);
+                else
+                    sc.put("  if (!SBOUND(%u, X%u, %lldLL, %lldLL)) k_ = 0u;\n", site, t.reg, (long long)t.off,
+                           (long long)(t.off + t.span + t.size));
+            }
+            sc.put("  if (SHOT(k_ >= 2u)) goto T_%u;\n", h0);
+        }
         uint32_t k_st = 0, k_xt = 0, k_fb = 0, k_db = 0;   // committed so far in this block
         auto commit = [&](uint32_t st, uint32_t xt, uint32_t fb, uint32_t db) {
             // per-lane counters of the running lanes (zero terms omitted), wave iterations
@@ -1372,6 +1449,13 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
                         if (S.chain.count(h0) && n_sites < kSiteCaches) {
                             const uint32_t i = n_sites++;
                             sc_site = (int)i;
+                            // (the stretch's entry test above was written for the site caches st_site
+                            // predicted: the allocation here must be the one it read through)
+                            if (stretch && st_site.at(i_inst) != i) {
+                                fprintf(stderr, "fi_translate: stretch site caches out of order at pc 0x%llx\n",
+                                        (unsigned long long)pc);
+                                abort();
+                            }
                             const std::string drop = blk_ahead.count(i_inst) ? sfmt("HT%u = ~0ULL; ", i) : std::string();
                             sc.put("  { uint8_t *p_; bool pv_; const uint64_t ea_ = %s + %s, vp_ = ea_ >> 12;\n"
                                    "    if (%s(vp_ != CV%u)) { const uint64_t e_ = tlb_find(m, vp_); if (SCOND(!e_)) %s "
@@ -1521,6 +1605,65 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
             for (size_t at = sc.out.find(from, sc_at); at != std::string::npos; at = sc.out.find(from, at + to.size()))
                 sc.out.replace(at, from.size(), to);
         }
+        // ---- the stretch: the block's body again for k_ passes, no page, tag or
+        // budget test in it (the entry showed they all pass).  A walking site
+        // that delivers a value holds the next pass's in WV_i, loaded a pass
+        // ahead; a bounded site reads through its site cache.  It is left by
+        // the block's own exit or after the last pass, the passes done committed.
+        if (stretch) {
+            sc.put("T_%u: { // stretch of pc 0x%llx, %u insts a pass\n  ks_ = k_;\n", h0, (unsigned long long)pc0, n);
+            for (const auto &kv : *stretch) {
+                const StretchSite &t = kv.second;
+                if (!t.walk || !pre[insts[kv.first]].rd) continue;
+                // (the ahead loads go through WP_i, the frame's offset plus immediate and
+                // step made opaque: seeing that this pass's ahead address is the next
+                // pass's own, the compiler loads at the top of that pass instead and
+                // waits there -- two round trips on the chain again)
+                sc.put("  WV%u = *(const g_%s *)SC_PTR(%u, X%u + (uint64_t)(int64_t)%lldLL);\n"
+                       "  WP%u = SC_BASE(%u) + (uint64_t)(int64_t)%lldLL; SOPAQUE(WP%u);\n", st_site[kv.first],
+                       gtype(t.size), st_site[kv.first], t.reg, (long long)t.off, st_site[kv.first], st_site[kv.first],
+                       (long long)pre[insts[kv.first]].imm + t.step, st_site[kv.first]);
+                stretch_held[st_site[kv.first]] = t.size;
+            }
+            sc.put("T_%u_P: ;\n", h0);
+            for (uint32_t i = 0; i < n; i++) {
+                const PreInst &p = pre[insts[i]];
+                const uint64_t pc = g.pc_of(insts[i]);
+                std::string e;
+                uint32_t sz;
+                int sx;
+                const char *cond;
+                const Cls k = classify(p, e, sz, sx, cond);
+                const std::string A = Gen::R(p.rs1), B = Gen::R(p.rs2);
+                char immb[48];
+                snprintf(immb, sizeof immb, "((uint64_t)(int64_t)%dLL)", p.imm);
+                if (k == C_ALU && p.rd) sc.put("  SX(%u, %s);\n", p.rd, subst(e, A, B, immb, hex(pc)).c_str());
+                if (k == C_LOAD && p.rd) {
+                    const StretchSite &t = stretch->at(i);
+                    const uint32_t site = st_site[i];
+                    if (t.walk)
+                        sc.put("  v_ = WV%u; WV%u = *(const g_%s *)(uintptr_t)(WP%u + %s);\n", site, site, gtype(sz), site,
+                               A.c_str());
+                    else
+                        sc.put("  v_ = *(const g_%s *)SC_PTR(%u, %s + %s);\n", gtype(sz), site, A.c_str(), immb);
+                    if (sx) sc.put("  X%u = (uint64_t)(int64_t)(int%d_t)v_;\n", p.rd, sx);
+                    else sc.put("  X%u = v_;\n", p.rd);
+                }
+                if (k == C_BR) {
+                    // (the held values stay live on both ways out: dead there, the ahead
+                    // loads are sunk below the exit branch, behind the pass's last wait)
+                    std::string keep;
+                    for (const auto &kv : *stretch)
+                        if (kv.second.walk && pre[insts[kv.first]].rd) keep += sfmt("SKEEP(WV%u); ", st_site[kv.first]);
+                    const std::string done = keep + sfmt("SADD(%uu * d_); ", k_st) + (k_xt ? sfmt("xt += %uu * d_; ", k_xt) : "") +
+                                             (k_fb ? sfmt("fb += %uu * d_; ", k_fb) : "") +
+                                             (k_db ? sfmt("db += %uu * d_; ", k_db) : "");
+                    sc.put("  k_ -= 1u;\n  if (SCOND(!(%s))) { d_ = ks_ - k_; %s%s }\n", subst(cond, A, B, immb, hex(pc)).c_str(),
+                           done.c_str(), sgo(h0, pc + p.len).c_str());
+                    sc.put("  if (SHOT(k_ != 0u)) goto T_%u_P;\n  d_ = ks_; %sgoto %s%u_K;\n}\n", h0, done.c_str(), SB.c_str(), h0);
+                }
+            }
+        }
         if (cur_odd) g.out.swap(g_keep);
     }
     if (oddon) g.out.swap(g_mode);
@@ -1539,6 +1682,8 @@ std::string translate_blocks(const std::vector<PreInst> &pre, uint64_t text_lo, 
     for (uint32_t i = 0; i < kSiteCaches; i++) sc_head += sfmt("  uint64_t CV%u, CP%u; uint32_t CQ%u;\n", i, i, i);
     for (const auto &kv : ahead_sites)
         sc_head += sfmt("  %s HV%u; uint64_t HT%u;\n", kv.second == 8 ? "uint64_t" : "uint32_t", kv.first, kv.first);
+    for (uint32_t i = 0; i < kSiteCaches; i++)
+        if (stretch_held.count(i)) sc_head += sfmt("  %s WV%u; uint64_t WP%u;\n", stretch_held[i] == 8 ? "uint64_t" : "uint32_t", i, i);
     sc_head += "S_entry:\n";
     for (uint32_t i = 0; i < kSiteCaches; i++) sc_head += sfmt("  CV%u = ~0ULL; CP%u = 0; CQ%u = 0;\n", i, i, i);
     sc_head += "  goto S_dispatch;\n";

@@ -1590,9 +1590,10 @@ typedef __attribute__((address_space(1), aligned(1))) uint64_t g_u64;
     uint8_t *p_;                                                                         \
     bool pv_, ok_, c_, chg_;                                                             \
     uint64_t v_, ea_, vp_, e_, t_, t0_, tk_, off_;                                       \
-    uint32_t cs_, mm_;                                                                   \
+    uint32_t cs_, mm_, k_, ks_, d_;                                                      \
     (void)p_; (void)pv_; (void)ok_; (void)c_; (void)chg_; (void)v_; (void)ea_; (void)vp_; \
-    (void)e_; (void)t_; (void)t0_; (void)tk_; (void)off_; (void)cs_; (void)mm_
+    (void)e_; (void)t_; (void)t0_; (void)tk_; (void)off_; (void)cs_; (void)mm_; (void)k_; \
+    (void)ks_; (void)d_
 // cycle headers: the pending-route flag as an opaque scalar (fi_translate.cpp)
 #define ETGT_OPAQUE() __asm__ volatile("" : "+s"(eon))
 
@@ -1933,6 +1934,24 @@ __device__ __noinline__ int loop_outcome(KCtx *c, const WaveMem &w, const LaneMe
 }
 
 #ifdef FI_TX
+// Check-free stretches of the clean solo body (fi_translate.cpp).
+// A walking site reads ea, ea + c, ea + 2c, ...: the number of passes whose
+// access lies wholly inside the page cv that its site cache holds (0 if ea is
+// in another page).  A site that holds the next pass's value loads once more
+// after its last pass, so it gets one pass fewer.
+__device__ __forceinline__ uint32_t tx_walk_room(uint64_t ea, uint64_t cv, int c, uint32_t size, bool held) {
+    const uint32_t off = (uint32_t)ea & 4095u;
+    if ((ea >> 12) != cv || off > 4096u - size) return 0u;
+    const uint32_t more = c > 0 ? (4096u - size - off) / (uint32_t)c : off / (uint32_t)-c;   // accesses after the first
+    return held ? more : more + 1u;
+}
+// A bounded site reads size bytes at base + [lo, end - size]: the whole range
+// lies in the page cv that its site cache holds.
+__device__ __forceinline__ bool tx_bound_fits(uint64_t base, uint64_t cv, int64_t lo, int64_t end) {
+    const int64_t off = (int64_t)(base & 4095u);
+    return (base >> 12) == cv && off + lo >= 0 && off + end <= 4096;
+}
+
 // The clean solo body (fi_translate.cpp): for a trial that rewrote no code and
 // watches no register, blocks without those checks (a store into the code
 // range leaves before itself).  Same calling convention as solo_tx_run.
@@ -1976,6 +1995,15 @@ __device__ __noinline__ void solo_tx_clean_run(KCtx *CX, lds_u64 *R, lds_mem *mp
 #define SC_SET(i, vp, e) (CV##i = (vp), CP##i = ((e) & ~1ULL) - ((vp) << 12), CQ##i = (uint32_t)(e) & 1u)
 #define SC_PTR(i, ea) ((uint8_t *)(uintptr_t)(CP##i + (ea)))
 #define SC_PRIV(i) (CQ##i != 0u)
+    // stretches: a site's passes inside its cached page, its frame's offset, an
+    // opaque scalar (fi_translate.cpp: the ahead loads' base), the hot-path hint
+#define SWALK(i, ea, c, sz, held) tx_walk_room((ea), CV##i, (c), (sz), (held) != 0)
+#define SBOUND(i, base, lo, end) tx_bound_fits((base), CV##i, (lo), (end))
+#define SC_BASE(i) (CP##i)
+#define SOPAQUE(x) __asm__ volatile("" : "+s"(x))
+#define SKEEP(x) __asm__ volatile("" : : "v"(x))
+#define SMINU(a, b) ((a) < (b) ? (a) : (b))
+#define SHOT(x) __builtin_expect(!!(x), 1)
     // every translated load through the vector memory path (shared frames are
     // read-only during a launch: either path reads the same bytes)
 #undef SPRIV

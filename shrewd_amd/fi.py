@@ -147,6 +147,7 @@ CFG_NO_HANG_PROOF = 16384
 CFG_NO_OVERFLOW = 32768
 CFG_NO_LOOP_ORDER = 65536
 CFG_NO_LOAD_AHEAD = 131072
+CFG_NO_LOOP_STRETCH = 262144
 
 
 class GoldenInfo(C.Structure):
