@@ -52,7 +52,8 @@ def parse(argv=None):
                          "instead of reporting them as escape/timing")
     ap.add_argument("--exact", action="store_true",
                     help="cover the whole fault space instead of --trials samples: one trial per first-access "
-                         "class, weighted (registers, pc, result; --cpu-type atomic; the ctypes path)")
+                         "class, weighted (registers, pc, result; the ctypes path).  --cpu-type timing: every tick "
+                         "of the TimingSimpleCPU run, one trial per class of ticks, weighted by ticks")
     ap.add_argument("--exact-memory", action="store_true",
                     help="--exact, and also cover the memory words (structure mem) by byte-liveness class "
                          "(the ctypes path)")
@@ -67,6 +68,8 @@ def parse(argv=None):
     a.exact = a.exact or a.exact_memory
     if a.profile and not a.exact:
         ap.error("--profile needs --exact")
+    if a.cpu_type == "timing" and (a.profile or a.exact_memory):
+        ap.error("--profile and --exact-memory need --cpu-type atomic (the tick domain has neither)")
     return a
 
 

@@ -806,6 +806,120 @@ fi_status fi_exact_consumers(fi_engine *e, uint64_t first, uint64_t n, uint32_t 
 fi_status fi_run_exact_profile(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist,
                                fi_profile_bins *prof, uint64_t prof_rows);
 
+/* ---- Exact campaigns in the tick domain (DESIGN.md §4j "Tick domain"): every
+ * tick of a FI_CPU_TIMING golden run covered, where fi_run_tick_trials samples.
+ *
+ * T = fi_tick_info.golden_ticks.  The space is every (t, structure, b): t < T,
+ * a selected structure among x1..x31, FI_T_PC, FI_T_RESULT (FI_T_MEM selected:
+ * FI_E_ARG, memory is not in the tick domain), b eligible as in fi_run_exact.
+ *
+ * Segments.  Attempt j of the golden run owns the ticks [done[j - 1] + 1,
+ * min(done[j], T - 1)] (from 0 for j = 0).  Inside it the map of
+ * fi_map_tick_sites tells up to three phases apart: [.., fetch_done0] when
+ * nfetch == 2, (.., exec], (exec, done].  The non-empty ones are the attempt's
+ * segments; the map is the same for every tick of a segment, so a segment's
+ * first tick stands for all of them.
+ *
+ * Classes.
+ *  - Register r: the map does not depend on the bit.  A segment that maps to a
+ *    plain numInst site at inst n (tick descriptor 0) joins the interval of
+ *    r's first-access index that n falls into -- headed by the first entry
+ *    with ev >> 2 >= n, unclipped: the exit ecall's reads stand at n == ninst.
+ *    An entry that reads and whose interval holds at least one tick is a
+ *    class: it runs at inst = ev >> 2 and its weight is the interval's ticks.
+ *    The ticks of the other intervals (headed by a write, after the last
+ *    entry) are dead; those of golden-equal segments (disposition 1) count as
+ *    dead too; those of escaped segments (disposition 2) are counted under
+ *    FI_ESCAPE / FI_ESC_TIMING with the attempt's numInst, none with a trial.
+ *    A segment whose site carries a tick descriptor (FI_TICK_CONTRACT_LITERAL)
+ *    is a class of its own, weight = its length.
+ *  - The pc: one class per segment, weight = its length; a trial whose map
+ *    says golden-equal or escape keeps its id and gets that outcome.
+ *  - An instruction's result: one class per distinct numInst of the attempts,
+ *    weight = the ticks of the attempts with that numInst.
+ * Ids: structures ascending; within a register its interval classes in time
+ * order, then its descriptor classes in segment order; within a class the
+ * eligible positions ascending.  2^40 trials or more: FI_E_ARG.
+ *
+ * Refusals: FI_E_STATE on a FI_CPU_ATOMIC engine, without a golden run or a
+ * first-access index, or when fi_tick_golden().status is not empty; FI_E_ARG
+ * with fi_set_protect / fi_set_protect_opclasses on (as fi_run_tick_sites).
+ * Both tick contracts are supported; the classes are rebuilt when the contract
+ * changes. */
+typedef struct {
+    uint64_t space;          /* T x eligible bits x selected structures */
+    uint64_t trials;         /* classes x eligible bits */
+    uint64_t segments;       /* of the golden run */
+    uint64_t dead_ticks;     /* (tick, register) pairs without a trial that count as the golden run, over the
+                                selected registers: dead intervals and golden-equal segments */
+    uint64_t escaped_ticks;  /* ... that count as FI_ESC_TIMING */
+    uint32_t nbits, pad;
+    uint64_t classes[FI_N_STRUCT];   /* per structure (0: not selected) */
+    double build_ms;         /* what building the segments and classes took (once per golden run and contract) */
+} fi_exact_tick_info;
+fi_status fi_exact_tick_get_info(fi_engine *e, fi_exact_tick_info *out);
+/* Exact tick trials [first, first + n): the site each runs (a disposition 1 /
+ * 2 pc trial: what the map left in it), its representative tick site and the
+ * ticks it stands for (representative and weights may be NULL). */
+fi_status fi_exact_tick_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site *sites, fi_tick_site *representative,
+                              uint64_t *weights);
+/* Run exact tick trials [first, first + n).  out and hist as fi_run_exact, with
+ * ticks for weights (64 bits: counts, crash_sub, escape_sub, trials and
+ * guest_insts are sums modulo 2^64); every trial is filed under its tick
+ * site's structure and first bit, as tick campaigns do.  The dead and escaped
+ * ticks are added by the call with first == 0 and by no other.  Over ranges
+ * that cover the campaign counts.sum() == hist.trials == space. */
+fi_status fi_run_exact_ticks(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist);
+/* Host side: where tick sites of the space belong.  kind[i] = FI_XT_TRIAL:
+ * trial[i] is the exact tick trial whose outcome is the site's; else the site
+ * has no trial and its outcome is the golden run's, masked (FI_XT_DEAD,
+ * FI_XT_GOLDEN) or FI_ESC_TIMING (FI_XT_ESCAPE).  A site outside the space
+ * (structure not selected, mask not an eligible position's, tick >= T): FI_E_ARG. */
+#define FI_XT_TRIAL 0
+#define FI_XT_DEAD 1
+#define FI_XT_GOLDEN 2
+#define FI_XT_ESCAPE 3
+fi_status fi_exact_tick_locate(fi_engine *e, const fi_tick_site *ts, uint64_t n, uint64_t *trial, uint8_t *kind);
+
+/* One attempt of the packed table the tick map reads (fi_exact_tick_attempts
+ * exports the golden run's).  flags: FI_TA_*; ctl: 0 none, 1 branch, 2 jal,
+ * 3 jalr, 4 auipc. */
+#define FI_TA_COMMITS 1
+#define FI_TA_ECALL 2
+#define FI_TA_PGFAULT 4
+#define FI_TA_END 8
+#define FI_TA_MACRO 16
+#define FI_TA_TAKEN 32
+typedef struct {
+    uint64_t done;               /* the tick of its last event */
+    uint64_t pc, n;              /* its pc; numInst before it */
+    uint64_t fetch_done0, exec;  /* the ticks its first fetch completes and it executes */
+    int32_t imm;                 /* branch / jal offset */
+    uint32_t g;                  /* index of the first attempt since the last commit (its own: none before it) */
+    uint8_t len, nfetch, ctl;
+    uint8_t rd, rs1, rs2, done_rd;   /* done_rd: the x register its data access's completion writes (0 none) */
+    uint8_t flags;
+} fi_tick_attempt;
+/* The golden run's attempts (copies up to cap; *n = count). */
+fi_status fi_exact_tick_attempts(fi_engine *e, fi_tick_attempt *out, uint64_t cap, uint64_t *n);
+/* Pure host function (no device, no engine), next to fi_exact_classes:
+ * register reg's classes over an attempt table (n_att attempts, golden_ticks =
+ * T) and a first-access index (off33, ev) of a golden run of ninst
+ * instructions, under tick contract `contract`.  Copies up to cap classes to
+ * out (may be NULL) in id order; a class with inst == FI_XT_MAPPED is a
+ * descriptor class (its site is the map of `tick`).  *n = their number;
+ * totals (may be NULL) = the register's ticks without a trial. */
+#define FI_XT_MAPPED 0xFFFFFFFFu
+typedef struct {
+    uint64_t weight;     /* ticks */
+    uint64_t tick;       /* a representative tick */
+    uint32_t inst, pad;  /* the numInst its trial runs at, or FI_XT_MAPPED */
+} fi_exact_tick_class;
+typedef struct { uint64_t dead, golden, escaped, esc_insts; } fi_exact_tick_totals;
+fi_status fi_exact_tick_classes(const fi_tick_attempt *att, uint64_t n_att, uint64_t golden_ticks, uint64_t ninst,
+                                int contract, const uint32_t *off33, const uint32_t *ev, uint32_t reg,
+                                fi_exact_tick_class *out, uint64_t cap, uint64_t *n, fi_exact_tick_totals *totals);
+
 /* Output capture.  A trial's stdout (stderr) stream is every byte its run
  * writes to fd 1 (fd 2) from process start (or the checkpoint restore point)
  * to its end: what the serial gem5 run of that site leaves in its output

@@ -6,11 +6,12 @@ is the host-side mirror of the gem5 FaultCampaign SimObject interface.
 """
 from .fi import (CLASS_NAMES, CRASH_NAMES, END_NAMES, ESCAPE_NAMES, HANG_NAMES, Capture, FaultCampaign, Engine,
                  EngineError, HIST_DT, OUTCOME_DT, SITE_DT, WAVE, allreduce_histogram, build_library, library_path,
-                 exact_class_consumers, exact_classes, exact_mem_classes, shard_range, structures_mask)
+                 exact_class_consumers, exact_classes, exact_mem_classes, exact_tick_classes, shard_range,
+                 structures_mask)
 
 __all__ = ["FaultCampaign", "Engine", "EngineError", "Capture", "OUTCOME_DT", "SITE_DT", "HIST_DT", "CLASS_NAMES",
            "CRASH_NAMES", "ESCAPE_NAMES", "HANG_NAMES", "END_NAMES", "allreduce_histogram", "build_library",
-           "library_path", "exact_class_consumers", "exact_classes", "exact_mem_classes", "shard_range", "structures_mask", "STAT", "WAVE"]
+           "library_path", "exact_class_consumers", "exact_classes", "exact_mem_classes", "exact_tick_classes", "shard_range", "structures_mask", "STAT", "WAVE"]
 
 
 def __getattr__(name):

@@ -29,6 +29,7 @@
 #include "fi_checkpoint.h"
 #include "fi_debug.h"
 #include "fi_exact.h"
+#include "fi_exact_tick.h"
 #include "fi_golden_host.h"
 #include "fi_site_draw.h"
 #include "fi_tick.h"
@@ -68,6 +69,12 @@ hipError_t launch_exact_profile(const ExactPlan &p, const ExactProfCtx &c, uint6
 hipError_t launch_exact_consumers(const ExactPlan &p, const uint32_t *reg_cons, const uint32_t *inst_row,
                                   uint64_t first, uint64_t n, uint32_t *row, hipStream_t st);
 hipError_t launch_exact_dead(const ExactDead &d, fi_histogram *h, hipStream_t st);
+hipError_t launch_exact_tick_sites(const ExactPlan &p, const TickMapCtx &c, uint64_t first, uint64_t n,
+                                   const ExactTickClass *cls, fi_site *sites, uint64_t *keys, uint32_t *perm,
+                                   fi_site *tsites, uint8_t *disp, fi_outcome *res, uint64_t *weight, hipStream_t st);
+hipError_t launch_exact_tick_hist(const fi_site *tsites, const fi_outcome *out, const uint64_t *weight, uint64_t n,
+                                  fi_histogram *h, hipStream_t st);
+hipError_t launch_exact_tick_dead(const ExactTickDead &d, fi_histogram *h, hipStream_t st);
 hipError_t launch_exact_mem_live(const ExactMemCtx &c, uint8_t *live, hipStream_t st);
 hipError_t launch_exact_mem_walk(const ExactMemCtx &c, const ExactMemRow *rows, uint32_t n_rows, const uint8_t *live,
                                  uint64_t *cnt, unsigned long long *wsum, ExactMemClass *cls, uint32_t emit,
@@ -283,6 +290,17 @@ struct ExProf {
     DevBuf<unsigned long long> d_bins;      // [rows][kProfBins]: a call's profile
 };
 
+// exact campaigns in the tick domain (fi_exact_tick.h, DESIGN.md §4j "Tick domain"): the segments and
+// every structure's classes under one tick contract, built at the first such call after a golden run
+// or a change of contract (exact_tick_build)
+struct ExTick {
+    bool ok = false;
+    int contract = 0;
+    double build_ms = 0;
+    ExactTickTable tab;
+    DevBuf<ExactTickClass> d_cls;
+};
+
 // The translated kernels: the 64-lane, solo and solo-odd code objects.
 struct Tx {
     Module mod[3];
@@ -324,6 +342,7 @@ struct Golden {
     DevBuf<uint64_t> d_ex_classes;
     ExMem xm;
     ExProf xp;
+    ExTick xt;
     // load-time build of the trial kernel with the translated golden blocks
     Tx tx;
     std::shared_ptr<JitJob> jit;     // the build in flight (nullptr: none); its thread holds the job too
@@ -416,6 +435,7 @@ struct Work {
     DevBuf<uint8_t> d_tk_disp[2];
     DevBuf<fi_outcome> d_tk_res[2];
     DevBuf<fi_tick_site> d_tk_in[2];
+    DevBuf<uint64_t> d_xt_weight[2];   // an exact tick chunk's weights (ensure_exact_tick_work), [cap] each
     Capture cx;
 };
 
@@ -1886,6 +1906,7 @@ struct Chunk {
     const uint8_t *disp = nullptr;
     const fi_outcome *res = nullptr;
     const uint32_t *weight = nullptr; // an exact chunk: the sites each trial stands for (the weighted histogram)
+    const uint64_t *tweight = nullptr; // an exact tick chunk: the ticks each trial stands for
     const ExactPlan *prof = nullptr;  // ... of a profiled call: its plan, and the chunk's first trial
     uint64_t prof_first = 0;
     uint32_t slot = 0;                // redo list / count / event pair
@@ -1941,6 +1962,7 @@ static fi_status chunk_end(fi_engine *e, const Chunk &ch, fi_histogram *d_hist, 
         HIPCHK(launch_exact_hist(ch.sites, ch.out, ch.weight, ch.k, d_hist, st));
         HIPCHK(launch_exact_profile(*ch.prof, c, ch.prof_first, ch.k, st));
     } else if (ch.weight) HIPCHK(launch_exact_hist(ch.sites, ch.out, ch.weight, ch.k, d_hist, st));
+    else if (ch.tweight) HIPCHK(launch_exact_tick_hist(ch.tsites, ch.out, ch.tweight, ch.k, d_hist, st));
     else HIPCHK(launch_hist(ch.tsites ? ch.tsites : ch.sites, ch.out, ch.k, d_hist, nullptr, st));
     if (ch.host_out) {
         if (!e->w.h_stage[ch.slot]) HIPCHK(e->w.h_stage[ch.slot].alloc(e->w.cap));
@@ -2008,6 +2030,8 @@ struct SiteSource {
     bool tick = false;
     const ExactPlan *exact = nullptr;
     bool profile = false;             // ... with the profile (fi_run_exact_profile)
+    // ... of a tick campaign (fi_run_exact_ticks; with tick and exact set): the class records
+    const ExactTickClass *tick_cls = nullptr;
 };
 
 // Trials [first, first + n) or the given sites (src), in chunks of at most
@@ -2034,6 +2058,12 @@ static fi_status run_chunks(fi_engine *e, uint64_t first, const SiteSource &src,
         if (src.sites) {
             HIPCHK(hipMemcpyAsync(ch.sites, src.sites + done, ch.k * sizeof(fi_site), hipMemcpyHostToDevice, st));
             HIPCHK(launch_keys(ch.sites, ch.k, e->w.d_keys, e->w.d_perm, st));
+        } else if (src.tick_cls) {   // exact tick trials: parked and fixed as mapped tick sites are
+            ch.tsites = e->w.d_tk_sites[ch.slot]; ch.disp = e->w.d_tk_disp[ch.slot]; ch.res = e->w.d_tk_res[ch.slot];
+            ch.tweight = e->w.d_xt_weight[ch.slot];
+            HIPCHK(launch_exact_tick_sites(*src.exact, tick_map_ctx(e, 0, nullptr), first + done, ch.k, src.tick_cls, ch.sites,
+                                           e->w.d_keys, e->w.d_perm, e->w.d_tk_sites[ch.slot], e->w.d_tk_disp[ch.slot],
+                                           e->w.d_tk_res[ch.slot], e->w.d_xt_weight[ch.slot], st));
         } else if (src.tick) {   // tick sites: the mapper takes the sampler's place
             ch.tsites = e->w.d_tk_sites[ch.slot]; ch.disp = e->w.d_tk_disp[ch.slot]; ch.res = e->w.d_tk_res[ch.slot];
             const fi_tick_site *in = nullptr;
@@ -2873,6 +2903,227 @@ fi_status fi_run_tick_trials(fi_engine *e, uint64_t first, uint64_t n, fi_outcom
     fi_status st = fi_sample_tick_sites(e, first, n, ts.data());
     if (st) return st;
     return fi_run_tick_sites(e, ts.data(), n, out, hist);
+}
+
+// ---- Exact campaigns in the tick domain (DESIGN.md §4j "Tick domain"; the segments, the classes and the
+// trial ids: fi_exact_tick.h)
+static std::vector<TickRec> tick_recs(const fi_tick_attempt *att, uint64_t n, std::vector<uint64_t> &done) {
+    std::vector<TickRec> rec(n);
+    done.resize(n);
+    for (uint64_t i = 0; i < n; i++) {
+        const fi_tick_attempt &a = att[i];
+        done[i] = a.done;
+        TickRec r{};
+        r.pc = a.pc; r.n = a.n; r.fetch_done0 = a.fetch_done0; r.exec = a.exec; r.imm = a.imm; r.g = a.g;
+        r.len = a.len; r.nfetch = a.nfetch; r.ctl = a.ctl; r.rd = a.rd; r.rs1 = a.rs1; r.rs2 = a.rs2;
+        r.done_rd = a.done_rd; r.flags = a.flags;
+        rec[i] = r;
+    }
+    return rec;
+}
+static_assert(FI_TA_COMMITS == kTrCommits && FI_TA_ECALL == kTrEcall && FI_TA_PGFAULT == kTrPgfault &&
+              FI_TA_END == kTrEnd && FI_TA_MACRO == kTrMacro && FI_TA_TAKEN == kTrTaken, "fi_tick_attempt.flags");
+static_assert(FI_XT_MAPPED == kExactTickMapped && FI_XT_TRIAL == kXtTrial && FI_XT_DEAD == kXtDeadTick &&
+              FI_XT_GOLDEN == kXtGoldenTick && FI_XT_ESCAPE == kXtEscapeTick, "fi_exact_tick_* constants");
+
+fi_status fi_exact_tick_classes(const fi_tick_attempt *att, uint64_t n_att, uint64_t golden_ticks, uint64_t ninst,
+                                int contract, const uint32_t *off33, const uint32_t *ev, uint32_t reg,
+                                fi_exact_tick_class *out, uint64_t cap, uint64_t *n, fi_exact_tick_totals *totals) {
+    if (!att || !n_att || !golden_ticks || !off33 || (!ev && off33[32]) || reg < 1 || reg > 31 ||
+        ninst >= (1ULL << kExactInstBits) || n_att >= (1ULL << 30) ||
+        (contract != FI_TICK_CONTRACT_NUMINST && contract != FI_TICK_CONTRACT_LITERAL))
+        return FI_E_ARG;
+    for (uint64_t i = 0; i < n_att; i++)
+        if (att[i].g > i || (i && att[i].done < att[i - 1].done)) return FI_E_ARG;
+    std::vector<uint64_t> done;
+    const std::vector<TickRec> rec = tick_recs(att, n_att, done);
+    std::vector<TickSeg> segs;
+    std::vector<uint32_t> seg_off;
+    exact_tick_segments(done.data(), rec.data(), n_att, golden_ticks, segs, seg_off);
+    std::vector<ExactTickClass> cls;
+    ExactTickTotals t{};
+    exact_tick_reg_classes(done.data(), rec.data(), n_att, ninst, contract == FI_TICK_CONTRACT_LITERAL ? 1u : 0u,
+                           segs.data(), segs.size(), off33, ev, reg, cls, nullptr, nullptr, &t);
+    for (size_t i = 0; out && i < cls.size() && i < cap; i++) out[i] = fi_exact_tick_class{cls[i].weight, cls[i].tick, cls[i].inst, 0};
+    if (n) *n = cls.size();
+    if (totals) *totals = fi_exact_tick_totals{t.dead, t.golden, t.escaped, t.esc_insts};
+    return FI_OK;
+}
+
+fi_status fi_exact_tick_attempts(fi_engine *e, fi_tick_attempt *out, uint64_t cap, uint64_t *n) {
+    if (!e) return FI_E_ARG;
+    fi_status s = tick_ready(e);
+    if (s) return s;
+    const Golden &g = e->gold;
+    for (uint64_t i = 0; out && i < cap && i < g.tk_rec.size(); i++) {
+        const TickRec &r = g.tk_rec[i];
+        out[i] = fi_tick_attempt{g.tk_done[i], r.pc, r.n, r.fetch_done0, r.exec, r.imm, r.g, r.len, r.nfetch, r.ctl,
+                                 r.rd, r.rs1, r.rs2, r.done_rd, r.flags};
+    }
+    if (n) *n = g.tk_rec.size();
+    return FI_OK;
+}
+
+// The segments and classes of the golden run under the engine's tick contract, on the host; the
+// class records uploaded for fi_exact_tick_sites_kernel.
+static fi_status exact_tick_build(fi_engine *e) {
+    Golden &g = e->gold;
+    if (g.xt.ok && g.xt.contract == e->tick_contract) return FI_OK;
+    g.xt = ExTick{};
+    const auto t0 = std::chrono::steady_clock::now();
+    exact_tick_table(g.tk_done.data(), g.tk_rec.data(), g.tk_done.size(), g.info.ninst, g.t_stats.ticks,
+                     e->tick_contract == FI_TICK_CONTRACT_LITERAL ? 1u : 0u, g.fw_off.data(), g.fw_ev.data(), g.xt.tab);
+    DevBuf<ExactTickClass> d_cls;
+    const std::vector<ExactTickClass> &cls = g.xt.tab.cls;
+    HIPCHK(d_cls.alloc(std::max<size_t>(cls.size(), 1)));
+    if (!cls.empty()) HIPCHK(hipMemcpy(d_cls, cls.data(), cls.size() * sizeof(ExactTickClass), hipMemcpyHostToDevice));
+    g.xt.d_cls = std::move(d_cls);
+    g.xt.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    g.xt.contract = e->tick_contract;
+    g.xt.ok = true;
+    return FI_OK;
+}
+
+// The checks every exact tick entry point shares, then the plan, the ticks without a trial and
+// (info, may be NULL) the sizes.  run: a call that runs trials (fi_set_protect* must be off).
+static fi_status exact_tick_prepare(fi_engine *e, const char *who, bool run, ExactPlan &p, ExactTickDead &dd,
+                                    fi_exact_tick_info *info) {
+    if (!e) return FI_E_ARG;
+    if (!e->gold.have_golden) return fail(e, FI_E_STATE, "%s: golden run required", who);
+    if (e->cpu_model != FI_CPU_TIMING)
+        return fail(e, FI_E_STATE, "%s: exact tick campaigns need the TimingSimpleCPU model (fi_set_cpu_model)", who);
+    if (!e->gold.t_status.empty()) return fail(e, FI_E_STATE, "%s: tick model: %s", who, e->gold.t_status.c_str());
+    if (!e->gold.fw_ok)
+        return fail(e, FI_E_STATE, "%s: the golden run has no first-access index (a golden trace that is incomplete "
+                    "or 2^29 instructions or more)", who);
+    if (!e->structures) return fail(e, FI_E_STATE, "%s: fi_set_campaign first", who);
+    if (e->structures & (1ULL << FI_T_MEM)) return fail(e, FI_E_ARG, "%s: memory words are not in the tick domain", who);
+    if (run && (e->protect || e->protect_opc))
+        return fail(e, FI_E_ARG, "%s: selective replication (fi_set_protect*) is not supported", who);
+    if (e->gold.tk_done.empty() || !e->gold.t_stats.ticks) return fail(e, FI_E_STATE, "%s: tick model: no attempts", who);
+    HIPCHK(hipSetDevice(e->dev));
+    fi_status s = exact_tick_build(e);
+    if (s) return s;
+    const ExTick &x = e->gold.xt;
+    fi_exact_tick_info o{};
+    p = exact_tick_plan(e->structures, x.tab.off, e->bits, e->burst, o.classes);
+    dd = ExactTickDead{};
+    dd.bits = p.bits;
+    const uint64_t T = e->gold.t_stats.ticks;
+    for (uint32_t t = 1; t < FI_N_STRUCT; t++) {
+        if (!((e->structures >> t) & 1)) continue;
+        o.space += T * p.nbits;
+        if (t >= 32) continue;
+        const ExactTickTotals &r = x.tab.tot[t];
+        dd.masked[t] = r.dead + r.golden;
+        dd.escaped[t] = r.escaped;
+        o.dead_ticks += r.dead + r.golden;
+        o.escaped_ticks += r.escaped;
+        dd.insts += ((r.dead + r.golden) * e->gold.info.ninst + r.esc_insts) * p.nbits;
+    }
+    dd.total = (o.dead_ticks + o.escaped_ticks) * p.nbits;
+    dd.esc_total = o.escaped_ticks * p.nbits;
+    o.trials = p.trials;
+    o.segments = x.tab.segs.size();
+    o.nbits = p.nbits;
+    o.build_ms = x.build_ms;
+    if (p.trials >= kExactMaxTrials) return fail(e, FI_E_ARG, "%s: 2^40 exact trials or more", who);
+    if (info) *info = o;
+    return FI_OK;
+}
+
+static fi_status ensure_exact_tick_work(fi_engine *e, uint64_t n) {
+    fi_status s = tick_device_prepare(e, n);
+    if (s) return s;
+    for (int i = 0; i < 2; i++)
+        if (!e->w.d_xt_weight[i]) HIPCHK(e->w.d_xt_weight[i].alloc(e->w.cap));
+    return FI_OK;
+}
+
+fi_status fi_exact_tick_get_info(fi_engine *e, fi_exact_tick_info *out) {
+    if (!e || !out) return FI_E_ARG;
+    ExactPlan p;
+    ExactTickDead dd;
+    return exact_tick_prepare(e, "fi_exact_tick_get_info", false, p, dd, out);
+}
+
+fi_status fi_exact_tick_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site *sites, fi_tick_site *representative,
+                              uint64_t *weights) {
+    if (!e || (n && !sites)) return FI_E_ARG;
+    ExactPlan p;
+    ExactTickDead dd;
+    fi_status s = exact_tick_prepare(e, "fi_exact_tick_sites", false, p, dd, nullptr);
+    if (s) return s;
+    if (first > p.trials || n > p.trials - first)
+        return fail(e, FI_E_ARG, "fi_exact_tick_sites: trials [%llu, %llu) outside the campaign's %llu", (unsigned long long)first,
+                    (unsigned long long)(first + n), (unsigned long long)p.trials);
+    if (!n) return FI_OK;
+    if ((s = ensure_exact_tick_work(e, n))) return s;
+    std::vector<fi_site> tsv(representative ? std::min<uint64_t>(n, e->w.cap) : 0);
+    for (uint64_t done = 0; done < n;) {
+        const uint64_t k = std::min<uint64_t>(n - done, e->w.cap);
+        HIPCHK(launch_exact_tick_sites(p, tick_map_ctx(e, 0, nullptr), first + done, k, e->gold.xt.d_cls, e->w.d_sites,
+                                       e->w.d_keys, e->w.d_perm, e->w.d_tk_sites[0], e->w.d_tk_disp[0], e->w.d_tk_res[0],
+                                       e->w.d_xt_weight[0], e->stream));
+        HIPCHK(hipMemcpyAsync(sites + done, e->w.d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        if (weights) HIPCHK(hipMemcpyAsync(weights + done, e->w.d_xt_weight[0], k * 8, hipMemcpyDeviceToHost, e->stream));
+        if (representative)
+            HIPCHK(hipMemcpyAsync(tsv.data(), e->w.d_tk_sites[0], k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipStreamSynchronize(e->stream));
+        for (uint64_t i = 0; representative && i < k; i++)
+            representative[done + i] = fi_tick_site{tsv[i].inst, tsv[i].mask, tsv[i].target, tsv[i].trial};
+        done += k;
+    }
+    return FI_OK;
+}
+
+fi_status fi_run_exact_ticks(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist) {
+    ExactPlan p;
+    ExactTickDead dd;
+    fi_status s = exact_tick_prepare(e, "fi_run_exact_ticks", true, p, dd, nullptr);
+    if (s) return s;
+    if (first > p.trials || n > p.trials - first)
+        return fail(e, FI_E_ARG, "fi_run_exact_ticks: trials [%llu, %llu) outside the campaign's %llu", (unsigned long long)first,
+                    (unsigned long long)(first + n), (unsigned long long)p.trials);
+    if ((s = ensure_exact_tick_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch)))) return s;
+    HIPCHK(hipMemsetAsync(e->w.d_hist, 0, sizeof(fi_histogram), e->stream));
+    if (first == 0) HIPCHK(launch_exact_tick_dead(dd, e->w.d_hist, e->stream));   // the ticks that need no trial
+    SiteSource src;
+    src.tick = true;
+    src.exact = &p;
+    src.tick_cls = e->gold.xt.d_cls;
+    s = run_chunks(e, first, src, n, nullptr, out, e->w.d_hist, e->stream);
+    return s ? s : run_finish(e, hist);
+}
+
+fi_status fi_exact_tick_locate(fi_engine *e, const fi_tick_site *ts, uint64_t n, uint64_t *trial, uint8_t *kind) {
+    if (!e || (n && (!ts || !trial || !kind))) return FI_E_ARG;
+    ExactPlan p;
+    ExactTickDead dd;
+    fi_status s = exact_tick_prepare(e, "fi_exact_tick_locate", false, p, dd, nullptr);
+    if (s) return s;
+    const Golden &g = e->gold;
+    const ExactTickTable &x = g.xt.tab;
+    uint64_t row_first[FI_N_STRUCT] = {};   // per selected structure: its first trial
+    for (uint32_t t = 1, r = 0; t < FI_N_STRUCT; t++)
+        if (((e->structures >> t) & 1)) row_first[t] = p.row[r++].first;
+    const uint32_t literal = e->tick_contract == FI_TICK_CONTRACT_LITERAL ? 1u : 0u;
+    for (uint64_t i = 0; i < n; i++) {
+        const fi_tick_site &t = ts[i];
+        const bool target_ok = t.target >= 1 && t.target < FI_N_STRUCT && ((e->structures >> t.target) & 1);
+        const uint32_t b = t.mask ? (uint32_t)__builtin_ctzll(t.mask) : 0;
+        if (!target_ok || !t.mask || !((p.bits >> b) & 1) || t.mask != exact_burst_mask(p.burst) << b ||
+            t.tick >= g.t_stats.ticks)
+            return fail(e, FI_E_ARG, "fi_exact_tick_locate: site %llu (target %u, mask %llx, tick %llu) is outside the "
+                        "campaign's space", (unsigned long long)i, t.target, (unsigned long long)t.mask,
+                        (unsigned long long)t.tick);
+        uint32_t c = 0;
+        kind[i] = exact_tick_locate(x, g.tk_done.data(), g.tk_rec.data(), g.tk_done.size(), g.info.ninst, g.t_stats.ticks,
+                                    literal, g.fw_off.data(), g.fw_ev.data(), t.tick, t.target, t.mask, &c);
+        const uint64_t slot = (uint64_t)__builtin_popcountll(p.bits & ((1ULL << b) - 1));
+        trial[i] = kind[i] == kXtTrial ? row_first[t.target] + (uint64_t)c * p.nbits + slot : 0;
+    }
+    return FI_OK;
 }
 
 fi_status fi_run_trials_device(fi_engine *e, uint64_t first, uint64_t n, void *d_out, void *d_hist, void *stream) {

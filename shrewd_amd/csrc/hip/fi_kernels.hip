@@ -6,6 +6,8 @@
 //   fi_hist_kernel      outcome histogram (structure x first-bit x class)
 //   fi_exact_*_kernel   exact campaigns: sites by first-access class, the weighted histogram, the dead sites,
 //                       the memory words' byte-liveness classes
+//   fi_exact_tick_*     exact campaigns in the tick domain: sites by class record, the histogram with 64-bit
+//                       weights, the ticks without a trial
 //   hipcub radix sort   trials by inject time, so a wave's 64 lanes share the
 //                       golden prefix and start at the same snapshot
 //
@@ -17,6 +19,7 @@
 #include "fi_site_draw.h"
 #include "fi_tick_map.h"
 #include "fi_exact.h"
+#include "fi_exact_tick.h"
 #include "fi_device.h"
 #include "rv64_isa.h"
 #include "fi_softfp.h"
@@ -472,6 +475,101 @@ __global__ void __launch_bounds__(64) fi_exact_dead_kernel(ExactDead d, fi_histo
     }
 }
 
+// ------------------------------------------------------------------ exact campaigns, tick domain
+// fi_exact_sites_kernel's counterpart over the tick classes (fi_exact_tick.h
+// exact_tick_site): thread i takes exact tick trial first + i -- the class
+// record shared by the nbits consecutive lanes of a class; an interval class
+// is a plain site, every other one goes through tick_map_site -- and writes
+// what fi_tick_map_kernel writes (the site, the tick site in fi_site layout,
+// disp, a disp 1 / 2 trial's outcome) plus the ticks the trial stands for.
+__global__ void __launch_bounds__(256) fi_exact_tick_sites_kernel(ExactPlan p, TickMapCtx c, uint64_t first, uint64_t n,
+                                                                  const ExactTickClass *cls, fi_site *sites,
+                                                                  uint64_t *keys, uint32_t *perm, fi_site *tsites,
+                                                                  uint8_t *disp, fi_outcome *res, uint64_t *weight) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ExactTickSite x = exact_tick_site(p, cls, c, first + i);
+    fi_site t;   // inst = the tick
+    t.inst = x.tsite.tick; t.mask = x.tsite.mask; t.addr = 0; t.target = x.tsite.target; t.trial = x.tsite.trial;
+    sites[i] = x.site;
+    keys[i] = x.site.inst;
+    perm[i] = (uint32_t)i;
+    tsites[i] = t;
+    disp[i] = (uint8_t)x.disp;
+    res[i] = x.res;
+    weight[i] = x.weight;
+}
+
+// fi_exact_hist_kernel with 64-bit weights (tick counts pass 2^32), keyed by
+// the tick sites: the same LDS table of the block's first structure, the same
+// wave sums; every product and sum is modulo 2^64.
+__global__ void __launch_bounds__(256) fi_exact_tick_hist_kernel(const fi_site *tsites, const fi_outcome *out,
+                                                                 const uint64_t *weight, uint64_t n, fi_histogram *h) {
+    __shared__ unsigned long long bins[64 * FI_N_CLASS];
+    for (uint32_t b = threadIdx.x; b < 64 * FI_N_CLASS; b += blockDim.x) bins[b] = 0;
+    // (the grid covers n: the block's first trial exists; every lane reads the same word)
+    uint32_t t0 = tsites[(uint64_t)blockIdx.x * blockDim.x].target;
+    t0 = t0 < FI_N_STRUCT ? t0 : 0;
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t cls = FI_N_CLASS, sub = 0;
+    uint64_t w = 0, wi = 0;
+    if (i < n) {
+        const fi_site s = tsites[i];
+        const fi_outcome o = out[i];
+        const uint32_t t = s.target < FI_N_STRUCT ? s.target : 0;
+        const uint32_t bit = s.mask ? (uint32_t)__builtin_ctzll(s.mask) : 0;
+        cls = o.cls < FI_N_CLASS ? o.cls : FI_ESCAPE;
+        sub = o.sub;
+        w = weight[i];
+        wi = w * o.ninst;
+        if (t == t0) atomicAdd(&bins[bit * FI_N_CLASS + cls], (unsigned long long)w);
+        else atomicAdd((unsigned long long *)&h->counts[t][bit][cls], (unsigned long long)w);
+    }
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t crash = __ballot(cls == FI_CRASH), esc = __ballot(cls == FI_ESCAPE);
+    if (crash) {
+        for (uint32_t k = 0; k < 16; k++) {
+            if (!(crash & __ballot((sub & 15) == k))) continue;   // (wave-uniform)
+            const uint64_t c = wave_sum64(cls == FI_CRASH && (sub & 15) == k ? w : 0);
+            if (c && lane == 0) atomicAdd((unsigned long long *)&h->crash_sub[k], (unsigned long long)c);
+        }
+    }
+    if (esc) {
+        for (uint32_t k = 0; k < 8; k++) {
+            if (!(esc & __ballot((sub & 7) == k))) continue;
+            const uint64_t c = wave_sum64(cls == FI_ESCAPE && (sub & 7) == k ? w : 0);
+            if (c && lane == 0) atomicAdd((unsigned long long *)&h->escape_sub[k], (unsigned long long)c);
+        }
+    }
+    const uint64_t nt = wave_sum64(w), ni = wave_sum64(wi);
+    if (lane == 0 && (nt | ni)) {
+        atomicAdd((unsigned long long *)&h->trials, (unsigned long long)nt);
+        atomicAdd((unsigned long long *)&h->guest_insts, (unsigned long long)ni);
+    }
+    __syncthreads();
+    unsigned long long *g = (unsigned long long *)&h->counts[t0][0][0];
+    for (uint32_t b = threadIdx.x; b < 64 * FI_N_CLASS; b += blockDim.x)
+        if (bins[b]) atomicAdd(&g[b], bins[b]);
+}
+
+// The ticks of an exact tick campaign that need no trial: block r, thread b
+// adds register r's masked ticks (dead, golden-equal) to counts[r][b][FI_MASKED]
+// and its escaped ones to counts[r][b][FI_ESCAPE] for every eligible b; the
+// totals by one thread.
+__global__ void __launch_bounds__(64) fi_exact_tick_dead_kernel(ExactTickDead d, fi_histogram *h) {
+    const uint32_t r = blockIdx.x, b = threadIdx.x;
+    if ((d.bits >> b) & 1) {
+        if (d.masked[r]) atomicAdd((unsigned long long *)&h->counts[r][b][FI_MASKED], (unsigned long long)d.masked[r]);
+        if (d.escaped[r]) atomicAdd((unsigned long long *)&h->counts[r][b][FI_ESCAPE], (unsigned long long)d.escaped[r]);
+    }
+    if (r == 0 && b == 0 && d.total) {
+        atomicAdd((unsigned long long *)&h->trials, (unsigned long long)d.total);
+        atomicAdd((unsigned long long *)&h->guest_insts, (unsigned long long)d.insts);
+        if (d.esc_total) atomicAdd((unsigned long long *)&h->escape_sub[FI_ESC_TIMING], (unsigned long long)d.esc_total);
+    }
+}
+
 // Epochs: sort keys of the suspended lanes (their pc: lanes of one loop end
 // up in the same wave); entries past the survivor count sort last.
 // Survivor sort key: pc offset from the text base (low 32 bits) above the
@@ -738,6 +836,22 @@ hipError_t launch_exact_consumers(const ExactPlan &p, const uint32_t *reg_cons, 
 }
 hipError_t launch_exact_dead(const ExactDead &d, fi_histogram *h, hipStream_t st) {
     hipLaunchKernelGGL(fi_exact_dead_kernel, dim3(33), dim3(64), 0, st, d, h);
+    return hipGetLastError();
+}
+hipError_t launch_exact_tick_sites(const ExactPlan &p, const TickMapCtx &c, uint64_t first, uint64_t n,
+                                   const ExactTickClass *cls, fi_site *sites, uint64_t *keys, uint32_t *perm,
+                                   fi_site *tsites, uint8_t *disp, fi_outcome *res, uint64_t *weight, hipStream_t st) {
+    hipLaunchKernelGGL(fi_exact_tick_sites_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, p, c, first, n, cls, sites,
+                       keys, perm, tsites, disp, res, weight);
+    return hipGetLastError();
+}
+hipError_t launch_exact_tick_hist(const fi_site *tsites, const fi_outcome *out, const uint64_t *weight, uint64_t n,
+                                  fi_histogram *h, hipStream_t st) {
+    hipLaunchKernelGGL(fi_exact_tick_hist_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, tsites, out, weight, n, h);
+    return hipGetLastError();
+}
+hipError_t launch_exact_tick_dead(const ExactTickDead &d, fi_histogram *h, hipStream_t st) {
+    hipLaunchKernelGGL(fi_exact_tick_dead_kernel, dim3(32), dim3(64), 0, st, d, h);
     return hipGetLastError();
 }
 hipError_t launch_exact_mem_live(const ExactMemCtx &c, uint8_t *live, hipStream_t st) {

@@ -168,6 +168,19 @@ class ExactInfo(C.Structure):
                 "nbits": int(self.nbits), "classes": {s: int(c) for s, c in enumerate(self.classes) if c}}
 
 
+class ExactTickInfo(C.Structure):
+    """fi_exact_tick_info: the sizes of an exact campaign in the tick domain (Engine.exact_tick_info)."""
+    _fields_ = [("space", C.c_uint64), ("trials", C.c_uint64), ("segments", C.c_uint64), ("dead_ticks", C.c_uint64),
+                ("escaped_ticks", C.c_uint64), ("nbits", C.c_uint32), ("pad", C.c_uint32),
+                ("classes", C.c_uint64 * N_STRUCT), ("build_ms", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {"space": int(self.space), "trials": int(self.trials), "segments": int(self.segments),
+                "dead_ticks": int(self.dead_ticks), "escaped_ticks": int(self.escaped_ticks),
+                "nbits": int(self.nbits), "build_ms": float(self.build_ms),
+                "classes": {s: int(c) for s, c in enumerate(self.classes) if c}}
+
+
 class _ExactMemSet(C.Structure):
     _fields_ = [("bytes", C.c_uint32), ("pad", C.c_uint32), ("positions", C.c_uint64), ("classes", C.c_uint64),
                 ("dead_sites", C.c_uint64)]
@@ -287,6 +300,38 @@ def exact_classes(off, ev, ninst: int, reg: int):
     if rc != FI_OK:
         raise EngineError(f"fi_exact_classes: {rc}")
     return out[:n.value].copy(), int(dead.value)
+
+
+# fi_tick_attempt: one attempt of the packed table the tick map reads (Engine.exact_tick_attempts)
+TICK_ATTEMPT_DT = np.dtype([("done", "<u8"), ("pc", "<u8"), ("n", "<u8"), ("fetch_done0", "<u8"), ("exec", "<u8"),
+                            ("imm", "<i4"), ("g", "<u4"), ("len", "u1"), ("nfetch", "u1"), ("ctl", "u1"), ("rd", "u1"),
+                            ("rs1", "u1"), ("rs2", "u1"), ("done_rd", "u1"), ("flags", "u1")])
+TA_COMMITS, TA_ECALL, TA_PGFAULT, TA_END, TA_MACRO, TA_TAKEN = 1, 2, 4, 8, 16, 32   # fi_tick_attempt.flags
+EXACT_TICK_CLASS_DT = np.dtype([("weight", "<u8"), ("tick", "<u8"), ("inst", "<u4"), ("pad", "<u4")])
+XT_MAPPED = 0xFFFFFFFF                       # fi_exact_tick_class.inst of a descriptor class
+XT_TRIAL, XT_DEAD, XT_GOLDEN, XT_ESCAPE = 0, 1, 2, 3   # fi_exact_tick_locate kinds
+
+
+def exact_tick_classes(att, golden_ticks: int, ninst: int, off, ev, reg: int, contract: int | str = 0):
+    """fi_exact_tick_classes (pure host code): register reg's classes in the
+    tick domain over an attempt table (TICK_ATTEMPT_DT) and a first-access
+    index -> (EXACT_TICK_CLASS_DT[] in id order, {dead, golden, escaped,
+    esc_insts} ticks without a trial)."""
+    att = np.ascontiguousarray(att, TICK_ATTEMPT_DT)
+    off = np.ascontiguousarray(off, np.uint32)
+    ev = np.ascontiguousarray(ev, np.uint32)
+    if len(off) != 33 or int(off[32]) > len(ev):
+        raise ValueError("exact_tick_classes: off has 33 entries and off[32] <= len(ev)")
+    if isinstance(contract, str):
+        contract = TICK_CONTRACTS[contract.lower()]
+    out = np.zeros(int(off[reg + 1] - off[reg]) + 3 * len(att) if 1 <= reg <= 31 else 0, EXACT_TICK_CLASS_DT)
+    n = C.c_uint64(0)
+    tot = (C.c_uint64 * 4)()
+    rc = lib().fi_exact_tick_classes(att.ctypes.data, len(att), golden_ticks, ninst, contract, off.ctypes.data,
+                                     ev.ctypes.data, reg, out.ctypes.data, len(out), C.byref(n), tot)
+    if rc:
+        raise EngineError(f"fi_exact_tick_classes: {rc}")
+    return out[:n.value], dict(zip(("dead", "golden", "escaped", "esc_insts"), (int(v) for v in tot)))
 
 
 def exact_class_consumers(trace, off, ev, ninst: int, reg: int) -> np.ndarray:
@@ -413,6 +458,13 @@ def lib():
         L.fi_exact_get_info.argtypes = [vp, C.POINTER(ExactInfo)]
         L.fi_exact_sites.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
         L.fi_run_exact.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
+        L.fi_exact_tick_get_info.argtypes = [vp, C.POINTER(ExactTickInfo)]
+        L.fi_exact_tick_sites.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp, vp]
+        L.fi_run_exact_ticks.argtypes = [vp, C.c_uint64, C.c_uint64, vp, vp]
+        L.fi_exact_tick_locate.argtypes = [vp, vp, C.c_uint64, vp, vp]
+        L.fi_exact_tick_attempts.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.fi_exact_tick_classes.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, vp, vp, C.c_uint32, vp,
+                                            C.c_uint64, C.POINTER(C.c_uint64), vp]
         L.fi_exact_class_consumers.argtypes = [vp, C.c_uint64, vp, vp, C.c_uint64, C.c_uint32, vp, C.c_uint64,
                                                C.POINTER(C.c_uint64)]
         L.fi_profile_rows.argtypes = [vp, vp, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -761,6 +813,53 @@ class Engine:
                                               hist.ctypes.data, prof.ctypes.data, len(prof)), "fi_run_exact_profile")
         return out, hist[0], prof
 
+    # ---- exact campaigns in the tick domain (include/fi_engine.h, DESIGN.md 4j "Tick domain")
+    def exact_tick_info(self) -> ExactTickInfo:
+        """fi_exact_tick_get_info: the space (ticks x bits x structures), the
+        trial count, the segments, the dead and escaped ticks, build_ms."""
+        x = ExactTickInfo()
+        self._chk(self.L.fi_exact_tick_get_info(self.h, C.byref(x)), "fi_exact_tick_get_info")
+        return x
+
+    def exact_tick_sites(self, first: int, n: int):
+        """-> (sites of exact tick trials [first, first + n), their
+        representative tick sites, the ticks each stands for)"""
+        sites = np.zeros(n, SITE_DT)
+        rep = np.zeros(n, TICK_SITE_DT)
+        w = np.zeros(n, np.uint64)
+        self._chk(self.L.fi_exact_tick_sites(self.h, first, n, sites.ctypes.data, rep.ctypes.data, w.ctypes.data),
+                  "fi_exact_tick_sites")
+        return sites, rep, w
+
+    def run_exact_ticks(self, first: int, n: int, want_outcomes: bool = True):
+        """fi_run_exact_ticks: exact tick trials [first, first + n) ->
+        (outcomes, histogram weighted by ticks; the range that starts at 0 adds
+        the dead and escaped ticks)."""
+        out = np.zeros(n, OUTCOME_DT) if want_outcomes else None
+        hist = np.zeros((), HIST_DT)
+        self._chk(self.L.fi_run_exact_ticks(self.h, first, n, out.ctypes.data if out is not None else None,
+                                            hist.ctypes.data), "fi_run_exact_ticks")
+        return out, hist
+
+    def exact_tick_locate(self, ts: np.ndarray):
+        """fi_exact_tick_locate: -> (trial, kind) per tick site: kind XT_TRIAL
+        names the exact tick trial whose outcome is the site's; XT_DEAD /
+        XT_GOLDEN: masked, the golden run; XT_ESCAPE: FI_ESC_TIMING."""
+        ts = np.ascontiguousarray(ts, TICK_SITE_DT)
+        trial = np.zeros(len(ts), np.uint64)
+        kind = np.zeros(len(ts), np.uint8)
+        self._chk(self.L.fi_exact_tick_locate(self.h, ts.ctypes.data, len(ts), trial.ctypes.data, kind.ctypes.data),
+                  "fi_exact_tick_locate")
+        return trial, kind
+
+    def exact_tick_attempts(self) -> np.ndarray:
+        """fi_exact_tick_attempts: the golden run's packed attempt table (TICK_ATTEMPT_DT)."""
+        n = C.c_uint64(0)
+        self._chk(self.L.fi_exact_tick_attempts(self.h, None, 0, C.byref(n)), "fi_exact_tick_attempts")
+        out = np.zeros(n.value, TICK_ATTEMPT_DT)
+        self._chk(self.L.fi_exact_tick_attempts(self.h, out.ctypes.data, len(out), C.byref(n)), "fi_exact_tick_attempts")
+        return out
+
     def profile_rows(self) -> np.ndarray:
         """fi_profile_rows: the static instructions (and attempted ecalls) of
         the golden run, ascending in pc -> PROFILE_ROW_DT[rows]."""
@@ -1066,6 +1165,10 @@ class FaultCampaign:
             raise ValueError(f"tick_contract {tick_contract!r}: 'numinst' or 'literal'")
         if self.tick_contract != "numinst" and self.cpu_type != "timing":
             raise ValueError(f"tick_contract {tick_contract!r} needs cpu_type='timing'")
+        if self.cpu_type == "timing" and (profile or exact_memory):
+            raise ValueError(f"{'profile' if profile else 'exact_memory'}=True needs cpu_type='atomic': the tick "
+                             "domain has no memory words and no profile (run_exact() covers registers, the pc "
+                             "and instruction results there)")
         self.workload, self.cmd, self.env = workload, list(cmd or [workload]), list(env or [])
         self.trials, self.seed, self.structures, self.burst = trials, seed, structures, burst
         self.protect_mask, self.num_gpus, self.output = protect_mask, num_gpus, output
@@ -1162,7 +1265,8 @@ class FaultCampaign:
         atomic CPU model).  Shards the exact trial ids like run(); only rank
         0's range starts at 0 and counts the dead sites, and the histogram is
         all-reduced the same way.  summary() and vulnerability() read it."""
-        n = int(self.engine.exact_info().trials)
+        timing = self.cpu_type == "timing"   # every tick of the TimingSimpleCPU run (Engine.run_exact_ticks)
+        n = int((self.engine.exact_tick_info() if timing else self.engine.exact_info()).trials)
         rank, world = 0, 1
         if self.num_gpus > 1:
             import torch.distributed as dist
@@ -1170,7 +1274,9 @@ class FaultCampaign:
                 rank, world = dist.get_rank(), dist.get_world_size()
         lo, cnt = shard_range(n, world, rank)
         self.first = lo
-        if self.profiled:
+        if timing:
+            self.outcomes, self._hist = self.engine.run_exact_ticks(lo, cnt)
+        elif self.profiled:
             self.outcomes, self._hist, self._prof = self.engine.run_exact(lo, cnt, profile=True)
         else:
             self.outcomes, self._hist = self.engine.run_exact(lo, cnt)
@@ -1188,10 +1294,16 @@ class FaultCampaign:
     def vulnerability(self) -> dict:
         """Per selected structure, the six outcome-class shares of its sites
         after run_exact(): counts[s].sum(bits) / (ninst x eligible bits), for
-        the memory words (33) / (words x ninst x eligible bits)."""
+        the memory words (33) / (words x ninst x eligible bits); for a timing
+        campaign / (golden ticks x eligible bits): time-weighted."""
+        sel = structures_mask(self.structures)
+        if self.cpu_type == "timing":
+            per = int(self.engine.tick_info()["golden_ticks"]) * int(self.engine.exact_tick_info().nbits)
+            h = self._hist["counts"]
+            return {s: {CLASS_NAMES[c]: int(h[s, :, c].sum()) / per for c in range(6)}
+                    for s in range(1, N_STRUCT) if (sel >> s) & 1}
         x = self.engine.exact_info()
         per = int(self.golden.ninst) * int(x.nbits)
-        sel = structures_mask(self.structures)
         words = int(self.engine.exact_mem_info().words) if (sel >> 33) & 1 else 1
         h = self._hist["counts"]
         return {s: {CLASS_NAMES[c]: int(h[s, :, c].sum()) / (per * (words if s == 33 else 1)) for c in range(6)}
