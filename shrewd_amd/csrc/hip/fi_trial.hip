@@ -4660,7 +4660,16 @@ __device__ __forceinline__ void trial_body() {
                 if (!CX->record) {   // solo: the out-of-line run (solo_pre_run), then the general path
                     __shared__ SoloPreIO pio[1];
                     pio->spc = lpc; pio->slot = slot; pio->tab = w.tab; pio->tab_n = w.tab_n;
-                    pio->budget = budget; pio->watch = L.watch;
+                    // the run returns when a loop probe is due: a loop this path owns
+                    // outright (integer ops on golden text no translated block covers)
+                    // otherwise stays in one call up to the next event -- past the last
+                    // golden snapshot, the hang cap -- and is never probed
+                    uint32_t pbud = budget;
+                    if (CX->hang_proof && LP_ELIGIBLE) {
+                        const uint32_t due = LP.at > LP.cnt ? LP.at - LP.cnt : 1u;
+                        pbud = due < pbud ? due : pbud;
+                    }
+                    pio->budget = pbud; pio->watch = L.watch;
                     pio->fps = (L.fp ? 1u : 0u) | ((uint32_t)L.fflags << 8) | ((uint32_t)L.frm << 16);
                     pio->tx_gate = tx_skip_until > n_iter ? tx_skip_until - n_iter : 0u;
                     solo_pre_run<kOdd>(CX, (lds_u64 *)R, (lds_mem *)&m, (lds_u32 *)DCT, (lds_pre4 *)DCE, (lds_u32 *)LC,

@@ -439,6 +439,80 @@ def test_dynamic_loop_proofs(engine_factory, oracle_mod, name):
     assert np.array_equal(c, d)
 
 
+def test_dynamic_loop_known_answers(oracle_mod):
+    """The lp program (tests/test_isa_vectors.py): one gated loop per rule of
+    the dynamic loop proof, each entered by one explicit fault on its gate.
+    H loops are true hangs the probe must prove, U loops true hangs it must
+    refuse (kLpBad instructions, a pass longer than the window), N loops near
+    misses that end (masked) after outlasting the first probe.  Every record
+    equals the oracle's, which runs every trial to its end.
+    1. On the solo kernel the H sites alone: each one proved by the probe
+       (LP_COMMIT), same records as without proofs, with less than a third of
+       the instructions (without proofs a trial runs at least the golden
+       run's length, 60 k, inside its loop; with them the slowest, h_fpsat,
+       is proved by its second probe, FI_LP_START + 2 * FI_LP_START plus two
+       windows in: about 12.5 k, the others by their first, 4.2 k).
+    2. The U and N sites: none proved, each examined and refused (LP_FAIL).
+    3. Under default flags (the 64-lane epoch first) and without translated
+       blocks, all sites: only H loops may be proved."""
+    from shrewd_amd import STAT
+    from shrewd_amd import Engine
+    from shrewd_amd.fi import CFG_NO_HANG_PROOF, CFG_NO_TRANSLATE, CFG_SOLO_ALL
+    import test_isa_vectors as kat
+    if not oracle_mod.has_softfloat():
+        pytest.skip("oracle without the reference SoftFloat")
+    elf = kat.lp_program_elf()
+    o = oracle_mod.Oracle(elf, "lp")
+    g = o.run_golden()
+    assert kat.lp_program_model()["end"] == g.ninst
+    cap = kat.lp_hang_cap(g.ninst)
+    (names_h, s_h), (names_un, s_un), (names, s_all) = kat.lp_sites("H"), kat.lp_sites("UN"), kat.lp_sites()
+    ref_h, ref_un, ref_all = (o.run_trials(s, protect_mask=0) for s in (s_h, s_un, s_all))
+    hang = np.array([kat.LP_KIND[n] in "HU" for n in names])
+    assert (ref_all["cls"][hang] == 3).all() and (ref_all["ninst"][hang] == cap).all()
+    assert (ref_all["cls"][~hang] == 0).all() and (ref_all["ninst"][~hang] > g.ninst + kat.LP_START).all()
+
+    def engine(flags):
+        e = Engine(private_pages=64, flags=flags)
+        e.load_elf(elf, ["lp"])
+        e.golden_run()
+        assert e.golden_stdout() == kat.lp_program_expected()
+        return e
+
+    def run(e, sites, ref):
+        dev, h = e.run_sites(sites)
+        compare(dev, ref, sites)
+        st = e.debug_stats()
+        return dev, int(h["device_insts"]), int(st[STAT.LP_COMMIT]), int(st[STAT.LP_FAIL])
+
+    on, off = engine(CFG_SOLO_ALL), engine(CFG_SOLO_ALL | CFG_NO_HANG_PROOF)
+    # 1. the H sites, proofs on and off
+    a, ins_on, commit_on, fail_on = run(on, s_h, ref_h)
+    b, ins_off, commit_off, _ = run(off, s_h, ref_h)
+    print("lp H sites (device insts, LP_COMMIT, LP_FAIL): on", (ins_on, commit_on, fail_on),
+          "off", (ins_off, commit_off))
+    assert np.array_equal(a, b)
+    assert commit_on == len(names_h) and commit_off == 0
+    assert 3 * ins_on < ins_off
+    # 2. the U and N sites: examined and refused
+    a, _, commit_on, fail_on = run(on, s_un, ref_un)
+    b, _, commit_off, fail_off = run(off, s_un, ref_un)
+    print("lp U and N sites (LP_COMMIT, LP_FAIL): on", (commit_on, fail_on), "off", (commit_off, fail_off))
+    assert np.array_equal(a, b)
+    assert commit_on == 0 and commit_off == 0
+    assert fail_on >= len(names_un)
+    on.close()
+    off.close()
+    # 3. all sites inside a normal campaign, with and without translated blocks
+    for flags in (0, CFG_NO_TRANSLATE):
+        e = engine(flags)
+        dev, _, commit, fail = run(e, s_all, ref_all)
+        print(f"lp all sites, flags {flags} (LP_COMMIT, LP_FAIL):", (commit, fail))
+        assert commit <= len(names_h)
+        assert (dev["cls"][~hang] == 0).all()
+        e.close()
+
+
 def test_runoff_loop_proofs(oracle_mod):
     """Run-off loops (fi_translate.cpp, fi_trial.hip loop_outcome): faults on
     the scan pointer / end of the runoff program's three scan loops.  Trials
@@ -718,7 +792,7 @@ def test_native_driver_matches_engine(engine_factory, tmp_path):
 
 
 @pytest.mark.parametrize("prog", ["alu", "mem", "cmp", "rvc", "sys", "lrsc", "vm", "fp", "rnd", "xop", "sys2", "clk",
-                                  "stdin", "vset", "vcfg"])
+                                  "stdin", "vset", "vcfg", "fmov"])
 def test_known_answer_programs(oracle_mod, prog):
     """Known answers on the device (guest programs of tests/test_isa_vectors.py).
 
@@ -743,7 +817,10 @@ def test_known_answer_programs(oracle_mod, prog):
     sys2: read, readlinkat (/proc/self/exe) and riscv_hwprobe.
     vset: vset* with illegal vtype requests from the start vector state.
     vcfg: vset* chains through legal vector configurations (AVL, VLMAX, the
-    kept vl of x0, x0, uint32_t AVL truncation, vsetvl's vill bit).  The device golden run (general interpreter)
+    kept vl of x0, x0, uint32_t AVL truncation, vsetvl's vill bit).
+    fmov: FP data movement -- NaN-boxing of loads, moves and sign injection,
+    all ten fclass classes, raw stores, line- and page-crossing FP accesses,
+    the compressed forms and FP reads before any FP write.  The device golden run (general interpreter)
     must print exactly the reference-derived models; no-fault trials
     (pre-decoded and translated paths, from snapshots) must end masked with
     the oracle's records; faulted trials must match the oracle bit for bit."""
@@ -763,7 +840,8 @@ def test_known_answer_programs(oracle_mod, prog):
                      "clk": (kat.clk_program_elf, kat.clk_program_expected),
                      "stdin": (kat.stdin_program_elf, kat.stdin_program_expected),
                      "vset": (kat.vset_program_elf, kat.vset_program_expected),
-                     "vcfg": (kat.vcfg_program_elf, kat.vcfg_program_expected)}[prog]
+                     "vcfg": (kat.vcfg_program_elf, kat.vcfg_program_expected),
+                     "fmov": (kat.fmov_program_elf, kat.fmov_program_expected)}[prog]
     if prog in ("fp", "xop") and not oracle_mod.has_softfloat():
         pytest.skip("oracle without the reference SoftFloat")
     if prog == "xop" and not oracle_mod.has_rvk():
@@ -801,7 +879,8 @@ def test_known_answer_programs(oracle_mod, prog):
 
 
 @pytest.mark.parametrize("prog,path", [pytest.param(p, q, id=p if q == "solo" else f"{p}-{q}")
-                                       for q in ("solo", "lanes", "simt") for p in ("alu", "cmp", "rvc", "mem")])
+                                       for q in ("solo", "lanes", "simt")
+                                       for p in ("alu", "cmp", "rvc", "mem", "fp", "fmov", "lrsc", "xop")])
 def test_known_answer_programs_solo_interpreter(oracle_mod, prog, path):
     """The known-answer programs from process start through one pre-decoded
     interpreter only (NO_TRANSLATE | NO_SNAPSHOT_START | NO_EARLY_EXIT), once
@@ -813,19 +892,38 @@ def test_known_answer_programs_solo_interpreter(oracle_mod, prog, path):
     lanes: in the 64-lane pre-decoded loop (NO_SOLO);
     simt: the same with diverged lanes in the SIMT step loop (SIMT);
     no-fault trials print the models and end masked, faulted trials match the
-    oracle."""
+    oracle.  fp, fmov, lrsc and xop take the copies of the FP, atomic and
+    crypto semantics the same way: on the solo kernel the pre-decoded loop's
+    own FP ops (solo_fp_op: loads, stores, moves, sign injection, classify,
+    the arithmetic of fp_exec and the commit that makes the FP file exist at
+    its first write), everything else through the general path behind it.
+    The device golden stdout is the program's model; on the solo path every
+    instruction of the no-fault run is counted by the solo kernel
+    (SOLO_DEVICE_INSTS == DEVICE_INSTS: nothing ran elsewhere)."""
     from shrewd_amd import STAT
     from shrewd_amd import Engine
     from shrewd_amd.fi import (CFG_NO_EARLY_EXIT, CFG_NO_SNAPSHOT_START, CFG_NO_SOLO, CFG_NO_TRANSLATE, CFG_SIMT,
                                CFG_SOLO_ALL)
     import test_isa_vectors as kat
-    elf = {"alu": kat.program_elf, "cmp": kat.cmp_program_elf, "rvc": kat.rvc_program_elf,
-           "mem": kat.mem_program_elf}[prog]()
+    if prog in ("fp", "xop") and not oracle_mod.has_softfloat():
+        pytest.skip("oracle without the reference SoftFloat")
+    if prog == "xop" and not oracle_mod.has_rvk():
+        pytest.skip("oracle without the reference rvk.hh")
+    elf, expected = {"alu": (kat.program_elf, kat.program_expected),
+                     "cmp": (kat.cmp_program_elf, kat.cmp_program_expected),
+                     "rvc": (kat.rvc_program_elf, kat.rvc_program_expected),
+                     "mem": (kat.mem_program_elf, kat.mem_program_expected),
+                     "fp": (kat.fp_program_elf, kat.fp_program_expected),
+                     "fmov": (kat.fmov_program_elf, kat.fmov_program_expected),
+                     "lrsc": (kat.lrsc_program_elf, kat.lrsc_program_expected),
+                     "xop": (kat.xop_program_elf, kat.xop_program_expected)}[prog]
+    elf = elf()
     start = CFG_NO_TRANSLATE | CFG_NO_SNAPSHOT_START | CFG_NO_EARLY_EXIT
     flags = {"solo": CFG_SOLO_ALL | start, "lanes": CFG_NO_SOLO | start, "simt": CFG_NO_SOLO | CFG_SIMT | start}[path]
     e = Engine(private_pages=64, flags=flags)
     e.load_elf(elf, [prog])
     e.golden_run()
+    assert e.golden_stdout() == expected()
     o = oracle_mod.Oracle(elf, prog)
     o.run_golden()
     e.set_campaign(0x5EED00A5, REGS | PC, 1)
@@ -836,6 +934,10 @@ def test_known_answer_programs_solo_interpreter(oracle_mod, prog, path):
     dev, h = e.run_sites(nofault)
     assert (dev["cls"] == 0).all()
     assert int(h["device_insts"]) == int(h["guest_insts"])
+    if path == "solo":   # everything from process start ran in trial_body<1>
+        st = e.debug_stats()
+        assert int(st[STAT.SOLO_DEVICE_INSTS]) == int(st[STAT.DEVICE_INSTS]) > 0, (
+            int(st[STAT.SOLO_DEVICE_INSTS]), int(st[STAT.DEVICE_INSTS]))
     compare(dev, o.run_trials(nofault, protect_mask=0), nofault)
     dev, _ = e.run_sites(sites)
     compare(dev, o.run_trials(sites, protect_mask=0), sites)
@@ -845,6 +947,34 @@ def test_known_answer_programs_solo_interpreter(oracle_mod, prog, path):
     if path == "simt":
         assert int(st[STAT.SIMT_LANE_INSTS]) > 0, "the SIMT step loop did not run"
     e.close()
+
+
+@pytest.mark.parametrize("path", ["solo", "lanes", "simt"])
+def test_fpamo_forced_interpreters(engine_factory, oracle_mod, path):
+    """The fpamo workload (F/D/Zfh moves, sign injection, classify and every
+    AMO folded into a hash) from process start through one pre-decoded
+    interpreter only, as test_known_answer_programs_solo_interpreter forces
+    them: the device golden stdout is the Python model's (test_oracle.ref_fpamo)
+    and register, pc and memory faults give the oracle's records."""
+    from shrewd_amd.fi import (CFG_NO_EARLY_EXIT, CFG_NO_SNAPSHOT_START, CFG_NO_SOLO, CFG_NO_TRANSLATE, CFG_SIMT,
+                               CFG_SOLO_ALL)
+    from test_oracle import ref_fpamo
+    start = CFG_NO_TRANSLATE | CFG_NO_SNAPSHOT_START | CFG_NO_EARLY_EXIT
+    flags = {"solo": CFG_SOLO_ALL | start, "lanes": CFG_NO_SOLO | start, "simt": CFG_NO_SOLO | CFG_SIMT | start}[path]
+    e = engine_factory("fpamo", flags=flags, private_pages=64)
+    assert e.golden_stdout() == ref_fpamo()
+    e.set_campaign(0x5EED00A7, REGS | PC | MEM, 1)
+    e.set_protect(0)
+    sites = e.sample(0, 1500)
+    if "fpamo" not in _FPAMO_REF:
+        _FPAMO_REF["fpamo"] = (sites, oracle_for(oracle_mod, "fpamo").run_trials(sites, protect_mask=0))
+    rsites, ref = _FPAMO_REF["fpamo"]
+    assert np.array_equal(sites, rsites)
+    dev, _ = e.run_sites(sites)
+    compare(dev, ref, sites)
+
+
+_FPAMO_REF = {}
 
 
 @pytest.mark.parametrize("flags", [0, 128 | 4 | 1 | 2])

@@ -737,6 +737,15 @@ LRSC_EXPECTED = [
 ]
 
 
+# Between its LR / SC / AMO instructions, and the stretches in which the
+# context holds a lock record, the program has no run of more than eight
+# instructions: the solo kernel's assembly inner loop takes a run over only
+# after eight (solo_pre_run).  A run of plain instructions after the last SC
+# (no record held) lets it in, so that the forced solo path shows both sides
+# of the lock record's gate (tests/test_gpu_parity.py).
+LRSC_PLAIN_RUN = "\n".join(["    addi  t6, t6, 1"] * 16)
+
+
 def lrsc_program_source() -> str:
     return f"""    .text
 _start:
@@ -801,6 +810,7 @@ _start:
     sd    t3, 104(s2)
     ld    t5, 0(t4)
     sd    t5, 112(s2)
+{LRSC_PLAIN_RUN}
     li    a0, 1
     la    a1, out
     li    a2, {8 * len(LRSC_EXPECTED)}
@@ -2791,3 +2801,404 @@ def test_region_program_on_oracle(oracle_mod):
     names = region_site_variant(sites[:REGION_SITES_CPU])
     valid = np.array([n in REGION_VALID for n in names])
     assert {0, 1, 2, 3} <= set(res["cls"][:REGION_SITES_CPU][valid].tolist())
+
+
+# ------------------------------------------------------------------ lp program
+# Dynamic loop proofs (fi_trial.hip LoopProbe / lp_entry / lp_prove /
+# lp_same_state / lp_commit): one gated loop per rule of the
+# proof.  A prologue sets the constants, a counted pad loop lengthens the
+# golden run, then one gate per loop -- `li t6, 0; bnez t6, tr_<loop>;
+# back_<loop>:` -- a write of the 64-byte buffer and exit(0).  The golden run
+# never executes the loop bodies, and no translated block may cover them: the
+# translator also takes the code its blocks reach by direct branches and by
+# falling through (fi_translate.cpp, static closure), so the bodies stand
+# before _start, where nothing falls into them, and a gate enters its loop
+# through an indirect jump (`tr_<loop>: la t5, <loop>; jr t5`, after the exit).
+# Each trial is one explicit site: bit 0 of t6 flipped at the fault time at
+# which the gate's bnez reads it, so the trial enters the loop.
+# Kinds:
+#   H  a true hang the probe must prove;
+#   U  a true hang the probe must not prove (the trial runs to the cap);
+#   N  a near miss: the loop terminates (`j back_<loop>` after putting memory
+#      back), so the trial is masked.
+# Constants: s0 = buf (64 zero bytes), s1 = tab (the address of h_ind's head),
+# s2 = scan (6008 bytes, byte 6000 = 1), s3 = buf + 24, set by the prologue;
+# f2 = 1.0h, f3 = 4096.0h, f5 = f7 = 1.0d, f8 = 3000.0d, set by the set-up of
+# the loops that use them, before the loop's head: a golden run that writes FP
+# state has no snapshots on the device (the FP file is not in them), every
+# trial would start at the process's first instruction, and a proved hang could
+# not run under a third of an unproved one's instructions, whatever the proof.
+LP_F2_F3 = ["li    t0, 0x3C00", "fmv.h.x f2, t0", "li    t0, 0x6C00", "fmv.h.x f3, t0"]
+LP_F5 = ["li    t0, 0x3FF0000000000000", "fmv.d.x f5, t0"]
+LP_F7_F8 = ["li    t0, 0x3FF0000000000000", "fmv.d.x f7, t0", "li    t0, 0x40A7700000000000", "fmv.d.x f8, t0"]
+LP_PAD = 30000
+LP_WINDOW = 128    # FI_LP_WINDOW: instructions per recorded pass at most
+LP_START = 4096    # FI_LP_START: interpreted instructions before the first probe
+LP_SCAN = 6000
+# the pipeline of n_pipe: x5 <- 0, then register to register, one stage a pass
+LP_PIPE_X = [5, 6, 7, 10, 11, 12, 13, 14, 15, 16, 17, 20, 21, 22, 23, 24, 25, 26, 27, 28, 29, 30]
+LP_PIPE = len(LP_PIPE_X) + 32 + 1   # ... the integer stages, f0..f31, and x31 (the branch operand)
+
+
+def _lp_pipe():
+    """n_pipe's set-up and body: every stage starts at 1; a pass moves each
+    stage's value one on (last stage first) and zeroes the first; the loop
+    leaves when the zero reaches x31, LP_PIPE passes on.  Every branch
+    operand is `invariant' by the fixpoint of lp_prove (x5 is a constant,
+    each stage a copy of an invariant one): only the comparison of the
+    written registers taken as invariant at the pass's start with their values
+    at its end (`chk', fi_trial.hip lp_prove) refuses the pass, on the stage
+    that changes in it.  Padded to LP_WINDOW - 1 instructions a pass, so that
+    the first probe (LP_START instructions in) finds the zero mid-way."""
+    x, n = LP_PIPE_X, len(LP_PIPE_X)
+    setup = [f"li    x{r}, 1" for r in x] + [f"fmv.d.x f{f}, x5" for f in range(32)] + ["li    x31, 1"]
+    body = ["fmv.x.d x31, f31"] + [f"fsgnj.d f{f}, f{f - 1}, f{f - 1}" for f in range(31, 0, -1)]
+    body += [f"fmv.d.x f0, x{x[-1]}"] + [f"mv    x{x[k]}, x{x[k - 1]}" for k in range(n - 1, 0, -1)] + ["li    x5, 0"]
+    body += ["addi  x1, x1, 1"] * (LP_WINDOW - 2 - len(body)) + ["bnez  x31, @L"]
+    assert len(body) == LP_WINDOW - 1
+    return setup, body
+
+
+# name, kind, set-up, loop body (@L = its head), after the loop, passes the
+# loop makes before it leaves (N loops; closed form in the loop's bounds)
+LP_LOOPS = [
+    # one-entry pass
+    ("h_self", "H", [], ["j     @L"], [], None),
+    # a written, non-invariant register nothing depends on
+    ("h_count", "H", [], ["addi  t1, t1, 1", "j     @L"], [], None),
+    # invariant branch operand
+    ("h_invbr", "H", ["li    t1, 5"], ["addi  t2, t2, 3", "bnez  t1, @L"], [], None),
+    # silent store, load of unchanged memory
+    ("h_silent", "H", ["li    t1, 0"], ["addi  t3, t3, 1", "sd    t1, 0(s0)", "ld    t2, 0(s0)", "beqz  t2, @L"], [],
+     None),
+    # the stores are loud for 64 passes; then the whole state repeats (lp_same_state)
+    ("h_conv", "H", ["li    t1, -1"], ["srli  t1, t1, 1", "sd    t1, 8(s0)", "bgez  t1, @L"], [], None),
+    # binary16 saturates at 2048 after 2048 passes (instruction 6144 of the
+    # loop): the first probe must fail, a later one proves it through the FP
+    # file in lp_same_state
+    ("h_fpsat", "H", LP_F2_F3 + ["fmv.h.x f1, zero"], ["fadd.h f1, f1, f2", "flt.h t1, f1, f3", "bnez  t1, @L"], [],
+     None),
+    # FP load, silent FP store, FP-to-int move as the branch operand; the free
+    # counter forces the rule path, not lp_same_state
+    ("h_fpinv", "H", LP_F5, ["addi  t3, t3, 1", "fsgnjn.d f4, f5, f5", "fmv.x.d t1, f4", "fld   f6, 32(s0)",
+                          "fsd   f6, 32(s0)", "bnez  t1, @L"], [], None),
+    # indirect jump through a loaded, invariant target
+    ("h_ind", "H", [], ["ld    t1, 0(s1)", "addi  t2, t2, 1", "jr    t1"], [], None),
+    # a pass of exactly FI_LP_WINDOW - 1 / FI_LP_WINDOW instructions
+    ("h_w127", "H", [], ["addi  t2, t2, 1"] * (LP_WINDOW - 2) + ["j     @L"], [], None),
+    ("h_w128", "H", [], ["addi  t2, t2, 1"] * (LP_WINDOW - 1) + ["j     @L"], [], None),
+    # a pass longer than the window
+    ("u_w129", "U", [], ["addi  t2, t2, 1"] * LP_WINDOW + ["j     @L"], [], None),
+    # kLpBad: a syscall, LR/SC, an AMO (although it changes nothing)
+    ("u_ecall", "U", [], ["li    a7, 172", "ecall", "j     @L"], [], None),
+    ("u_lrsc", "U", [], ["lr.w  t1, (s0)", "sc.w  t2, t1, (s0)", "j     @L"], [], None),
+    ("u_amo", "U", [], ["amoadd.w t1, zero, (s0)", "j     @L"], [], None),
+    # non-invariant branch operand
+    ("n_count", "N", ["li    t1, 5000"], ["addi  t1, t1, -1", "bnez  t1, @L"], [], 5000),
+    # the store is silent for 4095 passes but its datum is not invariant
+    ("n_datum", "N", ["li    t1, 0"], ["addi  t1, t1, 1", "srli  t2, t1, 12", "sb    t2, 16(s0)", "lbu   t3, 16(s0)",
+                                       "beqz  t3, @L"], ["sb    zero, 16(s0)"], 1 << 12),
+    # the same through an int-to-FP move and an FP store (the 32 + rd destination fields)
+    ("n_fpdatum", "N", ["li    t1, 0"], ["addi  t1, t1, 1", "srli  t2, t1, 12", "fmv.d.x f9, t2", "fsd   f9, 48(s0)",
+                                         "ld    t3, 48(s0)", "beqz  t3, @L"], ["sd    zero, 48(s0)"], 1 << 12),
+    # the branch operand is a load whose address is not invariant
+    ("n_scan", "N", ["mv    t1, s2"], ["lbu   t2, 0(t1)", "addi  t1, t1, 1", "beqz  t2, @L"], [], LP_SCAN + 1),
+    # every register is equal from pass to pass, only memory counts: a loud
+    # store must bar lp_same_state
+    ("n_memcnt", "N", ["li    t2, 3000"], ["ld    t1, 40(s0)", "addi  t1, t1, 1", "sd    t1, 40(s0)",
+                                           "slt   t1, t1, t2", "bnez  t1, @L"], ["sd    zero, 40(s0)"], 3000),
+    # an AMO is the counter (it returns the old value: 0 .. 4000)
+    ("n_amo", "N", ["li    t3, 1", "li    t2, 4000"], ["amoadd.w t1, t3, (s3)", "blt   t1, t2, @L"],
+     ["sw    zero, 0(s3)"], 4000 + 1),
+    # LR/SC is the counter
+    ("n_lrsc", "N", ["li    t2, 3000"], ["lr.w  t1, (s3)", "addi  t1, t1, 1", "sc.w  t3, t1, (s3)",
+                                         "blt   t1, t2, @L"], ["sw    zero, 0(s3)"], 3000),
+    # the branch operand comes from a non-invariant FP register
+    ("n_fp", "N", LP_F7_F8 + ["fmv.d.x f1, zero"], ["fadd.d f1, f1, f7", "flt.d t1, f1, f8", "bnez  t1, @L"], [], 3000),
+    # a register pipeline: every operand `invariant', the registers' values not yet
+    ("n_pipe", "N", *_lp_pipe(), [], LP_PIPE),
+]
+LP_KIND = {name: kind for name, kind, *_ in LP_LOOPS}
+
+LP_PROLOGUE = ["la    s0, buf", "la    s1, tab", "la    s2, scan", "addi  s3, s0, 24", "la    t0, h_ind_L",
+               "sd    t0, 0(s1)", f"li    t0, {LP_SCAN}", "add   t0, t0, s2", "li    t1, 1", "sb    t1, 0(t0)"]
+LP_TRAMPOLINE = ["la    t5, @", "jr    t5"]
+LP_EPILOGUE = ["li    a0, 1", "mv    a1, s0", "li    a2, 64", "li    a7, 64", "ecall", "li    a0, 0", "li    a7, 93",
+               "ecall"]
+
+
+def _lp_count(lines):
+    """Committed instructions of straight-line code (`li` as the assembler
+    expands it, `la` = auipc + addi, an ecall is not counted)."""
+    from rvasm import li_sequence
+    n = 0
+    for ln in lines:
+        op, _, rest = ln.partition(" ")
+        if op == "li":
+            n += len(li_sequence(5, int(rest.split(",")[1], 0)))
+        else:
+            n += {"la": 2, "ecall": 0}.get(op, 1)
+    return n
+
+
+def lp_program_source() -> str:
+    out = ["    .text"]
+    for name, kind, setup, body, after, _ in LP_LOOPS:
+        out += [f"{name}:"] + ["    " + ln for ln in setup] + [f"{name}_L:"]
+        out += ["    " + ln.replace("@L", f"{name}_L") for ln in body] + ["    " + ln for ln in after]
+        out += [f"    j     back_{name}"]   # (never reached in an H or U loop)
+    out += ["_start:"] + ["    " + ln for ln in LP_PROLOGUE]
+    out += [f"    li    t0, {LP_PAD}", "pad:", "    addi  t0, t0, -1", "    bnez  t0, pad"]
+    for name, *_ in LP_LOOPS:
+        out += ["    li    t6, 0", f"    bnez  t6, tr_{name}", f"back_{name}:"]
+    out += ["    " + ln for ln in LP_EPILOGUE]
+    for name, *_ in LP_LOOPS:
+        out += [f"tr_{name}:"] + ["    " + ln.replace("@", name) for ln in LP_TRAMPOLINE]
+    out += ["    .bss", "    .balign 64", "buf:", "    .zero 64", "tab:", "    .zero 8", "scan:",
+            f"    .zero {LP_SCAN + 8}"]
+    return "\n".join(out) + "\n"
+
+
+def lp_program_elf() -> bytes:
+    from tools.rvasm.rvasm import assemble
+    return assemble(lp_program_source())
+
+
+def lp_program_expected() -> bytes:
+    return bytes(64)
+
+
+def lp_program_model():
+    """The golden run's instruction counts: {"gate": {loop: the count committed
+    before its gate's bnez}, "extra": {N loop: what its trial commits beyond the
+    golden run}, "end": the whole run's count}."""
+    n = _lp_count(LP_PROLOGUE) + _lp_count([f"li t0, {LP_PAD}"]) + 2 * LP_PAD
+    gate, extra = {}, {}
+    for name, kind, setup, body, after, passes in LP_LOOPS:
+        gate[name] = n + 1
+        n += 2
+        if kind == "N":   # the trampoline, set-up, the passes, what puts memory back, `j back`
+            extra[name] = (_lp_count(LP_TRAMPOLINE) + _lp_count(setup) + _lp_count(body) * passes + _lp_count(after)
+                           + 1)
+    return {"gate": gate, "extra": extra, "end": n + _lp_count(LP_EPILOGUE)}
+
+
+def lp_sites(kinds="HUN"):
+    """One site per loop of the given kinds, in LP_LOOPS order: t6 (target 31)
+    bit 0 at the gate's bnez."""
+    import numpy as np
+    from oracle.pyoracle import SITE_DT
+    lay = lp_program_model()
+    names = [name for name, kind, *_ in LP_LOOPS if kind in kinds]
+    s = np.zeros(len(names), SITE_DT)
+    s["inst"] = [lay["gate"][name] for name in names]
+    s["target"], s["mask"] = 31, 1
+    s["trial"] = np.arange(len(s))
+    return names, s
+
+
+def lp_hang_cap(ninst):
+    """The default cap: twice the golden run and 1000 (oracle/rv64se.c hang_cap)."""
+    return 2 * ninst + 1000
+
+
+def test_lp_program_on_oracle(oracle_mod):
+    """Every gate site on the oracle: H and U loops run to the cap, N loops end
+    masked after exactly the model's instruction count, each one longer than
+    FI_LP_START (so it is probed) and well under the cap."""
+    if not oracle_mod.has_softfloat():
+        pytest.skip("oracle without the reference SoftFloat")
+    o = oracle_mod.Oracle(lp_program_elf(), "lp")
+    g = o.run_golden()
+    lay = lp_program_model()
+    assert g.exit_code == 0 and o.golden_stdout() == lp_program_expected()
+    assert lay["end"] == g.ninst, (lay["end"], g.ninst)
+    cap = lp_hang_cap(g.ninst)
+    names, sites = lp_sites()
+    res = o.run_trials(sites, protect_mask=0)
+    for name, r in zip(names, res):
+        if LP_KIND[name] in "HU":
+            assert (int(r["cls"]), int(r["sub"]), int(r["ninst"])) == (3, 1, cap), (name, r)
+        else:
+            assert int(r["cls"]) == 0 and int(r["ninst"]) == g.ninst + lay["extra"][name], (name, r, lay["extra"][name])
+    # the closed forms, for the bounds above (5 * 4096 + 3 and so on), after the trampoline's three
+    ex = {k: v - 3 for k, v in lay["extra"].items()}
+    assert ex["n_count"] == 2 * 5000 + 3 and ex["n_datum"] == 5 * 4096 + 3
+    assert ex["n_scan"] == 3 * (LP_SCAN + 1) + 2 and ex["n_memcnt"] == 5 * 3000 + 4
+    assert ex["n_amo"] == 2 * 4001 + 5 and ex["n_lrsc"] == 4 * 3000 + 4
+    assert ex["n_fp"] == 3 * 3000 + 2 + _lp_count(LP_F7_F8) and ex["n_fpdatum"] == 6 * 4096 + 3
+    assert min(lay["extra"].values()) > LP_START and g.ninst + max(lay["extra"].values()) < cap
+    # n_pipe: the first probe (LP_START interpreted instructions in, at most
+    # the set-up and a window later) finds the zero inside the pipeline
+    assert (LP_PIPE - 2) * (LP_WINDOW - 1) > LP_START + LP_PIPE + LP_WINDOW
+
+
+# ---------------------------------------------------------------- fmov program
+# FP data movement, known answers: each case leaves a raw 64-bit result in t1
+# that goes to stdout.  Expected values are computed here from the reference's
+# definitions, not by the oracle:
+# - NaN-boxing: unboxF16 / unboxF32 give the canonical NaN for a register whose
+#   upper bits are not all ones, boxF16 / boxF32 set them
+#   (`src/arch/riscv/regs/float.hh:71-94`);
+# - fsgnj / fsgnjn / fsgnjx unbox both operands and box the result; the .d
+#   forms work on the raw 64 bits (`decoder.isa:2895-2943`);
+# - fclass.{s,d,h} classify the unboxed operand (`:3508-3541`,
+#   `ext/softfloat/f32_classify.c`: bit 0 -inf, 1 -normal, 2 -subnormal, 3 -0,
+#   4 +0, 5 +subnormal, 6 +normal, 7 +inf, 8 sNaN, 9 qNaN);
+# - fmv.x.w / fmv.x.h sign-extend the raw low 32 / 16 bits, no unboxing
+#   (`:3501-3507`, `:3532-3538`); fmv.x.d is the raw register (`:3515-3517`);
+#   fmv.w.x / fmv.h.x box, fmv.d.x copies (`:3545-3549`, `:3594-3598`,
+#   `:3648-3652`);
+# - flh / flw box what they load, fld loads raw (`:570-595`); fsh / fsw store
+#   the raw low bytes (unboxF32(boxF32(x)) = the low 32 bits), fsd all eight
+#   (`:1743-1763`); c.fld / c.fsd / c.fldsp / c.fsdsp are fld / fsd
+#   (`:58-67`, `:147-156`, `:375-386`, `:493-503`);
+# - an FP register read before any FP write is zero (the file starts zeroed).
+# Accesses are split at 64-byte lines and cross pages (see the mem program).
+FMOV_OFFS = [0, 1, 3, 30, 61, 62, 63, 4089, 4093, 4094, 4095]
+FMOV_QNAN = {"h": 0x7E00, "s": 0x7FC00000}
+FMOV_W = {"h": 16, "s": 32, "d": 64}
+
+
+def fmov_unbox(v, f):
+    if f == "d":
+        return v
+    w = FMOV_W[f]
+    return v & ((1 << w) - 1) if v >> w == (1 << (64 - w)) - 1 else FMOV_QNAN[f]
+
+
+def fmov_box(v, f):
+    return (v | FP_BOX[f]) & M64
+
+
+def fmov_class(v, f):
+    eb, fb = {"h": (5, 10), "s": (8, 23), "d": (11, 52)}[f]
+    s, e, m = v >> (eb + fb), (v >> fb) & ((1 << eb) - 1), v & ((1 << fb) - 1)
+    if e == (1 << eb) - 1:
+        if m == 0:
+            return 1 << (0 if s else 7)
+        return 1 << (9 if m >> (fb - 1) else 8)
+    if e == 0:
+        return 1 << ((3 if s else 4) if m == 0 else (2 if s else 5))
+    return 1 << (1 if s else 6)
+
+
+def fmov_cases():
+    """[(name, lines leaving the result in t1, expected value)], in program
+    order; the lines may use t0, t1, t3, f0..f31 and the bases s0 (buf, two
+    pages), sp (buf + 512)."""
+    c = []
+    # an FP register read before any FP write (these come first: nothing here writes one)
+    c.append(("early fmv.x.d", ["fmv.x.d t1, f9"], 0))
+    c.append(("early fclass.d", ["fclass.d t1, f10"], 1 << 4))
+    c.append(("early fclass.s", ["fclass.s t1, f12"], 1 << 9))   # (zero is no boxed binary32)
+    c.append(("early fmv.x.w", ["fmv.x.w t1, f13"], 0))
+    c.append(("early c.fsd", ["li    t0, -1", "sd    t0, 0(s0)", "fsd   f11, 0(s0)", "ld    t1, 0(s0)"], 0))
+    c.append(("early fsd", ["li    t0, -1", "sd    t0, 8(s0)", "fsd   f20, 8(s0)", "ld    t1, 8(s0)"], 0))
+    c.append(("early fsw", ["li    t0, -1", "sd    t0, 16(s0)", "fsw   f21, 16(s0)", "ld    t1, 16(s0)"],
+              0xFFFFFFFF00000000))
+    c.append(("early fsgnjn.d", ["fsgnjn.d f1, f22, f23", "fmv.x.d t1, f1"], 1 << 63))   # (the first FP write)
+    c.append(("after the first write", ["fmv.x.d t1, f24"], 0))
+    # fclass on the ten classes, and on improperly boxed s / h operands
+    cls = {"h": [0xFC00, 0xC200, 0x8001, 0x8000, 0x0000, 0x03FF, 0x7BFF, 0x7C00, 0x7C01, 0x7E00],
+           "s": [0xFF800000, 0xC0400000, 0x80000001, 0x80000000, 0, 0x007FFFFF, 0x7F7FFFFF, 0x7F800000, 0x7F800001,
+                 0x7FC00000],
+           "d": [0xFFF0000000000000, 0xC008000000000000, 0x8000000000000001, 0x8000000000000000, 0,
+                 0x000FFFFFFFFFFFFF, 0x7FEFFFFFFFFFFFFF, 0x7FF0000000000000, 0x7FF0000000000001,
+                 0x7FF8000000000000]}
+    for f in "hsd":
+        for k, v in enumerate(cls[f]):
+            reg_ = fmov_box(v, f)
+            assert fmov_class(fmov_unbox(reg_, f), f) == 1 << k
+            c.append((f"fclass.{f} class {k}", [f"li    t0, {reg_}", "fmv.d.x f1, t0", f"fclass.{f} t1, f1"], 1 << k))
+    for f, reg_ in (("s", 0x000000003F800000), ("s", 0xFFFFFFFE80000000), ("h", 0xFFFFFFFF0000FC00),
+                    ("h", 0x0000000000003C00), ("h", 0xFFFF7FFFFFFFFC00)):
+        c.append((f"fclass.{f} unboxed {reg_:#x}", [f"li    t0, {reg_}", "fmv.d.x f1, t0", f"fclass.{f} t1, f1"], 1 << 9))
+    # sign injection: the four sign pairs; rs1 improperly boxed; rs2 improperly boxed
+    mag = {"h": 0x3555, "s": 0x3FC12345, "d": 0x3FF123456789ABCD}
+    mag2 = {"h": 0x4ABC, "s": 0x41234567, "d": 0x4023456789ABCDEF}
+    for f in "hsd":
+        S = FP_SIGN[f]
+        pairs = [(fmov_box(mag[f] | sa, f), fmov_box(mag2[f] | sb, f)) for sa in (0, S) for sb in (0, S)]
+        if f != "d":   # (binary64 has no boxing: the raw bits are the value)
+            bad = (mag[f] | S) | (FP_BOX[f] & ~(1 << 40))
+            bad2 = (mag2[f] | S) | (FP_BOX[f] & ~(1 << 63))
+            pairs += [(bad, fmov_box(mag2[f] | S, f)), (bad, fmov_box(mag2[f], f)),
+                      (fmov_box(mag[f], f), bad2), (fmov_box(mag[f] | S, f), bad2)]
+        for op in ("fsgnj", "fsgnjn", "fsgnjx"):
+            for a, b in pairs:
+                x, y = fmov_unbox(a, f), fmov_unbox(b, f)
+                sg = {"fsgnj": y, "fsgnjn": ~y, "fsgnjx": x ^ y}[op]
+                want = fmov_box((x & (S - 1)) | (sg & S), f)
+                c.append((f"{op}.{f} {a:#x} {b:#x}", [f"li    t0, {a}", "fmv.d.x f1, t0", f"li    t0, {b}", "fmv.d.x f2, t0",
+                                                     f"{op}.{f} f3, f1, f2", "fmv.x.d t1, f3"], want))
+    # FP-to-int moves: the raw low bits, sign-extended, of improperly boxed registers
+    for v in (0x1234567889ABCDEF, 0xFFFFFFFF7BCD1234, 0x00000000800080FF, 0xFFFF0000FFFF7FFF):
+        c.append((f"fmv.x.w {v:#x}", [f"li    t0, {v}", "fmv.d.x f1, t0", "fmv.x.w t1, f1"], sx(v, 32) & M64))
+        c.append((f"fmv.x.h {v:#x}", [f"li    t0, {v}", "fmv.d.x f1, t0", "fmv.x.h t1, f1"], sx(v, 16) & M64))
+    # int-to-FP moves box
+    for v in (0x0123456789ABCDEF, 0xFEDCBA9876543210):
+        c.append((f"fmv.w.x {v:#x}", [f"li    t0, {v}", "fmv.w.x f1, t0", "fmv.x.d t1, f1"], fmov_box(v & M32, "s")))
+        c.append((f"fmv.h.x {v:#x}", [f"li    t0, {v}", "fmv.h.x f1, t0", "fmv.x.d t1, f1"], fmov_box(v & 0xFFFF, "h")))
+        c.append((f"fmv.d.x {v:#x}", [f"li    t0, {v}", "fmv.d.x f1, t0", "fmv.x.d t1, f1"], v))
+    # stores write the raw low bytes of an improperly boxed source; loads box
+    rng = random.Random(0xF30)
+    mem = bytearray(8192 + 8)
+    mem[0:24] = bytes(16) + bytes(4) + b"\xff" * 4   # (what the early cases left)
+    for st, w in (("fsh", 2), ("fsw", 4), ("fsd", 8)):
+        for off in FMOV_OFFS:
+            v = (rng.getrandbits(64) & ~(1 << 40)) | (1 << 15) | (1 << 31)
+            mem[off:off + w] = (v & ((1 << (8 * w)) - 1)).to_bytes(w, "little")
+            head = [f"li    t0, {v}", "fmv.d.x f1, t0", f"li    t3, {off}", "add   t3, t3, s0", f"{st}   f1, 0(t3)"]
+            for ld, lw, f in (("flh", 2, "h"), ("flw", 4, "s"), ("fld", 8, "d")):
+                want = fmov_box(int.from_bytes(mem[off:off + lw], "little"), f)
+                c.append((f"{st} {ld} at {off}", head + [f"{ld}   f4, 0(t3)", "fmv.x.d t1, f4"], want))
+                head = []
+    # the compressed forms (register and offset choices that compress: see
+    # test_fmov_program_on_oracle)
+    v1, v2 = 0x0F1E2D3C4B5A6978, 0x8796A5B4C3D2E1F0
+    c.append(("c.fsd", [f"li    t0, {v1}", "fmv.d.x f9, t0", "fsd   f9, 128(s0)", "ld    t1, 128(s0)"], v1))
+    c.append(("c.fld", ["fld   f10, 128(s0)", "fmv.x.d t1, f10"], v1))
+    c.append(("c.fsdsp", [f"li    t0, {v2}", "fmv.d.x f20, t0", "fsd   f20, 24(sp)", "ld    t1, 24(sp)"], v2))
+    c.append(("c.fldsp", ["fld   f21, 24(sp)", "fmv.x.d t1, f21"], v2))
+    return c
+
+
+# (name, operands as the assembler takes them, the oracle's mnemonic)
+FMOV_COMPRESSED = [("fsd", (11, 0, 8), "c_fsd"), ("fsd", (9, 128, 8), "c_fsd"), ("fld", (10, 128, 8), "c_fld"),
+                   ("fsd", (20, 24, 2), "c_fsdsp"), ("fld", (21, 24, 2), "c_fldsp")]
+
+
+def fmov_program_source() -> str:
+    cases = fmov_cases()
+    lines = ["    .text", "_start:", "    la    s0, buf", "    la    s2, out", "    addi  sp, s0, 512"]
+    for _, code, _ in cases:
+        lines += ["    " + ln for ln in code] + ["    sd    t1, 0(s2)", "    addi  s2, s2, 8"]
+    lines += ["    li    a0, 1", "    la    a1, out", f"    li    a2, {8 * len(cases)}", "    li    a7, 64", "    ecall",
+              "    li    a0, 0", "    li    a7, 93", "    ecall", "    .bss", "    .balign 4096", "buf:",
+              "    .zero 8192", "out:", f"    .zero {8 * len(cases)}"]
+    return "\n".join(lines) + "\n"
+
+
+def fmov_program_elf() -> bytes:
+    from tools.rvasm.rvasm import assemble
+    return assemble(fmov_program_source())
+
+
+def fmov_program_expected() -> bytes:
+    return b"".join((want & M64).to_bytes(8, "little") for _, _, want in fmov_cases())
+
+
+def test_fmov_program_on_oracle(oracle_mod):
+    from rvasm import try_compress
+    for name, ops, mnem in FMOV_COMPRESSED:   # the compressed cases are compressed
+        code = try_compress(name, ops)
+        assert code is not None and oracle_mod.mnemonic(code) == mnem, (name, ops)
+    o = oracle_mod.Oracle(fmov_program_elf(), "fmov")
+    g = o.run_golden()
+    assert g.exit_code == 0, g
+    got, exp = o.golden_stdout(), fmov_program_expected()
+    assert len(got) == len(exp)
+    for k, (name, _, want) in enumerate(fmov_cases()):
+        gv = int.from_bytes(got[8 * k:8 * k + 8], "little")
+        assert gv == want & M64, (k, name, hex(gv), hex(want))
