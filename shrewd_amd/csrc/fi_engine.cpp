@@ -20,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <random>
 #include <string>
@@ -63,18 +64,16 @@ hipError_t launch_hist(const fi_site *sites, const fi_outcome *out, uint64_t n, 
 hipError_t launch_hist_stats(const unsigned long long *stats, fi_histogram *h, hipStream_t st);
 hipError_t launch_exact_sites(const ExactPlan &p, uint64_t first, uint64_t n, const uint64_t *classes, fi_site *sites,
                               uint64_t *keys, uint32_t *perm, uint32_t *weight, hipStream_t st);
-hipError_t launch_exact_hist(const fi_site *sites, const fi_outcome *out, const uint32_t *weight, uint64_t n,
-                             fi_histogram *h, hipStream_t st);
+template <typename W>   // uint32_t or uint64_t weights (instantiated in fi_kernels.hip)
+hipError_t launch_exact_hist(const fi_site *sites, const fi_outcome *out, const W *weight, uint64_t n, fi_histogram *h,
+                             hipStream_t st);
 hipError_t launch_exact_profile(const ExactPlan &p, const ExactProfCtx &c, uint64_t first, uint64_t n, hipStream_t st);
 hipError_t launch_exact_consumers(const ExactPlan &p, const uint32_t *reg_cons, const uint32_t *inst_row,
                                   uint64_t first, uint64_t n, uint32_t *row, hipStream_t st);
-hipError_t launch_exact_dead(const ExactDead &d, fi_histogram *h, hipStream_t st);
+hipError_t launch_exact_untried(const ExactUntried &d, fi_histogram *h, hipStream_t st);
 hipError_t launch_exact_tick_sites(const ExactPlan &p, const TickMapCtx &c, uint64_t first, uint64_t n,
                                    const ExactTickClass *cls, fi_site *sites, uint64_t *keys, uint32_t *perm,
                                    fi_site *tsites, uint8_t *disp, fi_outcome *res, uint64_t *weight, hipStream_t st);
-hipError_t launch_exact_tick_hist(const fi_site *tsites, const fi_outcome *out, const uint64_t *weight, uint64_t n,
-                                  fi_histogram *h, hipStream_t st);
-hipError_t launch_exact_tick_dead(const ExactTickDead &d, fi_histogram *h, hipStream_t st);
 hipError_t launch_exact_mem_live(const ExactMemCtx &c, uint8_t *live, hipStream_t st);
 hipError_t launch_exact_mem_walk(const ExactMemCtx &c, const ExactMemRow *rows, uint32_t n_rows, const uint8_t *live,
                                  uint64_t *cnt, unsigned long long *wsum, ExactMemClass *cls, uint32_t emit,
@@ -371,32 +370,58 @@ struct Golden {
     DevBuf<TickRec> d_tk_rec;
 };
 
-// output capture (fi_run_sites_capture): on only while such a call runs (bytes != 0);
-// its buffers are grown on demand.  Rows alternate between the two chunks in flight like the site
-// and outcome buffers; the pinned staging mirrors them.
+// output capture (fi_run_sites_capture): on only while such a call runs (bytes != 0).
+// Its rows live in the chunk slots (ChunkSlot::cap), grown on demand (ensure_capture).
 struct Capture {
     uint32_t bytes = 0, stride = 0;   // bytes kept per stream; device row pitch (bytes rounded up to 16)
     uint64_t rows = 0;                // trials per chunk
     uint64_t held_b = 0, held_rows = 0;   // what is allocated: bytes per row buffer, entries per length buffer
-    DevBuf<uint8_t> d_out[2], d_err[2];
-    DevBuf<fi_stream_len> d_len[2];
-    PinBuf<uint8_t> h_out[2], h_err[2];
-    PinBuf<fi_stream_len> h_len[2];
     uint8_t *out = nullptr, *err = nullptr;   // the caller's arrays (err, lens may be NULL)
     fi_stream_len *lens = nullptr;
+};
+
+// a chunk's rows and lengths and their pinned mirror
+struct CaptureRows {
+    DevBuf<uint8_t> d_out, d_err;
+    DevBuf<fi_stream_len> d_len;
+    PinBuf<uint8_t> h_out, h_err;
+    PinBuf<fi_stream_len> h_len;
+};
+
+// Everything that alternates between the two chunks in flight (run_chunks): chunk i uses slot i & 1,
+// so that chunk i + 1 is filled and run while chunk i's second pass, tally and copies are still queued.
+struct ChunkSlot {
+    DevBuf<fi_site> d_sites;
+    DevBuf<fi_outcome> d_out;
+    DevBuf<uint32_t> d_weight;         // an exact chunk's weights: the sites each trial stands for
+    // the device tick map's buffers, [cap] each, made on first use (ensure_tick_work; Work::tk_ok): the
+    // tick sites in fi_site layout, the dispositions, the disp 1 / 2 outcomes, uploaded explicit sites
+    DevBuf<fi_site> d_tk_sites;
+    DevBuf<uint8_t> d_tk_disp;
+    DevBuf<fi_outcome> d_tk_res;
+    DevBuf<fi_tick_site> d_tk_in;
+    DevBuf<uint64_t> d_xt_weight;      // an exact tick chunk's weights, made on first use (ensure_exact_tick_work)
+    // the second pass (chunk_end): this slot's part of Work::d_redo_idx, d_redo_cnt and h_redo_cnt
+    uint32_t *redo_idx = nullptr, *redo_cnt = nullptr, *h_redo_cnt = nullptr;
+    // the redo count has reached h_redo_cnt / the outcomes have reached h_stage: fi_engine::ev_cnt,
+    // ev_stage, which fi_create makes and fi_destroy releases (the slots come and go with the work buffers)
+    hipEvent_t ev_cnt = nullptr, ev_stage = nullptr;
+    // pinned staging of the outcomes on their way to the caller's (pageable) array, made on first
+    // use (chunk_end): a copy straight into pageable memory would hold the host until the stream
+    // reaches it
+    PinBuf<fi_outcome> h_stage;
+    CaptureRows cap;                   // a capture call's (ensure_capture)
 };
 
 // Work buffers, sized for `cap` trials per launch (work_buffers); a larger
 // launch replaces them all.
 struct Work {
     uint64_t cap = 0;
-    DevBuf<fi_site> d_sites, d_sites_alt;   // the chunk being run / the one being finished
-    DevBuf<uint32_t> d_weight[2];           // an exact chunk's weights, alternating like the sites
+    ChunkSlot slot[2];
     DevBuf<uint64_t> d_keys, d_keys2;
     DevBuf<uint32_t> d_perm, d_perm2;
     DevBuf<uint8_t> d_tmp;
     size_t tmp_bytes = 0;
-    DevBuf<fi_outcome> d_out, d_out_alt;
     DevBuf<uint64_t> d_eff;          // effective inject time per trial (kFwDead: dead at injection)
     DevBuf<fi_histogram> d_hist;
     DevBuf<unsigned long long> d_stats;
@@ -419,23 +444,13 @@ struct Work {
     DevBuf<uint32_t> d_wrange, d_nwaves;   // packed resume (FI_CFG_PACK_RUNS)
     DevBuf<uint32_t> d_split;   // per epoch: odd-pc survivors, then the solo kernel's share of the list
     DevBuf<uint32_t> d_dmap;    // per slot: rewritten-code map (DevCtx::dmap, kDmapWords words)
-    // second pass of the trials that ran out of private pages (chunk_end): two of each, a chunk and its predecessor
+    // second pass of the trials that ran out of private pages (chunk_end): the lists and counts of
+    // both chunk slots (ChunkSlot::redo_*), one pass's sites and outcomes
     DevBuf<uint32_t> d_redo_idx, d_redo_cnt;
     PinBuf<uint32_t> h_redo_cnt;
     DevBuf<fi_site> d_redo_sites;
     DevBuf<fi_outcome> d_redo_out;
-    // pinned staging of a chunk's outcomes on their way to the caller's (pageable) array, made on
-    // first use (chunk_end): a copy straight into pageable memory would hold the host until the
-    // stream reaches it
-    PinBuf<fi_outcome> h_stage[2];
-    // the device tick map's buffers (ensure_tick_work), [cap] each: the tick sites in fi_site
-    // layout, the dispositions, the disp 1 / 2 outcomes, uploaded explicit sites
-    bool tk_ok = false;
-    DevBuf<fi_site> d_tk_sites[2];
-    DevBuf<uint8_t> d_tk_disp[2];
-    DevBuf<fi_outcome> d_tk_res[2];
-    DevBuf<fi_tick_site> d_tk_in[2];
-    DevBuf<uint64_t> d_xt_weight[2];   // an exact tick chunk's weights (ensure_exact_tick_work), [cap] each
+    bool tk_ok = false;         // both slots have the device tick map's buffers
     Capture cx;
 };
 
@@ -447,8 +462,7 @@ struct fi_engine {
     // solo-odd kernel runs beside the solo kernel on its own stream
     hipStream_t stream = nullptr, stream_odd = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_fork = nullptr, ev_join = nullptr;
-    hipEvent_t ev_cnt[2] = {nullptr, nullptr};     // a chunk's redo count has reached h_redo_cnt
-    hipEvent_t ev_stage[2] = {nullptr, nullptr};   // a chunk's outcomes have reached h_stage
+    hipEvent_t ev_cnt[2] = {nullptr, nullptr}, ev_stage[2] = {nullptr, nullptr};   // the chunk slots' (ChunkSlot)
     double last_ms = 0;
     // per-launch timing of the interpreter kernel (bench roofline)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> tpool;
@@ -546,18 +560,17 @@ static fi_status work_buffers(fi_engine *e, Work &w, uint64_t c, uint64_t *count
         return count ? hipSuccess : b.alloc(n);
     };
     const uint64_t P = e->cfg.private_pages, P2 = redo_pages(P);
-    HIPCHK(buf(w.d_sites, c));
-    HIPCHK(buf(w.d_sites_alt, c));
-    HIPCHK(buf(w.d_weight[0], c));
-    HIPCHK(buf(w.d_weight[1], c));
+    for (ChunkSlot &s : w.slot) {
+        HIPCHK(buf(s.d_sites, c));
+        HIPCHK(buf(s.d_weight, c));
+        HIPCHK(buf(s.d_out, c));
+    }
     HIPCHK(buf(w.d_keys, c));
     HIPCHK(buf(w.d_keys2, c));
     HIPCHK(buf(w.d_perm, c));
     HIPCHK(buf(w.d_perm2, c));
     HIPCHK(sort_pairs_bytes(c, w.tmp_bytes));
     HIPCHK(buf(w.d_tmp, std::max<size_t>(w.tmp_bytes, 16)));
-    HIPCHK(buf(w.d_out, c));
-    HIPCHK(buf(w.d_out_alt, c));
     HIPCHK(buf(w.d_eff, c));
     HIPCHK(buf(w.d_hist, 1));
     HIPCHK(buf(w.d_stats, kNStats));
@@ -586,6 +599,11 @@ static fi_status work_buffers(fi_engine *e, Work &w, uint64_t c, uint64_t *count
     // (the pinned staging of host-bound outcomes is made on first use:
     // chunk_end; device-resident runs never need it)
     if (!count) HIPCHK(w.h_redo_cnt.alloc(4));
+    for (uint32_t i = 0; i < 2 && !count; i++) {
+        ChunkSlot &s = w.slot[i];
+        s.redo_idx = w.d_redo_idx + i * c; s.redo_cnt = w.d_redo_cnt + i; s.h_redo_cnt = w.h_redo_cnt + i;
+        s.ev_cnt = e->ev_cnt[i]; s.ev_stage = e->ev_stage[i];
+    }
     // overflow pool: a trial past P pages takes a block of P' - P more (P' the
     // redo pass's page count), one block per 2048 slots (at least 64)
     if (!(e->cfg.flags & FI_CFG_NO_OVERFLOW) && P2 > P) {
@@ -1078,6 +1096,23 @@ static fi_status ensure_work(fi_engine *e, uint64_t n) {
     if (!st) e->w = std::move(w);
     return st;
 }
+// ... for a call of n trials: one launch's worth, at least one slot
+static fi_status ensure_work_for(fi_engine *e, uint64_t n) {
+    return ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch));
+}
+
+// n entries in pieces of at most e->w.cap: fn(done, k) enqueues a piece's launch and copies on
+// e->stream, which is then waited for (the calls that borrow chunk slot 0 outside a run)
+static fi_status for_chunks(fi_engine *e, uint64_t n, const std::function<fi_status(uint64_t, uint64_t)> &fn) {
+    for (uint64_t done = 0; done < n;) {
+        const uint64_t k = std::min<uint64_t>(n - done, e->w.cap);
+        const fi_status s = fn(done, k);
+        if (s) return s;
+        HIPCHK(hipStreamSynchronize(e->stream));
+        done += k;
+    }
+    return FI_OK;
+}
 
 // The rewritten-code map's granule: one byte, coarser for large code so that
 // a slot's map stays within kDmapWords x 32 bits (the solo kernel's LDS
@@ -1178,7 +1213,7 @@ static fi_status golden_launch(fi_engine *e, uint32_t P, const GoldenRec &r, fi_
     c.rec_trace = r.trace; c.rec_trace_cap = r.trace ? r.trace_cap : 0;
     c.rec_mem = r.mem; c.rec_mem_cap = r.mem ? r.mem_cap : 0;
     c.mem_live = 0;
-    c.out = e->w.d_out;
+    c.out = e->w.slot[0].d_out;   // (borrowed: no run is in flight)
     c.n = 1;
     c.n_slots = 1;
     c.sites = nullptr; c.perm = nullptr;
@@ -1190,7 +1225,7 @@ static fi_status golden_launch(fi_engine *e, uint32_t P, const GoldenRec &r, fi_
     GLCHK(hipStreamSynchronize(e->stream));
     float ms = 0;
     GLCHK(hipEventElapsedTime(&ms, e->ev0, e->ev1));
-    GLCHK(hipMemcpy(&o, e->w.d_out, sizeof o, hipMemcpyDeviceToHost));
+    GLCHK(hipMemcpy(&o, e->w.slot[0].d_out, sizeof o, hipMemcpyDeviceToHost));
     GLCHK(hipMemcpy(stats, e->w.d_stats, kNStats * sizeof(unsigned long long), hipMemcpyDeviceToHost));
 #undef GLCHK
     e->last_ms = ms;
@@ -1696,17 +1731,14 @@ fi_status fi_sample_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site *out
     if (!e->gold.have_golden) return fail(e, FI_E_STATE, "golden run required before sampling");
     if (!e->structures) return fail(e, FI_E_STATE, "fi_set_campaign first");
     HIPCHK(hipSetDevice(e->dev));
-    const uint64_t chunk = e->cfg.max_trials_per_launch;
-    fi_status st = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), chunk));
+    const fi_status st = ensure_work_for(e, n);
     if (st) return st;
-    for (uint64_t done = 0; done < n;) {
-        const uint64_t k = std::min<uint64_t>(n - done, e->w.cap);
-        HIPCHK(launch_sample(sample_ctx(e, first + done), k, e->w.d_sites, e->w.d_keys, e->w.d_perm, e->stream));
-        HIPCHK(hipMemcpyAsync(out + done, e->w.d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        done += k;
-    }
-    return FI_OK;
+    return for_chunks(e, n, [&](uint64_t done, uint64_t k) -> fi_status {
+        const ChunkSlot &s0 = e->w.slot[0];
+        HIPCHK(launch_sample(sample_ctx(e, first + done), k, s0.d_sites, e->w.d_keys, e->w.d_perm, e->stream));
+        HIPCHK(hipMemcpyAsync(out + done, s0.d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        return FI_OK;
+    });
 }
 
 // The trial kernel: the load-time build with translated blocks when there is
@@ -1746,10 +1778,11 @@ static std::pair<hipEvent_t, hipEvent_t> &timer_slot(fi_engine *e, uint32_t kind
 // AtomicSimpleCPU's, so a curTick read escapes (DevCtx::clk_esc).
 // disp (device-mapped chunks, else NULL): trials with disp[i] != 0 are parked --
 // dead at injection, so the trial kernels end them at once as the golden run.
-// cslot (a capture call's chunks, else -1): the trials' output goes to that
-// pair of capture buffers, trial i of sites to row cidx[i] (NULL: row i).
+// cs (a capture call's chunks, else NULL): the trials' output goes to that
+// slot's capture buffers, trial i of sites to row cidx[i] (NULL: row i).
 static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *d_out, uint32_t P, hipStream_t st,
-                          bool tick, const uint8_t *disp = nullptr, int cslot = -1, const uint32_t *cidx = nullptr) {
+                          bool tick, const uint8_t *disp = nullptr, const ChunkSlot *cs = nullptr,
+                          const uint32_t *cidx = nullptr) {
     int end_bit = 64 - __builtin_clzll(std::max<uint64_t>(e->gold.info.ninst, 1));
     // (a dead site ends at injection: an early exit, so not with FI_CFG_NO_EARLY_EXIT)
     const bool fwd = e->gold.fw_ok && !(e->cfg.flags & (FI_CFG_NO_FORWARD | FI_CFG_NO_EARLY_EXIT));
@@ -1778,8 +1811,8 @@ static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *
     c.save = e->w.d_save;
     c.priv_pages = P;
     c.clk_esc = tick ? 1u : 0u;
-    if (cslot >= 0) {
-        c.cap_out = e->w.cx.d_out[cslot]; c.cap_err = e->w.cx.d_err[cslot]; c.cap_len = e->w.cx.d_len[cslot];
+    if (cs) {
+        c.cap_out = cs->cap.d_out; c.cap_err = cs->cap.d_err; c.cap_len = cs->cap.d_len;
         c.cap_idx = cidx;
         c.cap_bytes = e->w.cx.bytes; c.cap_stride = e->w.cx.stride;
     }
@@ -1893,117 +1926,31 @@ static fi_status run_pass(fi_engine *e, fi_site *sites, uint64_t k, fi_outcome *
 // is busy with chunk i+1.  Chunk i's second pass (redo_pages-fold pages, in
 // batches that reuse the same frames: batch x P' <= k x P), its histogram and
 // its host copy follow chunk i+1 on the stream; their outcomes replace the
-// escapes.  Sites and outcome buffers alternate between the two chunks in
-// flight.  FI_CFG_NO_REDO keeps the escapes.
-struct Chunk {
-    uint64_t k = 0;
-    fi_site *sites = nullptr;
-    fi_outcome *out = nullptr;
-    fi_outcome *host_out = nullptr;   // run_common: where the outcomes go on the host
-    bool tick = false;                // its sites are mapped tick sites (run_pass)
-    // a chunk mapped on the device (else NULL): the tick sites as fi_site, dispositions, disp 1 / 2 outcomes
-    const fi_site *tsites = nullptr;
-    const uint8_t *disp = nullptr;
-    const fi_outcome *res = nullptr;
-    const uint32_t *weight = nullptr; // an exact chunk: the sites each trial stands for (the weighted histogram)
-    const uint64_t *tweight = nullptr; // an exact tick chunk: the ticks each trial stands for
-    const ExactPlan *prof = nullptr;  // ... of a profiled call: its plan, and the chunk's first trial
+// escapes.  The two chunks in flight alternate between the two ChunkSlots.
+// FI_CFG_NO_REDO keeps the escapes.
+
+// How chunk_end tallies a chunk; chunk_fill records it.
+struct Tally {
+    // the site array that keys the histogram: the run sites, or -- a chunk mapped on the device, whose
+    // disp != 0 trials are parked (run_pass) and fixed (chunk_end) -- the tick sites
+    enum Key { kRunSites, kTickSites } key = kRunSites;
+    enum Weight { kNone, kW32, kW64 } weight = kNone;   // unweighted, ChunkSlot::d_weight, ChunkSlot::d_xt_weight
+    const ExactPlan *prof = nullptr;   // the profile kernel follows (else NULL): the plan, the chunk's first trial
     uint64_t prof_first = 0;
-    uint32_t slot = 0;                // redo list / count / event pair
-    uint64_t off = 0;                 // a capture call: the chunk's first trial (row of the caller's arrays)
-    bool capture = false;             //   and its output goes to the capture buffers of `slot`
 };
 
-static fi_status chunk_begin(fi_engine *e, const Chunk &ch, hipStream_t st) {
-    if (ch.capture) {   // every row = the golden stream (the prefix and golden-suffix rules, DESIGN.md §4i)
-        const Capture &x = e->w.cx;
-        HIPCHK(launch_capture_init(x.d_out[ch.slot], ch.k, x.stride, x.bytes, e->gold.d_gout, e->gold.gout.size(), st));
-        HIPCHK(launch_capture_init(x.d_err[ch.slot], ch.k, x.stride, x.bytes, e->gold.d_gerr, e->gold.gerr.size(), st));
-    }
-    fi_status s = run_pass(e, ch.sites, ch.k, ch.out, e->cfg.private_pages, st, ch.tick, ch.disp,
-                           ch.capture ? (int)ch.slot : -1);
-    if (s) return s;
-    if (!(e->cfg.flags & FI_CFG_NO_REDO)) {
-        uint32_t *cnt = e->w.d_redo_cnt + ch.slot;
-        HIPCHK(hipMemsetAsync(cnt, 0, 4, st));
-        HIPCHK(launch_redo_collect(ch.out, ch.k, e->w.d_redo_idx + ch.slot * e->w.cap, cnt, e->w.d_stats, st));
-        HIPCHK(hipMemcpyAsync(e->w.h_redo_cnt + ch.slot, cnt, 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipEventRecord(e->ev_cnt[ch.slot], st));
-    }
-    return FI_OK;
-}
-
-static fi_status chunk_end(fi_engine *e, const Chunk &ch, fi_histogram *d_hist, hipStream_t st) {
-    if (!(e->cfg.flags & FI_CFG_NO_REDO)) {
-        HIPCHK(hipEventSynchronize(e->ev_cnt[ch.slot]));   // (normally long done: a chunk later was enqueued first)
-        const uint64_t nr = e->w.h_redo_cnt[ch.slot];
-        const uint32_t *idx = e->w.d_redo_idx + ch.slot * e->w.cap;
-        if (nr) {
-            const uint64_t P = e->cfg.private_pages;
-            const uint64_t pool = e->w.cap * P;   // page frames a pass has
-            const uint64_t P2 = std::min<uint64_t>(pool, redo_pages(P));
-            const uint64_t B = std::max<uint64_t>(1, pool / P2);
-            for (uint64_t d = 0; d < nr; d += B) {
-                const uint64_t b = std::min(B, nr - d);
-                HIPCHK(launch_redo_gather(ch.sites, idx + d, b, e->w.d_redo_sites, e->w.d_keys, e->w.d_perm, st));
-                // (capture: the same deterministic run, only longer, into the trial's own row again)
-                fi_status s = run_pass(e, e->w.d_redo_sites, b, e->w.d_redo_out, (uint32_t)P2, st, ch.tick, nullptr,
-                                       ch.capture ? (int)ch.slot : -1, idx + d);
-                if (s) return s;
-                HIPCHK(launch_redo_scatter(idx + d, b, e->w.d_redo_out, ch.out, st));
-            }
-        }
-    }
-    // (a redo trial is never a parked one: those end masked, not as resource escapes)
-    if (ch.disp) HIPCHK(launch_tick_fix(ch.disp, ch.res, ch.k, ch.out, st));
-    if (ch.prof) {   // (an exact chunk: after its histogram)
-        const ExProf &x = e->gold.xp;
-        const ExactProfCtx c{x.d_reg_cons, x.d_inst_row, ch.out, ch.weight, x.d_bins, (uint32_t)x.rows.size(), e->prof_variant};
-        HIPCHK(launch_exact_hist(ch.sites, ch.out, ch.weight, ch.k, d_hist, st));
-        HIPCHK(launch_exact_profile(*ch.prof, c, ch.prof_first, ch.k, st));
-    } else if (ch.weight) HIPCHK(launch_exact_hist(ch.sites, ch.out, ch.weight, ch.k, d_hist, st));
-    else if (ch.tweight) HIPCHK(launch_exact_tick_hist(ch.tsites, ch.out, ch.tweight, ch.k, d_hist, st));
-    else HIPCHK(launch_hist(ch.tsites ? ch.tsites : ch.sites, ch.out, ch.k, d_hist, nullptr, st));
-    if (ch.host_out) {
-        if (!e->w.h_stage[ch.slot]) HIPCHK(e->w.h_stage[ch.slot].alloc(e->w.cap));
-        HIPCHK(hipMemcpyAsync(e->w.h_stage[ch.slot], ch.out, ch.k * sizeof(fi_outcome), hipMemcpyDeviceToHost, st));
-        if (ch.capture) {   // zeros past each stream's end, then rows and lengths to their staging
-            const Capture &x = e->w.cx;
-            const uint32_t sl = ch.slot;
-            HIPCHK(launch_capture_finish(x.d_out[sl], ch.k, x.stride, x.bytes, x.d_len[sl], 0u, st));
-            HIPCHK(hipMemcpyAsync(x.h_out[sl], x.d_out[sl], ch.k * x.stride, hipMemcpyDeviceToHost, st));
-            if (x.err) {
-                HIPCHK(launch_capture_finish(x.d_err[sl], ch.k, x.stride, x.bytes, x.d_len[sl], 1u, st));
-                HIPCHK(hipMemcpyAsync(x.h_err[sl], x.d_err[sl], ch.k * x.stride, hipMemcpyDeviceToHost, st));
-            }
-            if (x.lens)
-                HIPCHK(hipMemcpyAsync(x.h_len[sl], x.d_len[sl], ch.k * sizeof(fi_stream_len), hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK(hipEventRecord(e->ev_stage[ch.slot], st));
-    }
-    return FI_OK;
-}
-
-// A chunk's staged outcomes to the caller's array, once their copy has landed.
-static fi_status chunk_deliver(fi_engine *e, Chunk &ch) {
-    if (!ch.host_out || !ch.k) return FI_OK;
-    HIPCHK(hipEventSynchronize(e->ev_stage[ch.slot]));
-    memcpy(ch.host_out, e->w.h_stage[ch.slot], ch.k * sizeof(fi_outcome));
-    if (ch.capture) {
-        const Capture &x = e->w.cx;
-        capture_rows(x.out + ch.off * x.bytes, x.h_out[ch.slot], ch.k, x.bytes, x.stride);
-        if (x.err) capture_rows(x.err + ch.off * x.bytes, x.h_err[ch.slot], ch.k, x.bytes, x.stride);
-        if (x.lens) memcpy(x.lens + ch.off, x.h_len[ch.slot], ch.k * sizeof(fi_stream_len));
-    }
-    ch.k = 0;
-    return FI_OK;
-}
-
-static void hist_add(fi_histogram *dst, const fi_histogram *src) {
-    const uint64_t *s = (const uint64_t *)src;
-    uint64_t *d = (uint64_t *)dst;
-    for (size_t i = 0; i < sizeof(fi_histogram) / 8; i++) d[i] += s[i];
-}
+struct Chunk {
+    uint64_t k = 0;
+    ChunkSlot *s = nullptr;
+    uint64_t off = 0;                 // its first entry in the call's arrays
+    fi_outcome *out_dev = nullptr;    // its part of the caller's device array (NULL: the outcomes stay in the slot)
+    fi_outcome *host_out = nullptr;   // where the outcomes go on the host (NULL: nowhere)
+    bool tick = false;                // its sites are mapped tick sites (run_pass)
+    bool capture = false;             // a capture call's: its output goes to the slot's capture buffers
+    Tally tally;
+    fi_outcome *out() const { return out_dev ? out_dev : s->d_out.get(); }
+    const uint8_t *disp() const { return tally.key == Tally::kTickSites ? s->d_tk_disp.get() : nullptr; }
+};
 
 // The device map's arguments: the packed table, the campaign's draw, the
 // golden outcome.  in = uploaded explicit sites (NULL: sample from `first`).
@@ -2018,86 +1965,215 @@ static TickMapCtx tick_map_ctx(fi_engine *e, uint64_t first, const fi_tick_site 
     return c;
 }
 
-// Where a run's sites come from: given (host arrays of n entries), or sampled
-// on the device as trials first, first + 1, ...  A tick run's sites are tick
-// sites: mapped by the caller (sites) or, in the sampler's place, on the
-// device (ticks / sampled).  exact: trials first, first + 1, ... of that plan,
-// enumerated on the device in the sampler's place (fi_run_exact).
+// Where a run's sites come from: one kind and the payload that kind needs.
 struct SiteSource {
-    const fi_site *sites = nullptr;
-    const fi_tick_site *ticks = nullptr;
-    bool sampled = false;
-    bool tick = false;
-    const ExactPlan *exact = nullptr;
-    bool profile = false;             // ... with the profile (fi_run_exact_profile)
-    // ... of a tick campaign (fi_run_exact_ticks; with tick and exact set): the class records
-    const ExactTickClass *tick_cls = nullptr;
+    enum Kind {
+        kSampled,        // trials first, first + 1, ... drawn on the device
+        kGiven,          // sites: the caller's, a host array of n
+        kMapped,         // sites: the host map's, made of tick sites (fi_run_tick_sites)
+        kSampledTicks,   // tick sites drawn and mapped on the device, the mapper in the sampler's place
+        kGivenTicks,     // ticks: the caller's tick sites, a host array of n, mapped on the device
+        kExact,          // trials first, first + 1, ... of plan, enumerated on the device (fi_run_exact)
+        kExactProfile,   // ... with the profile (fi_run_exact_profile)
+        kExactTicks,     // ... of a tick campaign's plan and class records cls (fi_run_exact_ticks)
+    };
+    Kind kind;
+    const fi_site *sites;
+    const fi_tick_site *ticks;
+    const ExactPlan *plan;
+    const ExactTickClass *cls;
+
+    static SiteSource sampled() { return {kSampled, nullptr, nullptr, nullptr, nullptr}; }
+    static SiteSource given(const fi_site *sites) { return {kGiven, sites, nullptr, nullptr, nullptr}; }
+    static SiteSource mapped(const fi_site *sites) { return {kMapped, sites, nullptr, nullptr, nullptr}; }
+    static SiteSource sampled_ticks() { return {kSampledTicks, nullptr, nullptr, nullptr, nullptr}; }
+    static SiteSource given_ticks(const fi_tick_site *ticks) { return {kGivenTicks, nullptr, ticks, nullptr, nullptr}; }
+    static SiteSource exact(const ExactPlan *plan, bool profile) {
+        return {profile ? kExactProfile : kExact, nullptr, nullptr, plan, nullptr};
+    }
+    static SiteSource exact_ticks(const ExactPlan *plan, const ExactTickClass *cls) {
+        return {kExactTicks, nullptr, nullptr, plan, cls};
+    }
+    // its sites are mapped tick sites: this engine's clock is AtomicSimpleCPU's (run_pass)
+    bool tick() const { return kind == kMapped || kind == kSampledTicks || kind == kGivenTicks || kind == kExactTicks; }
 };
+
+// The chunk's sites, keys and perm into its slot and the work buffers -- trial
+// `first` on, or entries ch.off on of the source's array -- and how it is to be
+// tallied into ch.tally.
+static fi_status chunk_fill(fi_engine *e, const SiteSource &src, uint64_t first, Chunk &ch, hipStream_t st) {
+    ChunkSlot &s = *ch.s;
+    Work &w = e->w;
+    ch.tick = src.tick();
+    switch (src.kind) {
+    case SiteSource::kSampled:
+        HIPCHK(launch_sample(sample_ctx(e, first), ch.k, s.d_sites, w.d_keys, w.d_perm, st));
+        break;
+    case SiteSource::kGiven:
+    case SiteSource::kMapped:
+        HIPCHK(hipMemcpyAsync(s.d_sites, src.sites + ch.off, ch.k * sizeof(fi_site), hipMemcpyHostToDevice, st));
+        HIPCHK(launch_keys(s.d_sites, ch.k, w.d_keys, w.d_perm, st));
+        break;
+    case SiteSource::kGivenTicks:
+        HIPCHK(hipMemcpyAsync(s.d_tk_in, src.ticks + ch.off, ch.k * sizeof(fi_tick_site), hipMemcpyHostToDevice, st));
+        [[fallthrough]];
+    case SiteSource::kSampledTicks:   // tick sites: the mapper takes the sampler's place
+        ch.tally.key = Tally::kTickSites;
+        HIPCHK(launch_tick_map(tick_map_ctx(e, first, src.ticks ? s.d_tk_in.get() : nullptr), ch.k, s.d_sites, w.d_keys,
+                               w.d_perm, s.d_tk_sites, s.d_tk_disp, s.d_tk_res, st));
+        break;
+    case SiteSource::kExactProfile:
+        ch.tally.prof = src.plan; ch.tally.prof_first = first;
+        [[fallthrough]];
+    case SiteSource::kExact:
+        ch.tally.weight = Tally::kW32;
+        HIPCHK(launch_exact_sites(*src.plan, first, ch.k, e->gold.d_ex_classes, s.d_sites, w.d_keys, w.d_perm, s.d_weight, st));
+        break;
+    case SiteSource::kExactTicks:   // parked and fixed as mapped tick sites are
+        ch.tally.key = Tally::kTickSites;
+        ch.tally.weight = Tally::kW64;
+        HIPCHK(launch_exact_tick_sites(*src.plan, tick_map_ctx(e, 0, nullptr), first, ch.k, src.cls, s.d_sites, w.d_keys,
+                                       w.d_perm, s.d_tk_sites, s.d_tk_disp, s.d_tk_res, s.d_xt_weight, st));
+        break;
+    }
+    return FI_OK;
+}
+
+static fi_status chunk_begin(fi_engine *e, const Chunk &ch, hipStream_t st) {
+    const ChunkSlot &s = *ch.s;
+    if (ch.capture) {   // every row = the golden stream (the prefix and golden-suffix rules, DESIGN.md §4i)
+        const Capture &x = e->w.cx;
+        HIPCHK(launch_capture_init(s.cap.d_out, ch.k, x.stride, x.bytes, e->gold.d_gout, e->gold.gout.size(), st));
+        HIPCHK(launch_capture_init(s.cap.d_err, ch.k, x.stride, x.bytes, e->gold.d_gerr, e->gold.gerr.size(), st));
+    }
+    fi_status st2 = run_pass(e, s.d_sites, ch.k, ch.out(), e->cfg.private_pages, st, ch.tick, ch.disp(),
+                             ch.capture ? &s : nullptr);
+    if (st2) return st2;
+    if (!(e->cfg.flags & FI_CFG_NO_REDO)) {
+        HIPCHK(hipMemsetAsync(s.redo_cnt, 0, 4, st));
+        HIPCHK(launch_redo_collect(ch.out(), ch.k, s.redo_idx, s.redo_cnt, e->w.d_stats, st));
+        HIPCHK(hipMemcpyAsync(s.h_redo_cnt, s.redo_cnt, 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipEventRecord(s.ev_cnt, st));
+    }
+    return FI_OK;
+}
+
+static fi_status chunk_end(fi_engine *e, const Chunk &ch, fi_histogram *d_hist, hipStream_t st) {
+    ChunkSlot &s = *ch.s;
+    fi_outcome *out = ch.out();
+    if (!(e->cfg.flags & FI_CFG_NO_REDO)) {
+        HIPCHK(hipEventSynchronize(s.ev_cnt));   // (normally long done: a chunk later was enqueued first)
+        const uint64_t nr = *s.h_redo_cnt;
+        const uint32_t *idx = s.redo_idx;
+        if (nr) {
+            const uint64_t P = e->cfg.private_pages;
+            const uint64_t pool = e->w.cap * P;   // page frames a pass has
+            const uint64_t P2 = std::min<uint64_t>(pool, redo_pages(P));
+            const uint64_t B = std::max<uint64_t>(1, pool / P2);
+            for (uint64_t d = 0; d < nr; d += B) {
+                const uint64_t b = std::min(B, nr - d);
+                HIPCHK(launch_redo_gather(s.d_sites, idx + d, b, e->w.d_redo_sites, e->w.d_keys, e->w.d_perm, st));
+                // (capture: the same deterministic run, only longer, into the trial's own row again)
+                fi_status st2 = run_pass(e, e->w.d_redo_sites, b, e->w.d_redo_out, (uint32_t)P2, st, ch.tick, nullptr,
+                                         ch.capture ? &s : nullptr, idx + d);
+                if (st2) return st2;
+                HIPCHK(launch_redo_scatter(idx + d, b, e->w.d_redo_out, out, st));
+            }
+        }
+    }
+    // (a redo trial is never a parked one: those end masked, not as resource escapes)
+    if (ch.disp()) HIPCHK(launch_tick_fix(ch.disp(), s.d_tk_res, ch.k, out, st));
+    const fi_site *key = ch.tally.key == Tally::kTickSites ? s.d_tk_sites : s.d_sites;
+    switch (ch.tally.weight) {
+    case Tally::kNone: HIPCHK(launch_hist(key, out, ch.k, d_hist, nullptr, st)); break;
+    case Tally::kW32: HIPCHK(launch_exact_hist(key, out, s.d_weight.get(), ch.k, d_hist, st)); break;
+    case Tally::kW64: HIPCHK(launch_exact_hist(key, out, s.d_xt_weight.get(), ch.k, d_hist, st)); break;
+    }
+    if (ch.tally.prof) {   // (an exact chunk: after its histogram)
+        const ExProf &x = e->gold.xp;
+        const ExactProfCtx c{x.d_reg_cons, x.d_inst_row, out, s.d_weight, x.d_bins, (uint32_t)x.rows.size(), e->prof_variant};
+        HIPCHK(launch_exact_profile(*ch.tally.prof, c, ch.tally.prof_first, ch.k, st));
+    }
+    if (ch.host_out) {
+        if (!s.h_stage) HIPCHK(s.h_stage.alloc(e->w.cap));
+        HIPCHK(hipMemcpyAsync(s.h_stage, out, ch.k * sizeof(fi_outcome), hipMemcpyDeviceToHost, st));
+        if (ch.capture) {   // zeros past each stream's end, then rows and lengths to their staging
+            const Capture &x = e->w.cx;
+            HIPCHK(launch_capture_finish(s.cap.d_out, ch.k, x.stride, x.bytes, s.cap.d_len, 0u, st));
+            HIPCHK(hipMemcpyAsync(s.cap.h_out, s.cap.d_out, ch.k * x.stride, hipMemcpyDeviceToHost, st));
+            if (x.err) {
+                HIPCHK(launch_capture_finish(s.cap.d_err, ch.k, x.stride, x.bytes, s.cap.d_len, 1u, st));
+                HIPCHK(hipMemcpyAsync(s.cap.h_err, s.cap.d_err, ch.k * x.stride, hipMemcpyDeviceToHost, st));
+            }
+            if (x.lens)
+                HIPCHK(hipMemcpyAsync(s.cap.h_len, s.cap.d_len, ch.k * sizeof(fi_stream_len), hipMemcpyDeviceToHost, st));
+        }
+        HIPCHK(hipEventRecord(s.ev_stage, st));
+    }
+    return FI_OK;
+}
+
+// A chunk's staged outcomes to the caller's array, once their copy has landed.
+static fi_status chunk_deliver(fi_engine *e, Chunk &ch) {
+    if (!ch.host_out || !ch.k) return FI_OK;
+    const ChunkSlot &s = *ch.s;
+    HIPCHK(hipEventSynchronize(s.ev_stage));
+    memcpy(ch.host_out, s.h_stage, ch.k * sizeof(fi_outcome));
+    if (ch.capture) {
+        const Capture &x = e->w.cx;
+        capture_rows(x.out + ch.off * x.bytes, s.cap.h_out, ch.k, x.bytes, x.stride);
+        if (x.err) capture_rows(x.err + ch.off * x.bytes, s.cap.h_err, ch.k, x.bytes, x.stride);
+        if (x.lens) memcpy(x.lens + ch.off, s.cap.h_len, ch.k * sizeof(fi_stream_len));
+    }
+    ch.k = 0;
+    return FI_OK;
+}
+
+static void hist_add(fi_histogram *dst, const fi_histogram *src) {
+    const uint64_t *s = (const uint64_t *)src;
+    uint64_t *d = (uint64_t *)dst;
+    for (size_t i = 0; i < sizeof(fi_histogram) / 8; i++) d[i] += s[i];
+}
 
 // Trials [first, first + n) or the given sites (src), in chunks of at most
 // e->w.cap; outcomes to out_dev (device, n entries) or out_host (through the
-// alternating device buffers), histogram added to d_hist.  The event pair
+// slots' device buffers), histogram added to d_hist.  The event pair
 // ev0 / ev1 spans the whole call.
 static fi_status run_chunks(fi_engine *e, uint64_t first, const SiteSource &src, uint64_t n, fi_outcome *out_dev,
                             fi_outcome *out_host, fi_histogram *d_hist, hipStream_t st) {
     HIPCHK(hipMemsetAsync(e->w.d_stats, 0, kNStats * sizeof(unsigned long long), st));
     HIPCHK(hipEventRecord(e->ev0, st));
-    Chunk prev, staged[2];   // (staged: chunks whose outcomes still sit in h_stage)
+    Chunk prev, staged[2];   // (staged: per slot, the chunk whose outcomes still sit in h_stage)
     bool have_prev = false;
     uint32_t i = 0;
     for (uint64_t done = 0; done < n; i++) {
         jit_install(e, st, false);   // the translated kernels, once their build has landed
         Chunk ch;
         ch.k = std::min<uint64_t>({n - done, e->w.cap, e->gold.jit ? kJitWindowChunk : e->w.cap});
-        if (e->w.cx.bytes) { ch.k = std::min(ch.k, e->w.cx.rows); ch.capture = true; ch.off = done; }
-        ch.slot = i & 1;
-        ch.sites = ch.slot ? e->w.d_sites_alt : e->w.d_sites;
-        ch.out = out_dev ? out_dev + done : ch.slot ? e->w.d_out_alt : e->w.d_out;
+        if (e->w.cx.bytes) { ch.k = std::min(ch.k, e->w.cx.rows); ch.capture = true; }
+        ch.s = &e->w.slot[i & 1];
+        ch.off = done;
+        ch.out_dev = out_dev ? out_dev + done : nullptr;
         ch.host_out = out_host ? out_host + done : nullptr;
-        ch.tick = src.tick;
-        if (src.sites) {
-            HIPCHK(hipMemcpyAsync(ch.sites, src.sites + done, ch.k * sizeof(fi_site), hipMemcpyHostToDevice, st));
-            HIPCHK(launch_keys(ch.sites, ch.k, e->w.d_keys, e->w.d_perm, st));
-        } else if (src.tick_cls) {   // exact tick trials: parked and fixed as mapped tick sites are
-            ch.tsites = e->w.d_tk_sites[ch.slot]; ch.disp = e->w.d_tk_disp[ch.slot]; ch.res = e->w.d_tk_res[ch.slot];
-            ch.tweight = e->w.d_xt_weight[ch.slot];
-            HIPCHK(launch_exact_tick_sites(*src.exact, tick_map_ctx(e, 0, nullptr), first + done, ch.k, src.tick_cls, ch.sites,
-                                           e->w.d_keys, e->w.d_perm, e->w.d_tk_sites[ch.slot], e->w.d_tk_disp[ch.slot],
-                                           e->w.d_tk_res[ch.slot], e->w.d_xt_weight[ch.slot], st));
-        } else if (src.tick) {   // tick sites: the mapper takes the sampler's place
-            ch.tsites = e->w.d_tk_sites[ch.slot]; ch.disp = e->w.d_tk_disp[ch.slot]; ch.res = e->w.d_tk_res[ch.slot];
-            const fi_tick_site *in = nullptr;
-            if (src.ticks) {
-                HIPCHK(hipMemcpyAsync(e->w.d_tk_in[ch.slot], src.ticks + done, ch.k * sizeof(fi_tick_site),
-                                      hipMemcpyHostToDevice, st));
-                in = e->w.d_tk_in[ch.slot];
-            }
-            HIPCHK(launch_tick_map(tick_map_ctx(e, first + done, in), ch.k, ch.sites, e->w.d_keys, e->w.d_perm,
-                                   e->w.d_tk_sites[ch.slot], e->w.d_tk_disp[ch.slot], e->w.d_tk_res[ch.slot], st));
-        } else if (src.exact) {
-            ch.weight = e->w.d_weight[ch.slot];
-            if (src.profile) { ch.prof = src.exact; ch.prof_first = first + done; }
-            HIPCHK(launch_exact_sites(*src.exact, first + done, ch.k, e->gold.d_ex_classes, ch.sites, e->w.d_keys, e->w.d_perm,
-                                      e->w.d_weight[ch.slot], st));
-        } else {
-            HIPCHK(launch_sample(sample_ctx(e, first + done), ch.k, ch.sites, e->w.d_keys, e->w.d_perm, st));
-        }
-        fi_status s = chunk_begin(e, ch, st);
+        fi_status s = chunk_fill(e, src, first + done, ch, st);
+        if (!s) s = chunk_begin(e, ch, st);
         if (s) return s;
         if (have_prev) {
-            if ((s = chunk_deliver(e, staged[prev.slot]))) return s;   // (two chunks ago: long landed)
+            Chunk &held = staged[prev.s - e->w.slot];
+            if ((s = chunk_deliver(e, held))) return s;   // (two chunks ago: long landed)
             if ((s = chunk_end(e, prev, d_hist, st))) return s;
-            staged[prev.slot] = prev;
+            held = prev;
         }
         prev = ch;
         have_prev = true;
         done += ch.k;
     }
     if (have_prev) {
-        fi_status s = chunk_deliver(e, staged[prev.slot]);
+        Chunk &held = staged[prev.s - e->w.slot];
+        fi_status s = chunk_deliver(e, held);
         if (!s) s = chunk_end(e, prev, d_hist, st);
         if (s) return s;
-        staged[prev.slot] = prev;
+        held = prev;
     }
     HIPCHK(hipEventRecord(e->ev1, st));
     HIPCHK(launch_hist_stats(e->w.d_stats, d_hist, st));
@@ -2123,18 +2199,25 @@ static fi_status run_finish(fi_engine *e, fi_histogram *hist) {
     return FI_OK;
 }
 
+// A blocking run on e->stream (the work buffers are there): e->w.d_hist from
+// zero, what the caller enqueues ahead of the chunks (before, may be empty: the
+// sites that need no trial, the profile bins' memset), the chunks, run_finish.
+static fi_status run_blocking(fi_engine *e, uint64_t first, const SiteSource &src, uint64_t n, fi_outcome *out,
+                              fi_histogram *hist, const std::function<fi_status()> &before = nullptr) {
+    HIPCHK(hipMemsetAsync(e->w.d_hist, 0, sizeof(fi_histogram), e->stream));
+    fi_status s = before ? before() : FI_OK;
+    if (!s) s = run_chunks(e, first, src, n, nullptr, out, e->w.d_hist, e->stream);
+    return s ? s : run_finish(e, hist);
+}
+
 static fi_status run_common(fi_engine *e, uint64_t first, const SiteSource &src, uint64_t n, fi_outcome *out,
                             fi_histogram *hist) {
     if (!e) return FI_E_ARG;
     if (!e->gold.have_golden) return fail(e, FI_E_STATE, "golden run required");
-    if (src.sampled && !e->structures) return fail(e, FI_E_STATE, "fi_set_campaign first");
+    if (src.kind == SiteSource::kSampled && !e->structures) return fail(e, FI_E_STATE, "fi_set_campaign first");
     HIPCHK(hipSetDevice(e->dev));
-    const uint64_t chunk = e->cfg.max_trials_per_launch;
-    fi_status s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), chunk));
-    if (s) return s;
-    HIPCHK(hipMemsetAsync(e->w.d_hist, 0, sizeof(fi_histogram), e->stream));
-    s = run_chunks(e, first, src, n, nullptr, out, e->w.d_hist, e->stream);
-    return s ? s : run_finish(e, hist);
+    const fi_status s = ensure_work_for(e, n);
+    return s ? s : run_blocking(e, first, src, n, out, hist);
 }
 
 fi_status fi_wait_translation(fi_engine *e, fi_golden_info *out) {
@@ -2148,13 +2231,13 @@ fi_status fi_wait_translation(fi_engine *e, fi_golden_info *out) {
 }
 
 fi_status fi_run_trials(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist) {
-    return run_common(e, first, SiteSource{nullptr, nullptr, true, false}, n, out, hist);
+    return run_common(e, first, SiteSource::sampled(), n, out, hist);
 }
 
 fi_status fi_run_sites(fi_engine *e, const fi_site *sites, uint64_t n, fi_outcome *out, fi_histogram *hist) {
     if (!sites && n) return FI_E_ARG;
     // (no sites: an empty sampled run)
-    return run_common(e, 0, SiteSource{sites, nullptr, !sites, false}, n, out, hist);
+    return run_common(e, 0, sites ? SiteSource::given(sites) : SiteSource::sampled(), n, out, hist);
 }
 
 // ---- Exact campaigns (the classes and the trial ids: fi_exact.h)
@@ -2360,9 +2443,17 @@ static fi_status exact_mem_build(fi_engine *e, bool profiled = false) {
     return FI_OK;
 }
 
+// "who: trials [first, first + n) outside the campaign's ..." unless the range lies within `trials`
+static fi_status trial_range_check(fi_engine *e, const char *who, uint64_t first, uint64_t n, uint64_t trials) {
+    if (first > trials || n > trials - first)
+        return fail(e, FI_E_ARG, "%s: trials [%llu, %llu) outside the campaign's %llu", who, (unsigned long long)first,
+                    (unsigned long long)(first + n), (unsigned long long)trials);
+    return FI_OK;
+}
+
 // The checks every exact entry point shares, then the campaign's plan, its
 // dead sites and (info, may be NULL) its sizes.  profiled: the profile's tables too.
-static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, ExactDead &dd, fi_exact_info *info,
+static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, ExactUntried &dd, fi_exact_info *info,
                                bool profiled = false) {
     if (!e) return FI_E_ARG;
     if (!e->gold.have_golden) return fail(e, FI_E_STATE, "%s: golden run required", who);
@@ -2385,7 +2476,7 @@ static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, Exac
     if (!s && profiled) s = profile_build(e);
     if (!s && mem) s = exact_mem_build(e, profiled);
     if (s) return s;
-    dd = ExactDead{};
+    dd = ExactUntried{};
     fi_exact_info x{};
     const uint64_t ninst = e->gold.info.ninst;
     p = exact_plan(e->structures, e->gold.ex_off, ninst, e->bits, e->burst, x.classes);
@@ -2394,7 +2485,7 @@ static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, Exac
         if (t == FI_T_MEM) continue;
         x.space += ninst * p.nbits;
         if (t < 32) {
-            dd.dead[t] = (uint32_t)e->gold.ex_dead[t];
+            dd.masked[t] = e->gold.ex_dead[t];
             x.dead_sites += e->gold.ex_dead[t] * p.nbits;
         }
     }
@@ -2405,7 +2496,7 @@ static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, Exac
         x.space += m.words * ninst * p.nbits;
         for (uint32_t g = 0; g < m.n_rows; g++) {
             x.dead_sites += m.dead[g] * m.rows[g].npos;
-            for (uint64_t b = m.rows[g].pos; b; b &= b - 1) dd.mem_dead[__builtin_ctzll(b)] = m.dead[g];
+            for (uint64_t b = m.rows[g].pos; b; b &= b - 1) dd.mem_masked[__builtin_ctzll(b)] = m.dead[g];
         }
         uint64_t nc = m.n_classes;
         for (uint32_t t = 1; t < FI_N_STRUCT; t++) nc += t == FI_T_MEM ? 0 : x.classes[t];
@@ -2413,7 +2504,7 @@ static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, Exac
     }
     x.trials = p.trials;
     x.nbits = p.nbits;
-    dd.bits = p.bits; dd.total = x.dead_sites; dd.golden_ninst = ninst;
+    dd.bits = p.bits; dd.total = x.dead_sites; dd.insts = x.dead_sites * ninst;
     if (p.trials >= kExactMaxTrials) return fail(e, FI_E_ARG, "%s: 2^40 exact trials or more", who);
     if (info) *info = x;
     return FI_OK;
@@ -2422,7 +2513,7 @@ static fi_status exact_prepare(fi_engine *e, const char *who, ExactPlan &p, Exac
 fi_status fi_exact_get_info(fi_engine *e, fi_exact_info *out) {
     if (!e || !out) return FI_E_ARG;
     ExactPlan p;
-    ExactDead dd;
+    ExactUntried dd;
     return exact_prepare(e, "fi_exact_get_info", p, dd, out);
 }
 
@@ -2496,24 +2587,19 @@ fi_status fi_golden_mem_index(fi_engine *e, uint64_t *addr, uint64_t addr_cap, u
 fi_status fi_exact_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site *sites, uint32_t *weights) {
     if (!e || (n && !sites)) return FI_E_ARG;
     ExactPlan p;
-    ExactDead dd;
+    ExactUntried dd;
     fi_status s = exact_prepare(e, "fi_exact_sites", p, dd, nullptr);
+    if (!s) s = trial_range_check(e, "fi_exact_sites", first, n, p.trials);
+    if (!s) s = ensure_work_for(e, n);
     if (s) return s;
-    if (first > p.trials || n > p.trials - first)
-        return fail(e, FI_E_ARG, "fi_exact_sites: trials [%llu, %llu) outside the campaign's %llu", (unsigned long long)first,
-                    (unsigned long long)(first + n), (unsigned long long)p.trials);
-    s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch));
-    if (s) return s;
-    for (uint64_t done = 0; done < n;) {
-        const uint64_t k = std::min<uint64_t>(n - done, e->w.cap);
-        HIPCHK(launch_exact_sites(p, first + done, k, e->gold.d_ex_classes, e->w.d_sites, e->w.d_keys, e->w.d_perm, e->w.d_weight[0],
+    return for_chunks(e, n, [&](uint64_t done, uint64_t k) -> fi_status {
+        const ChunkSlot &s0 = e->w.slot[0];
+        HIPCHK(launch_exact_sites(p, first + done, k, e->gold.d_ex_classes, s0.d_sites, e->w.d_keys, e->w.d_perm, s0.d_weight,
                                   e->stream));
-        HIPCHK(hipMemcpyAsync(sites + done, e->w.d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
-        if (weights) HIPCHK(hipMemcpyAsync(weights + done, e->w.d_weight[0], k * 4, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        done += k;
-    }
-    return FI_OK;
+        HIPCHK(hipMemcpyAsync(sites + done, s0.d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        if (weights) HIPCHK(hipMemcpyAsync(weights + done, s0.d_weight, k * 4, hipMemcpyDeviceToHost, e->stream));
+        return FI_OK;
+    });
 }
 
 // fi_run_exact (prof == NULL: nothing of the profile is built, launched or copied) and
@@ -2521,26 +2607,20 @@ fi_status fi_exact_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site *site
 static fi_status run_exact(fi_engine *e, const char *who, uint64_t first, uint64_t n, fi_outcome *out,
                            fi_histogram *hist, fi_profile_bins *prof, uint64_t prof_rows) {
     ExactPlan p;
-    ExactDead dd;
+    ExactUntried dd;
     fi_status s = exact_prepare(e, who, p, dd, nullptr, prof != nullptr);
+    if (!s) s = trial_range_check(e, who, first, n, p.trials);
     if (s) return s;
-    if (first > p.trials || n > p.trials - first)
-        return fail(e, FI_E_ARG, "%s: trials [%llu, %llu) outside the campaign's %llu", who, (unsigned long long)first,
-                    (unsigned long long)(first + n), (unsigned long long)p.trials);
     if (prof && prof_rows != e->gold.xp.rows.size())
         return fail(e, FI_E_ARG, "%s: prof_rows %llu, the profile has %llu rows (fi_profile_rows)", who,
                     (unsigned long long)prof_rows, (unsigned long long)e->gold.xp.rows.size());
-    s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch));
-    if (s) return s;
-    HIPCHK(hipMemsetAsync(e->w.d_hist, 0, sizeof(fi_histogram), e->stream));
-    if (first == 0) HIPCHK(launch_exact_dead(dd, e->w.d_hist, e->stream));   // the sites that need no trial
+    if ((s = ensure_work_for(e, n))) return s;
     const size_t prof_bytes = prof ? prof_rows * sizeof(fi_profile_bins) : 0;
-    if (prof_bytes) HIPCHK(hipMemsetAsync(e->gold.xp.d_bins, 0, prof_bytes, e->stream));
-    SiteSource src;
-    src.exact = &p;
-    src.profile = prof != nullptr;
-    s = run_chunks(e, first, src, n, nullptr, out, e->w.d_hist, e->stream);
-    if (!s) s = run_finish(e, hist);
+    s = run_blocking(e, first, SiteSource::exact(&p, prof != nullptr), n, out, hist, [&]() -> fi_status {
+        if (first == 0) HIPCHK(launch_exact_untried(dd, e->w.d_hist, e->stream));   // the sites that need no trial
+        if (prof_bytes) HIPCHK(hipMemsetAsync(e->gold.xp.d_bins, 0, prof_bytes, e->stream));
+        return FI_OK;
+    });
     if (s || !prof_bytes) return s;
     std::vector<fi_profile_bins> got(prof_rows);
     HIPCHK(hipMemcpy(got.data(), e->gold.xp.d_bins, prof_bytes, hipMemcpyDeviceToHost));
@@ -2562,7 +2642,7 @@ fi_status fi_run_exact_profile(fi_engine *e, uint64_t first, uint64_t n, fi_outc
 
 fi_status fi_profile_rows(fi_engine *e, fi_profile_row *rows, uint64_t cap, uint64_t *n) {
     ExactPlan p;
-    ExactDead dd;
+    ExactUntried dd;
     fi_status s = exact_prepare(e, "fi_profile_rows", p, dd, nullptr, true);
     if (s) return s;
     const std::vector<fi_profile_row> &r = e->gold.xp.rows;
@@ -2574,22 +2654,16 @@ fi_status fi_profile_rows(fi_engine *e, fi_profile_row *rows, uint64_t cap, uint
 fi_status fi_exact_consumers(fi_engine *e, uint64_t first, uint64_t n, uint32_t *row) {
     if (!e || (n && !row)) return FI_E_ARG;
     ExactPlan p;
-    ExactDead dd;
+    ExactUntried dd;
     fi_status s = exact_prepare(e, "fi_exact_consumers", p, dd, nullptr, true);
+    if (!s) s = trial_range_check(e, "fi_exact_consumers", first, n, p.trials);
+    if (!s) s = ensure_work_for(e, n);
     if (s) return s;
-    if (first > p.trials || n > p.trials - first)
-        return fail(e, FI_E_ARG, "fi_exact_consumers: trials [%llu, %llu) outside the campaign's %llu",
-                    (unsigned long long)first, (unsigned long long)(first + n), (unsigned long long)p.trials);
-    s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch));
-    if (s) return s;
-    for (uint64_t done = 0; done < n;) {   // (d_perm: a uint32 per trial of a chunk, free between runs)
-        const uint64_t k = std::min<uint64_t>(n - done, e->w.cap);
+    return for_chunks(e, n, [&](uint64_t done, uint64_t k) -> fi_status {   // (d_perm: a uint32 per trial, free between runs)
         HIPCHK(launch_exact_consumers(p, e->gold.xp.d_reg_cons, e->gold.xp.d_inst_row, first + done, k, e->w.d_perm, e->stream));
         HIPCHK(hipMemcpyAsync(row + done, e->w.d_perm, k * 4, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        done += k;
-    }
-    return FI_OK;
+        return FI_OK;
+    });
 }
 
 uint32_t fi_debug_profile_slots(void) { return kProfSlots; }
@@ -2608,13 +2682,14 @@ static fi_status ensure_capture(fi_engine *e, uint64_t rows, uint32_t stride) {
     if (rows * stride <= x.held_b && rows <= x.held_rows) return FI_OK;
     const uint64_t b = std::max(x.held_b, rows * stride), r = std::max(x.held_rows, rows);
     x = Capture{};   // (holds nothing until every buffer is made)
-    for (int i = 0; i < 2; i++) {
-        HIPCHK(x.d_out[i].alloc(b));
-        HIPCHK(x.d_err[i].alloc(b));
-        HIPCHK(x.d_len[i].alloc(r));
-        HIPCHK(x.h_out[i].alloc(b));
-        HIPCHK(x.h_err[i].alloc(b));
-        HIPCHK(x.h_len[i].alloc(r));
+    for (ChunkSlot &s : e->w.slot) s.cap = CaptureRows{};
+    for (ChunkSlot &s : e->w.slot) {
+        HIPCHK(s.cap.d_out.alloc(b));
+        HIPCHK(s.cap.d_err.alloc(b));
+        HIPCHK(s.cap.d_len.alloc(r));
+        HIPCHK(s.cap.h_out.alloc(b));
+        HIPCHK(s.cap.h_err.alloc(b));
+        HIPCHK(s.cap.h_len.alloc(r));
     }
     x.held_b = b; x.held_rows = r;
     return FI_OK;
@@ -2647,7 +2722,7 @@ fi_status fi_run_sites_capture(fi_engine *e, const fi_site *sites, uint64_t n, u
         x.rows = rows; x.stride = stride;
         x.out = out_buf; x.err = err_buf; x.lens = lens;
         x.bytes = cap_bytes;   // capture is on
-        s = run_common(e, 0, SiteSource{sites, nullptr, false, false}, n, out, hist);
+        s = run_common(e, 0, SiteSource::given(sites), n, out, hist);
         if (s) (void)hipStreamSynchronize(e->stream);   // nothing in flight still writes the caller's arrays
         x.bytes = 0;           // ... and off again for every other entry point
         x.out = x.err = nullptr; x.lens = nullptr;
@@ -2752,6 +2827,9 @@ fi_status fi_map_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi
 }
 
 // ---- the device map (fi_set_tick_map FI_TICK_MAP_DEVICE)
+// A tick site as the device keeps it -- fi_site layout, inst = the tick -- back as a fi_tick_site
+static fi_tick_site tick_site_of(const fi_site &t) { return fi_tick_site{t.inst, t.mask, t.target, t.trial}; }
+
 fi_status fi_set_tick_map(fi_engine *e, int where) {
     if (!e) return FI_E_ARG;
     if (where != FI_TICK_MAP_HOST && where != FI_TICK_MAP_DEVICE) return fail(e, FI_E_ARG, "unknown tick map %d", where);
@@ -2784,17 +2862,17 @@ static fi_status ensure_tick_table(fi_engine *e) {
     return FI_OK;
 }
 
-// The device map's work buffers, one set per chunk slot, beside the others
-// (growth of the work buffers drops them): made once a device tick run or map
-// is first asked for; tk_ok once all are.
+// The device map's work buffers in both chunk slots (growth of the work
+// buffers drops them with the slots): made once a device tick run or map is
+// first asked for; tk_ok once all are.
 static fi_status ensure_tick_work(fi_engine *e) {
     Work &w = e->w;
     if (w.tk_ok) return FI_OK;
-    for (int i = 0; i < 2; i++) {
-        HIPCHK(w.d_tk_sites[i].alloc(w.cap));
-        HIPCHK(w.d_tk_disp[i].alloc(w.cap));
-        HIPCHK(w.d_tk_res[i].alloc(w.cap));
-        HIPCHK(w.d_tk_in[i].alloc(w.cap));
+    for (ChunkSlot &s : w.slot) {
+        HIPCHK(s.d_tk_sites.alloc(w.cap));
+        HIPCHK(s.d_tk_disp.alloc(w.cap));
+        HIPCHK(s.d_tk_res.alloc(w.cap));
+        HIPCHK(s.d_tk_in.alloc(w.cap));
     }
     w.tk_ok = true;
     return FI_OK;
@@ -2802,7 +2880,7 @@ static fi_status ensure_tick_work(fi_engine *e) {
 
 static fi_status tick_device_prepare(fi_engine *e, uint64_t n) {
     HIPCHK(hipSetDevice(e->dev));
-    fi_status s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch));
+    fi_status s = ensure_work_for(e, n);
     if (!s) s = ensure_tick_work(e);
     if (!s) s = ensure_tick_table(e);
     return s;
@@ -2816,9 +2894,7 @@ static fi_status tick_run_device(fi_engine *e, uint64_t first, const fi_tick_sit
     fi_status s = tick_check(e, ts, n, !ts, true);
     if (s || !n) return s;
     if ((s = tick_device_prepare(e, n))) return s;
-    HIPCHK(hipMemsetAsync(e->w.d_hist, 0, sizeof(fi_histogram), e->stream));
-    s = run_chunks(e, first, SiteSource{nullptr, ts, !ts, true}, n, nullptr, out, e->w.d_hist, e->stream);
-    return s ? s : run_finish(e, hist);
+    return run_blocking(e, first, ts ? SiteSource::given_ticks(ts) : SiteSource::sampled_ticks(), n, out, hist);
 }
 
 fi_status fi_run_tick_trials_device(fi_engine *e, uint64_t first, uint64_t n, void *d_out, void *d_hist, void *stream) {
@@ -2827,8 +2903,7 @@ fi_status fi_run_tick_trials_device(fi_engine *e, uint64_t first, uint64_t n, vo
     if (s || !n) return s;
     if ((s = tick_device_prepare(e, n))) return s;
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    return run_chunks(e, first, SiteSource{nullptr, nullptr, true, true}, n, (fi_outcome *)d_out, nullptr,
-                      (fi_histogram *)d_hist, st);
+    return run_chunks(e, first, SiteSource::sampled_ticks(), n, (fi_outcome *)d_out, nullptr, (fi_histogram *)d_hist, st);
 }
 
 fi_status fi_map_tick_sites_device(fi_engine *e, const fi_tick_site *ts, uint64_t first, uint64_t n,
@@ -2837,26 +2912,22 @@ fi_status fi_map_tick_sites_device(fi_engine *e, const fi_tick_site *ts, uint64_
     fi_status s = tick_check(e, ts, n, !ts, false);
     if (s || !n) return s;
     if ((s = tick_device_prepare(e, n))) return s;
-    std::vector<fi_site> tsv(ts_out ? std::min<uint64_t>(n, e->w.cap) : 0);
-    for (uint64_t done = 0; done < n;) {
-        const uint64_t k = std::min<uint64_t>(n - done, e->w.cap);
-        if (ts) HIPCHK(hipMemcpyAsync(e->w.d_tk_in[0], ts + done, k * sizeof(fi_tick_site), hipMemcpyHostToDevice, e->stream));
-        HIPCHK(launch_tick_map(tick_map_ctx(e, first + done, ts ? e->w.d_tk_in[0] : nullptr), k, e->w.d_sites, e->w.d_keys,
-                               e->w.d_perm, e->w.d_tk_sites[0], e->w.d_tk_disp[0], e->w.d_tk_res[0], e->stream));
-        HIPCHK(hipMemcpyAsync(sites + done, e->w.d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipMemcpyAsync(disp + done, e->w.d_tk_disp[0], k, hipMemcpyDeviceToHost, e->stream));
+    std::vector<fi_site> tsv(ts_out ? n : 0);
+    s = for_chunks(e, n, [&](uint64_t done, uint64_t k) -> fi_status {
+        const ChunkSlot &s0 = e->w.slot[0];
+        if (ts) HIPCHK(hipMemcpyAsync(s0.d_tk_in, ts + done, k * sizeof(fi_tick_site), hipMemcpyHostToDevice, e->stream));
+        HIPCHK(launch_tick_map(tick_map_ctx(e, first + done, ts ? s0.d_tk_in.get() : nullptr), k, s0.d_sites, e->w.d_keys,
+                               e->w.d_perm, s0.d_tk_sites, s0.d_tk_disp, s0.d_tk_res, e->stream));
+        HIPCHK(hipMemcpyAsync(sites + done, s0.d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(disp + done, s0.d_tk_disp, k, hipMemcpyDeviceToHost, e->stream));
         if (host_out)
-            HIPCHK(hipMemcpyAsync(host_out + done, e->w.d_tk_res[0], k * sizeof(fi_outcome), hipMemcpyDeviceToHost, e->stream));
+            HIPCHK(hipMemcpyAsync(host_out + done, s0.d_tk_res, k * sizeof(fi_outcome), hipMemcpyDeviceToHost, e->stream));
         if (ts_out)
-            HIPCHK(hipMemcpyAsync(tsv.data(), e->w.d_tk_sites[0], k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        for (uint64_t i = 0; ts_out && i < k; i++) {
-            fi_tick_site &o = ts_out[done + i];
-            o.tick = tsv[i].inst; o.mask = tsv[i].mask; o.target = tsv[i].target; o.trial = tsv[i].trial;
-        }
-        done += k;
-    }
-    return FI_OK;
+            HIPCHK(hipMemcpyAsync(tsv.data() + done, s0.d_tk_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        return FI_OK;
+    });
+    for (uint64_t i = 0; !s && ts_out && i < n; i++) ts_out[i] = tick_site_of(tsv[i]);
+    return s;
 }
 
 fi_status fi_run_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi_outcome *out, fi_histogram *hist) {
@@ -2875,7 +2946,7 @@ fi_status fi_run_tick_sites(fi_engine *e, const fi_tick_site *ts, uint64_t n, fi
     fi_histogram dh{};
     if (!run.empty()) {
         std::vector<fi_outcome> ro(run.size());
-        st = run_common(e, 0, SiteSource{run.data(), nullptr, false, true}, run.size(), ro.data(), &dh);
+        st = run_common(e, 0, SiteSource::mapped(run.data()), run.size(), ro.data(), &dh);
         if (st) return st;
         for (size_t q = 0; q < idx.size(); q++) res[idx[q]] = ro[q];
     }
@@ -2986,7 +3057,7 @@ static fi_status exact_tick_build(fi_engine *e) {
 
 // The checks every exact tick entry point shares, then the plan, the ticks without a trial and
 // (info, may be NULL) the sizes.  run: a call that runs trials (fi_set_protect* must be off).
-static fi_status exact_tick_prepare(fi_engine *e, const char *who, bool run, ExactPlan &p, ExactTickDead &dd,
+static fi_status exact_tick_prepare(fi_engine *e, const char *who, bool run, ExactPlan &p, ExactUntried &dd,
                                     fi_exact_tick_info *info) {
     if (!e) return FI_E_ARG;
     if (!e->gold.have_golden) return fail(e, FI_E_STATE, "%s: golden run required", who);
@@ -3007,7 +3078,7 @@ static fi_status exact_tick_prepare(fi_engine *e, const char *who, bool run, Exa
     const ExTick &x = e->gold.xt;
     fi_exact_tick_info o{};
     p = exact_tick_plan(e->structures, x.tab.off, e->bits, e->burst, o.classes);
-    dd = ExactTickDead{};
+    dd = ExactUntried{};
     dd.bits = p.bits;
     const uint64_t T = e->gold.t_stats.ticks;
     for (uint32_t t = 1; t < FI_N_STRUCT; t++) {
@@ -3035,15 +3106,15 @@ static fi_status exact_tick_prepare(fi_engine *e, const char *who, bool run, Exa
 static fi_status ensure_exact_tick_work(fi_engine *e, uint64_t n) {
     fi_status s = tick_device_prepare(e, n);
     if (s) return s;
-    for (int i = 0; i < 2; i++)
-        if (!e->w.d_xt_weight[i]) HIPCHK(e->w.d_xt_weight[i].alloc(e->w.cap));
+    for (ChunkSlot &sl : e->w.slot)
+        if (!sl.d_xt_weight) HIPCHK(sl.d_xt_weight.alloc(e->w.cap));
     return FI_OK;
 }
 
 fi_status fi_exact_tick_get_info(fi_engine *e, fi_exact_tick_info *out) {
     if (!e || !out) return FI_E_ARG;
     ExactPlan p;
-    ExactTickDead dd;
+    ExactUntried dd;
     return exact_tick_prepare(e, "fi_exact_tick_get_info", false, p, dd, out);
 }
 
@@ -3051,55 +3122,44 @@ fi_status fi_exact_tick_sites(fi_engine *e, uint64_t first, uint64_t n, fi_site 
                               uint64_t *weights) {
     if (!e || (n && !sites)) return FI_E_ARG;
     ExactPlan p;
-    ExactTickDead dd;
+    ExactUntried dd;
     fi_status s = exact_tick_prepare(e, "fi_exact_tick_sites", false, p, dd, nullptr);
-    if (s) return s;
-    if (first > p.trials || n > p.trials - first)
-        return fail(e, FI_E_ARG, "fi_exact_tick_sites: trials [%llu, %llu) outside the campaign's %llu", (unsigned long long)first,
-                    (unsigned long long)(first + n), (unsigned long long)p.trials);
-    if (!n) return FI_OK;
+    if (!s) s = trial_range_check(e, "fi_exact_tick_sites", first, n, p.trials);
+    if (s || !n) return s;
     if ((s = ensure_exact_tick_work(e, n))) return s;
-    std::vector<fi_site> tsv(representative ? std::min<uint64_t>(n, e->w.cap) : 0);
-    for (uint64_t done = 0; done < n;) {
-        const uint64_t k = std::min<uint64_t>(n - done, e->w.cap);
-        HIPCHK(launch_exact_tick_sites(p, tick_map_ctx(e, 0, nullptr), first + done, k, e->gold.xt.d_cls, e->w.d_sites,
-                                       e->w.d_keys, e->w.d_perm, e->w.d_tk_sites[0], e->w.d_tk_disp[0], e->w.d_tk_res[0],
-                                       e->w.d_xt_weight[0], e->stream));
-        HIPCHK(hipMemcpyAsync(sites + done, e->w.d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
-        if (weights) HIPCHK(hipMemcpyAsync(weights + done, e->w.d_xt_weight[0], k * 8, hipMemcpyDeviceToHost, e->stream));
+    std::vector<fi_site> tsv(representative ? n : 0);
+    s = for_chunks(e, n, [&](uint64_t done, uint64_t k) -> fi_status {
+        const ChunkSlot &s0 = e->w.slot[0];
+        HIPCHK(launch_exact_tick_sites(p, tick_map_ctx(e, 0, nullptr), first + done, k, e->gold.xt.d_cls, s0.d_sites,
+                                       e->w.d_keys, e->w.d_perm, s0.d_tk_sites, s0.d_tk_disp, s0.d_tk_res, s0.d_xt_weight,
+                                       e->stream));
+        HIPCHK(hipMemcpyAsync(sites + done, s0.d_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        if (weights) HIPCHK(hipMemcpyAsync(weights + done, s0.d_xt_weight, k * 8, hipMemcpyDeviceToHost, e->stream));
         if (representative)
-            HIPCHK(hipMemcpyAsync(tsv.data(), e->w.d_tk_sites[0], k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        for (uint64_t i = 0; representative && i < k; i++)
-            representative[done + i] = fi_tick_site{tsv[i].inst, tsv[i].mask, tsv[i].target, tsv[i].trial};
-        done += k;
-    }
-    return FI_OK;
+            HIPCHK(hipMemcpyAsync(tsv.data() + done, s0.d_tk_sites, k * sizeof(fi_site), hipMemcpyDeviceToHost, e->stream));
+        return FI_OK;
+    });
+    for (uint64_t i = 0; !s && representative && i < n; i++) representative[i] = tick_site_of(tsv[i]);
+    return s;
 }
 
 fi_status fi_run_exact_ticks(fi_engine *e, uint64_t first, uint64_t n, fi_outcome *out, fi_histogram *hist) {
     ExactPlan p;
-    ExactTickDead dd;
+    ExactUntried dd;
     fi_status s = exact_tick_prepare(e, "fi_run_exact_ticks", true, p, dd, nullptr);
+    if (!s) s = trial_range_check(e, "fi_run_exact_ticks", first, n, p.trials);
+    if (!s) s = ensure_exact_tick_work(e, n);
     if (s) return s;
-    if (first > p.trials || n > p.trials - first)
-        return fail(e, FI_E_ARG, "fi_run_exact_ticks: trials [%llu, %llu) outside the campaign's %llu", (unsigned long long)first,
-                    (unsigned long long)(first + n), (unsigned long long)p.trials);
-    if ((s = ensure_exact_tick_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), e->cfg.max_trials_per_launch)))) return s;
-    HIPCHK(hipMemsetAsync(e->w.d_hist, 0, sizeof(fi_histogram), e->stream));
-    if (first == 0) HIPCHK(launch_exact_tick_dead(dd, e->w.d_hist, e->stream));   // the ticks that need no trial
-    SiteSource src;
-    src.tick = true;
-    src.exact = &p;
-    src.tick_cls = e->gold.xt.d_cls;
-    s = run_chunks(e, first, src, n, nullptr, out, e->w.d_hist, e->stream);
-    return s ? s : run_finish(e, hist);
+    return run_blocking(e, first, SiteSource::exact_ticks(&p, e->gold.xt.d_cls), n, out, hist, [&]() -> fi_status {
+        if (first == 0) HIPCHK(launch_exact_untried(dd, e->w.d_hist, e->stream));   // the ticks that need no trial
+        return FI_OK;
+    });
 }
 
 fi_status fi_exact_tick_locate(fi_engine *e, const fi_tick_site *ts, uint64_t n, uint64_t *trial, uint8_t *kind) {
     if (!e || (n && (!ts || !trial || !kind))) return FI_E_ARG;
     ExactPlan p;
-    ExactTickDead dd;
+    ExactUntried dd;
     fi_status s = exact_tick_prepare(e, "fi_exact_tick_locate", false, p, dd, nullptr);
     if (s) return s;
     const Golden &g = e->gold;
@@ -3132,11 +3192,9 @@ fi_status fi_run_trials_device(fi_engine *e, uint64_t first, uint64_t n, void *d
     if (!e->structures) return fail(e, FI_E_STATE, "fi_set_campaign first");
     HIPCHK(hipSetDevice(e->dev));
     hipStream_t st = stream ? (hipStream_t)stream : e->stream;
-    const uint64_t chunk = e->cfg.max_trials_per_launch;
-    fi_status s = ensure_work(e, std::min<uint64_t>(std::max<uint64_t>(n, 1), chunk));
+    const fi_status s = ensure_work_for(e, n);
     if (s) return s;
-    return run_chunks(e, first, SiteSource{nullptr, nullptr, true, false}, n, (fi_outcome *)d_out, nullptr,
-                      (fi_histogram *)d_hist, st);
+    return run_chunks(e, first, SiteSource::sampled(), n, (fi_outcome *)d_out, nullptr, (fi_histogram *)d_hist, st);
 }
 
 fi_status fi_sync(fi_engine *e) {

@@ -2,7 +2,8 @@
 // enumerated by first-access class instead of sampled.  One statement for the
 // host (fi_engine.cpp fi_exact_classes, fi_exact_mem_classes, the plan of
 // fi_run_exact; tools/exact_host_check.cpp, tools/exact_mem_host_check.cpp)
-// and the device (fi_kernels.hip fi_exact_sites_kernel, fi_exact_mem_*_kernel).
+// and the device (fi_kernels.hip fi_exact_sites_kernel, fi_exact_mem_*_kernel;
+// the sites without a trial: ExactUntried, fi_exact_untried_kernel).
 //
 // Register r's entries ev[off[r] .. off[r + 1]) of the first-access index
 // (fi_golden_host.h first_access_index: (2 * numInst + !ecall) << 1 | reads)
@@ -405,12 +406,15 @@ struct ExactMemCtx {
     const uint32_t *proxy;
 };
 
-// The dead sites of a campaign (fi_exact_dead_kernel)
-struct ExactDead {
-    uint32_t dead[32];         // per register (0: not selected)
-    uint64_t bits, total;      // eligible positions; the sum of dead x the eligible positions (memory's included)
-    uint64_t golden_ninst;
-    uint64_t mem_dead[64];     // per position b: the dead (word, t) pairs of b's byte set (0: memory not selected)
+// What a campaign counts without a trial (fi_exact_untried_kernel), numInst or tick domain: per
+// register r the sites that end masked (dead; in a tick campaign golden-equal too) and escaped
+// (tick campaigns: FI_ESC_TIMING), per position b the dead (word, t) pairs of b's byte set
+// (numInst campaigns with memory).  A row of zeros adds nothing.
+struct ExactUntried {
+    uint64_t bits;                       // eligible positions
+    uint64_t masked[32], escaped[32];    // per register (0: not selected)
+    uint64_t mem_masked[64];             // per position
+    uint64_t total, insts, esc_total;    // sites over the eligible positions; their guest_insts (mod 2^64); the escaped
 };
 
 struct ExactSite {
@@ -467,6 +471,17 @@ FI_TM_HD inline uint32_t exact_class(const ExactPlan &p, uint64_t k, uint32_t *t
     return (uint32_t)q + delta;
 }
 
+// The mask of a class's bit slot
+FI_TM_HD inline uint64_t exact_slot_mask(const ExactPlan &p, uint32_t slot) {
+    uint64_t b = slot;   // positions 0 .. nbits - 1: the slot is the position
+    if (p.bits & (p.bits + 1)) {
+        uint64_t mm = p.bits;
+        for (uint32_t j = slot; j; j--) mm &= mm - 1;
+        b = (uint64_t)__builtin_ctzll(mm);
+    }
+    return exact_burst_mask(p.burst) << b;
+}
+
 // Exact trial k (k < p.trials); classes = every register's packed words
 FI_TM_HD inline ExactSite exact_site(const ExactPlan &p, const uint64_t *classes, uint64_t k) {
     if (k - p.mem_first < p.mem_trials) return exact_mem_site(p, k - p.mem_first);   // (k < mem_first wraps: no)
@@ -481,13 +496,7 @@ FI_TM_HD inline ExactSite exact_site(const ExactPlan &p, const uint64_t *classes
         const uint64_t w = classes[x];
         s.inst = exact_word_inst(w); s.target = exact_word_reg(w); s.weight = exact_word_weight(w);
     }
-    uint64_t b = slot;   // positions 0 .. nbits - 1: the slot is the position
-    if (p.bits & (p.bits + 1)) {
-        uint64_t mm = p.bits;
-        for (uint32_t j = slot; j; j--) mm &= mm - 1;
-        b = (uint64_t)__builtin_ctzll(mm);
-    }
-    s.mask = exact_burst_mask(p.burst) << b;
+    s.mask = exact_slot_mask(p, slot);
     return s;
 }
 

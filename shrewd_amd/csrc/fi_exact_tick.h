@@ -4,6 +4,8 @@
 // fi_exact_tick_locate; tools/exact_tick_host_check.cpp) and the device
 // (fi_kernels.hip fi_exact_tick_sites_kernel).  The map itself is
 // fi_tick_map.h tick_map_site and is only ever called here, never restated.
+// The ticks without a trial go into fi_exact.h's ExactUntried, the bit slots'
+// masks come from its exact_slot_mask: one of each for both domains.
 //
 // Segments.  T = golden_ticks.  Attempt j owns the ticks [done[j - 1] + 1,
 // min(done[j], T - 1)] (from 0 for j = 0; the last attempt up to T - 1:
@@ -237,17 +239,6 @@ inline ExactPlan exact_tick_plan(uint64_t structures, const uint32_t *off, uint6
     return p;
 }
 
-// The mask of a class's bit slot
-FI_TM_HD inline uint64_t exact_slot_mask(const ExactPlan &p, uint32_t slot) {
-    uint64_t b = slot;   // positions 0 .. nbits - 1: the slot is the position
-    if (p.bits & (p.bits + 1)) {
-        uint64_t mm = p.bits;
-        for (uint32_t j = slot; j; j--) mm &= mm - 1;
-        b = (uint64_t)__builtin_ctzll(mm);
-    }
-    return exact_burst_mask(p.burst) << b;
-}
-
 // Exact tick trial k (k < p.trials): the site the trial kernels run, its tick
 // site, the map's disposition and a disp 1 / 2 trial's outcome, the ticks it
 // stands for.  c: the packed table and the golden outcome (TickMapCtx).
@@ -278,15 +269,6 @@ FI_TM_HD inline ExactTickSite exact_tick_site(const ExactPlan &p, const ExactTic
     s.res = tick_map_outcome(m, c.rec[m.attempt], c.gsub, c.gexit, c.gdetail, c.golden_ninst);
     return s;
 }
-
-// The ticks without a trial (fi_exact_tick_dead_kernel): per register the
-// masked ones (dead + golden-equal) and the escaped ones; the totals over the
-// eligible positions.
-struct ExactTickDead {
-    uint64_t masked[32], escaped[32];
-    uint64_t bits;
-    uint64_t total, insts, esc_total;   // sites; their guest_insts (mod 2^64); the escaped among them
-};
 
 // Where a tick site of the space belongs (fi_exact_tick_locate): the class it
 // falls into, counted within its structure (*cls_index, from x.off[target]),

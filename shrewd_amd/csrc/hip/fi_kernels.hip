@@ -329,9 +329,14 @@ __global__ void __launch_bounds__(256) fi_exact_mem_walk_kernel(ExactMemCtx c, c
 // that straddles a segment boundary -- add to global memory directly, and the
 // block flushes its non-zero bins with one global atomic each.  Sub-codes and
 // totals are summed in the wave first.  Integer adds only: the result does
-// not depend on arrival order.
+// not depend on arrival order.  W: uint32_t, a numInst campaign's weights, keyed
+// by the run sites; uint64_t, a tick campaign's (tick counts pass 2^32), keyed
+// by the tick sites (a pc flip that maps to a write of rd counts under the pc);
+// every product and sum is modulo 2^64, so a wave's weights may sum to 0 while
+// its instructions do not: the totals' guard tests both.
+template <typename W>
 __global__ void __launch_bounds__(256) fi_exact_hist_kernel(const fi_site *sites, const fi_outcome *out,
-                                                            const uint32_t *weight, uint64_t n, fi_histogram *h) {
+                                                            const W *weight, uint64_t n, fi_histogram *h) {
     __shared__ unsigned long long bins[64 * FI_N_CLASS];
     for (uint32_t b = threadIdx.x; b < 64 * FI_N_CLASS; b += blockDim.x) bins[b] = 0;
     // (the grid covers n: the block's first trial exists; every lane reads the same word)
@@ -370,7 +375,7 @@ __global__ void __launch_bounds__(256) fi_exact_hist_kernel(const fi_site *sites
         }
     }
     const uint64_t nt = wave_sum64(w), ni = wave_sum64(wi);
-    if (lane == 0 && nt) {
+    if (lane == 0 && (nt | ni)) {
         atomicAdd((unsigned long long *)&h->trials, (unsigned long long)nt);
         atomicAdd((unsigned long long *)&h->guest_insts, (unsigned long long)ni);
     }
@@ -460,18 +465,23 @@ __global__ void __launch_bounds__(256) fi_exact_consumers_kernel(ExactPlan p, co
     row[i] = exact_trial_consumer(p, reg_cons, inst_row, first + i, &group);
 }
 
-// The dead sites of an exact campaign (no trial: the golden run, masked):
-// block r, thread b adds register r's dead count to counts[r][b][FI_MASKED]
-// for every selected r and eligible b, block 32 the dead (word, t) pairs of
-// b's byte set to counts[FI_T_MEM][b][FI_MASKED]; the totals by one thread.
-__global__ void __launch_bounds__(64) fi_exact_dead_kernel(ExactDead d, fi_histogram *h) {
+// What an exact campaign counts without a trial (fi_exact.h ExactUntried):
+// block r < 32, thread b adds register r's masked sites to
+// counts[r][b][FI_MASKED] and its escaped ones to counts[r][b][FI_ESCAPE] for
+// every eligible b, block 32 the dead (word, t) pairs of b's byte set to
+// counts[FI_T_MEM][b][FI_MASKED]; the totals by one thread.
+__global__ void __launch_bounds__(64) fi_exact_untried_kernel(ExactUntried d, fi_histogram *h) {
     const uint32_t r = blockIdx.x, b = threadIdx.x;
-    const uint64_t c = r < 32 ? d.dead[r] : d.mem_dead[b];
     const uint32_t t = r < 32 ? r : (uint32_t)FI_T_MEM;
-    if (c && ((d.bits >> b) & 1)) atomicAdd((unsigned long long *)&h->counts[t][b][FI_MASKED], (unsigned long long)c);
+    const uint64_t m = r < 32 ? d.masked[r] : d.mem_masked[b], x = r < 32 ? d.escaped[r] : 0;
+    if ((d.bits >> b) & 1) {
+        if (m) atomicAdd((unsigned long long *)&h->counts[t][b][FI_MASKED], (unsigned long long)m);
+        if (x) atomicAdd((unsigned long long *)&h->counts[t][b][FI_ESCAPE], (unsigned long long)x);
+    }
     if (r == 0 && b == 0 && d.total) {
         atomicAdd((unsigned long long *)&h->trials, (unsigned long long)d.total);
-        atomicAdd((unsigned long long *)&h->guest_insts, (unsigned long long)(d.total * d.golden_ninst));
+        atomicAdd((unsigned long long *)&h->guest_insts, (unsigned long long)d.insts);
+        if (d.esc_total) atomicAdd((unsigned long long *)&h->escape_sub[FI_ESC_TIMING], (unsigned long long)d.esc_total);
     }
 }
 
@@ -498,76 +508,6 @@ __global__ void __launch_bounds__(256) fi_exact_tick_sites_kernel(ExactPlan p, T
     disp[i] = (uint8_t)x.disp;
     res[i] = x.res;
     weight[i] = x.weight;
-}
-
-// fi_exact_hist_kernel with 64-bit weights (tick counts pass 2^32), keyed by
-// the tick sites: the same LDS table of the block's first structure, the same
-// wave sums; every product and sum is modulo 2^64.
-__global__ void __launch_bounds__(256) fi_exact_tick_hist_kernel(const fi_site *tsites, const fi_outcome *out,
-                                                                 const uint64_t *weight, uint64_t n, fi_histogram *h) {
-    __shared__ unsigned long long bins[64 * FI_N_CLASS];
-    for (uint32_t b = threadIdx.x; b < 64 * FI_N_CLASS; b += blockDim.x) bins[b] = 0;
-    // (the grid covers n: the block's first trial exists; every lane reads the same word)
-    uint32_t t0 = tsites[(uint64_t)blockIdx.x * blockDim.x].target;
-    t0 = t0 < FI_N_STRUCT ? t0 : 0;
-    __syncthreads();
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t cls = FI_N_CLASS, sub = 0;
-    uint64_t w = 0, wi = 0;
-    if (i < n) {
-        const fi_site s = tsites[i];
-        const fi_outcome o = out[i];
-        const uint32_t t = s.target < FI_N_STRUCT ? s.target : 0;
-        const uint32_t bit = s.mask ? (uint32_t)__builtin_ctzll(s.mask) : 0;
-        cls = o.cls < FI_N_CLASS ? o.cls : FI_ESCAPE;
-        sub = o.sub;
-        w = weight[i];
-        wi = w * o.ninst;
-        if (t == t0) atomicAdd(&bins[bit * FI_N_CLASS + cls], (unsigned long long)w);
-        else atomicAdd((unsigned long long *)&h->counts[t][bit][cls], (unsigned long long)w);
-    }
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t crash = __ballot(cls == FI_CRASH), esc = __ballot(cls == FI_ESCAPE);
-    if (crash) {
-        for (uint32_t k = 0; k < 16; k++) {
-            if (!(crash & __ballot((sub & 15) == k))) continue;   // (wave-uniform)
-            const uint64_t c = wave_sum64(cls == FI_CRASH && (sub & 15) == k ? w : 0);
-            if (c && lane == 0) atomicAdd((unsigned long long *)&h->crash_sub[k], (unsigned long long)c);
-        }
-    }
-    if (esc) {
-        for (uint32_t k = 0; k < 8; k++) {
-            if (!(esc & __ballot((sub & 7) == k))) continue;
-            const uint64_t c = wave_sum64(cls == FI_ESCAPE && (sub & 7) == k ? w : 0);
-            if (c && lane == 0) atomicAdd((unsigned long long *)&h->escape_sub[k], (unsigned long long)c);
-        }
-    }
-    const uint64_t nt = wave_sum64(w), ni = wave_sum64(wi);
-    if (lane == 0 && (nt | ni)) {
-        atomicAdd((unsigned long long *)&h->trials, (unsigned long long)nt);
-        atomicAdd((unsigned long long *)&h->guest_insts, (unsigned long long)ni);
-    }
-    __syncthreads();
-    unsigned long long *g = (unsigned long long *)&h->counts[t0][0][0];
-    for (uint32_t b = threadIdx.x; b < 64 * FI_N_CLASS; b += blockDim.x)
-        if (bins[b]) atomicAdd(&g[b], bins[b]);
-}
-
-// The ticks of an exact tick campaign that need no trial: block r, thread b
-// adds register r's masked ticks (dead, golden-equal) to counts[r][b][FI_MASKED]
-// and its escaped ones to counts[r][b][FI_ESCAPE] for every eligible b; the
-// totals by one thread.
-__global__ void __launch_bounds__(64) fi_exact_tick_dead_kernel(ExactTickDead d, fi_histogram *h) {
-    const uint32_t r = blockIdx.x, b = threadIdx.x;
-    if ((d.bits >> b) & 1) {
-        if (d.masked[r]) atomicAdd((unsigned long long *)&h->counts[r][b][FI_MASKED], (unsigned long long)d.masked[r]);
-        if (d.escaped[r]) atomicAdd((unsigned long long *)&h->counts[r][b][FI_ESCAPE], (unsigned long long)d.escaped[r]);
-    }
-    if (r == 0 && b == 0 && d.total) {
-        atomicAdd((unsigned long long *)&h->trials, (unsigned long long)d.total);
-        atomicAdd((unsigned long long *)&h->guest_insts, (unsigned long long)d.insts);
-        if (d.esc_total) atomicAdd((unsigned long long *)&h->escape_sub[FI_ESC_TIMING], (unsigned long long)d.esc_total);
-    }
 }
 
 // Epochs: sort keys of the suspended lanes (their pc: lanes of one loop end
@@ -819,11 +759,16 @@ hipError_t launch_exact_sites(const ExactPlan &p, uint64_t first, uint64_t n, co
                        perm, weight);
     return hipGetLastError();
 }
-hipError_t launch_exact_hist(const fi_site *sites, const fi_outcome *out, const uint32_t *weight, uint64_t n,
-                             fi_histogram *h, hipStream_t st) {
-    hipLaunchKernelGGL(fi_exact_hist_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, sites, out, weight, n, h);
+template <typename W>
+hipError_t launch_exact_hist(const fi_site *sites, const fi_outcome *out, const W *weight, uint64_t n, fi_histogram *h,
+                             hipStream_t st) {
+    hipLaunchKernelGGL(fi_exact_hist_kernel<W>, dim3(nblk(n, 256)), dim3(256), 0, st, sites, out, weight, n, h);
     return hipGetLastError();
 }
+template hipError_t launch_exact_hist(const fi_site *, const fi_outcome *, const uint32_t *, uint64_t, fi_histogram *,
+                                      hipStream_t);
+template hipError_t launch_exact_hist(const fi_site *, const fi_outcome *, const uint64_t *, uint64_t, fi_histogram *,
+                                      hipStream_t);
 hipError_t launch_exact_profile(const ExactPlan &p, const ExactProfCtx &c, uint64_t first, uint64_t n, hipStream_t st) {
     hipLaunchKernelGGL(fi_exact_profile_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, p, c, first, n);
     return hipGetLastError();
@@ -834,8 +779,8 @@ hipError_t launch_exact_consumers(const ExactPlan &p, const uint32_t *reg_cons, 
                        row);
     return hipGetLastError();
 }
-hipError_t launch_exact_dead(const ExactDead &d, fi_histogram *h, hipStream_t st) {
-    hipLaunchKernelGGL(fi_exact_dead_kernel, dim3(33), dim3(64), 0, st, d, h);
+hipError_t launch_exact_untried(const ExactUntried &d, fi_histogram *h, hipStream_t st) {
+    hipLaunchKernelGGL(fi_exact_untried_kernel, dim3(33), dim3(64), 0, st, d, h);
     return hipGetLastError();
 }
 hipError_t launch_exact_tick_sites(const ExactPlan &p, const TickMapCtx &c, uint64_t first, uint64_t n,
@@ -843,15 +788,6 @@ hipError_t launch_exact_tick_sites(const ExactPlan &p, const TickMapCtx &c, uint
                                    fi_site *tsites, uint8_t *disp, fi_outcome *res, uint64_t *weight, hipStream_t st) {
     hipLaunchKernelGGL(fi_exact_tick_sites_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, p, c, first, n, cls, sites,
                        keys, perm, tsites, disp, res, weight);
-    return hipGetLastError();
-}
-hipError_t launch_exact_tick_hist(const fi_site *tsites, const fi_outcome *out, const uint64_t *weight, uint64_t n,
-                                  fi_histogram *h, hipStream_t st) {
-    hipLaunchKernelGGL(fi_exact_tick_hist_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, tsites, out, weight, n, h);
-    return hipGetLastError();
-}
-hipError_t launch_exact_tick_dead(const ExactTickDead &d, fi_histogram *h, hipStream_t st) {
-    hipLaunchKernelGGL(fi_exact_tick_dead_kernel, dim3(32), dim3(64), 0, st, d, h);
     return hipGetLastError();
 }
 hipError_t launch_exact_mem_live(const ExactMemCtx &c, uint8_t *live, hipStream_t st) {

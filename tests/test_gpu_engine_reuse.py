@@ -203,6 +203,95 @@ def test_translated_kernels_do_not_cross_a_load():
     _same(run(e), run(_engine(flags=0)))
 
 
+def _fresh_each(make, steps):
+    """Each step on an engine of its own."""
+    fresh = {}
+    for name, step in steps:
+        e = make()
+        fresh[name] = step(e)
+        e.close()
+    return fresh
+
+
+def test_sources_do_not_leak_across_slots():
+    """Every kind of run leaves the two chunk slots (sites, outcomes, weights,
+    the tick map's and the capture's buffers) as the next kind expects them:
+    runs of different sources in a row on one engine equal the same calls on
+    fresh engines.  hello's exact campaign over x1..x31 | pc | result is 1,920
+    trials; chunks of 1,000 use both slots and end on a partial chunk."""
+    RESULT = 1 << 34
+
+    def exact(e, profile=False):
+        e.set_campaign(SEED, REGS_PC | RESULT, 1)
+        n = int(e.exact_info().trials)
+        assert n > 1000 and n % 1000
+        r = e.run_exact(0, n, profile=profile)
+        obs = {"out": r[0], "hist": _hist_dict(r[1])}
+        if profile:
+            obs["prof"] = r[2]
+        return obs
+
+    def capture(e):
+        e.set_campaign(SEED, REGS_PC | MEM, 1)
+        out, hist, cap = e.run_sites_capture(e.sample(0, 1500), cap_bytes=64)
+        return {"out": out, "hist": _hist_dict(hist), "stdout": cap.out, "stderr": cap.err, "out_len": cap.out_len,
+                "err_len": cap.err_len}
+
+    def trials(e):
+        e.set_campaign(SEED, REGS_PC | MEM, 1)
+        out, hist = e.run_trials(0, 2500)
+        return {"out": out, "hist": _hist_dict(hist)}
+
+    def atomic():
+        e = _engine(max_trials_per_launch=1000)
+        e.load_elf(workload_elf("hello"), ["hello"])
+        e.golden_run()
+        return e
+    steps = [("exact", exact), ("capture", capture), ("profile", lambda e: exact(e, True)), ("trials", trials),
+             ("exact again", exact)]
+    e = atomic()
+    used = {name: step(e) for name, step in steps}
+    e.close()
+    _same(used, _fresh_each(atomic, steps))
+    _same(used["exact again"], used["exact"])
+
+    # the timing model with the device map: the tick map's buffers and the 64-bit weights are made on
+    # first use and dropped when the work buffers grow -- from the exact tick campaign's trials to
+    # 1,500 to 3,000 slots here
+    def exact_ticks(e):
+        e.set_campaign(SEED, REGS_PC | RESULT, 1)
+        e.set_bits(0xFFFF)
+        n = int(e.exact_tick_info().trials)
+        assert 0 < n < 1500
+        out, hist = e.run_exact_ticks(0, n)
+        return {"out": out, "hist": _hist_dict(hist)}
+
+    def tick_trials(e):
+        e.set_campaign(SEED, REGS_PC, 1)
+        out, hist = e.run_tick_trials(0, 1500)
+        return {"out": out, "hist": _hist_dict(hist)}
+
+    def sites(e):
+        e.set_campaign(SEED, REGS_PC | MEM, 1)
+        out, hist = e.run_sites(e.sample(0, 3000))
+        return {"out": out, "hist": _hist_dict(hist)}
+
+    def timing():
+        e = _engine(max_trials_per_launch=4096)
+        e.load_elf(workload_elf("hello"), ["hello"])
+        e.set_cpu_model("timing")
+        e.golden_run()
+        e.set_tick_map("device")
+        return e
+    steps = [("exact ticks", exact_ticks), ("tick trials", tick_trials), ("sites", sites),
+             ("exact ticks again", exact_ticks)]
+    e = timing()
+    used = {name: step(e) for name, step in steps}
+    e.close()
+    _same(used, _fresh_each(timing, steps))
+    _same(used["exact ticks again"], used["exact ticks"])
+
+
 def test_work_growth_equals_a_fresh_engine():
     """Work buffers grown from 64 to 256 slots, with the tick and capture
     buffers already made at 64: three-chunk runs equal a fresh engine's."""

@@ -13,8 +13,9 @@ alternating R times, L = min(trials, the engine's trials per launch).
 
 --probe: for a kernel trace taken around this process in a run of its own.
 Only the first launch of the campaign, then fi_run_sites on the same chunk's
-sites, so that fi_exact_hist_kernel and fi_hist_kernel each run once on the
-same sites and outcomes.
+sites, so that fi_exact_hist_kernel (its uint32_t instantiation: a numInst
+campaign's weights) and fi_hist_kernel each run once on the same sites and
+outcomes.
 
 --memory: the memory words (structure 33) alone, by byte-liveness class
 (Engine.set_exact_memory): the one-time class build on its own (the first
